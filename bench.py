@@ -324,7 +324,7 @@ def pileup_main(args):
     host_s = time.perf_counter() - t0
     base = pl.stats()
     check = (int(len(centers)), float(tens.sum().item()), int(depth.sum().item()))
-    steps = args.steps if args.steps != 64 else 20
+    steps = args.steps
 
     def one_pass():
         _lib_check(pl.lib.cv_pileup_recount(pl.h, pl._stream()))
@@ -592,7 +592,7 @@ def exchange_main(args):
     nfl = int(bucket.numel())
     use_dist = dist.is_available() and dist.is_initialized()
     staged = use_dist and dist.get_backend() == "gloo"
-    steps = args.steps if args.steps != 64 else 50
+    steps = args.steps
     pieces = [("whole bucket (the tiny-share plan: one collective per step)", 0, nfl),
               ("dense part: fc4 / fc5 / heads gradients (under the convolution backward pass)", d, nfl),
               ("convolution gradients + loss header (behind the step)", 0, d),
@@ -653,7 +653,7 @@ def train_main(args):
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     gb = param.trainBatchSize if args.batch == BATCH else args.batch      # --batch: another global batch (default: the reference's)
-    steps = args.steps if args.steps != 64 else 20
+    steps = args.steps
     r = run_train(args.arch, gb, steps, args.warmup, rank, ws, dev, sync_loss=args.sync_loss,
                   options=dict({"train_overlap": args.overlap, "train_tiny_groups": args.tiny, "train_ksplit": args.ksplit,
                                 "train_side_streams": args.sides, "train_sched": args.sched},
@@ -683,7 +683,7 @@ def train_main(args):
 
 def run_infer(arch, batch, steps, warmup, rank, ws, dev, variant=None, batches=None):
     """`steps` passes of the inference hot path over batches resident in HBM; barrier + synchronize on both sides,
-    MAX over ranks.  -> (result dict, model, parameters, batches); the caller closes the model."""
+    MAX over ranks.  -> (result dict, model, parameters, batches, output of the last step); the caller closes the model."""
     import torch
     import torch.distributed as dist
     from clairvoyante_amd import clairvoyante_v3, clairvoyante_v3_slim, synth, _lib
@@ -787,7 +787,31 @@ def run_infer(arch, batch, steps, warmup, rank, ws, dev, variant=None, batches=N
                 "hbm_frac_compulsory": value / ws * 2176 / 1e9 / PEAK_HBM_GBS}
     res = {"value": value, "unit": "candidates/s", "ms_per_step": dt / steps * 1e3, "steps": steps,
            "roofline": roof, "kernels": stages, "per_rank_ms": per_rank}
-    return res, m, P, batches
+    return res, m, P, batches, out
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, out16):
+    """--dump-outputs DIR: what the timed path returned in its last step, predict_device's [batch, 16] float32
+    probabilities (base 0..3, zygosity 4..5, variant type 6..9, indel length 10..15), as DIR/out16.npy -- rank 0's own
+    shard.  The inputs are seeded, so two builds given the same arguments can be compared file for file.  An output
+    larger than DUMP_BYTES is written as a fixed, seeded sample of its rows, their indices beside it as
+    DIR/out16_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    a = out16.cpu().numpy()
+    rows_fn = os.path.join(dirname, "out16_rows.npy")
+    budget = DUMP_BYTES - 4096                   # (room for the two .npy headers)
+    if a.nbytes > budget:
+        k = budget // (a.shape[1] * a.itemsize + 8)
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=k, replace=False))
+        np.save(rows_fn, rows.astype(np.float64))
+        a = a[rows]
+    elif os.path.exists(rows_fn):
+        os.remove(rows_fn)                       # (left by an earlier, larger run)
+    np.save(os.path.join(dirname, "out16.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def host_legs(dev, rows=1000000, train_items=600000):
@@ -961,7 +985,8 @@ def order_sensitivity(got, want64, other=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default: infer 64, train 20, pileup 20, exchange 50)")
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--arch", default="full", choices=["full", "slim"])
     ap.add_argument("--batch", type=int, default=BATCH)
@@ -984,7 +1009,15 @@ def main():
                          "(BASELINE.json configs[3]); pileup: candidate extraction + tensor generation over "
                          "alignments resident in HBM (SURVEY.md 8f N4); exchange: only the all-reduce of the step's "
                          "gradient bucket and of its pieces (time, algorithm / bus bandwidth, RCCL's algorithm choice)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="infer mode: after the timed steps, write what the last step computed to DIR (dump_outputs)")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = {"infer": 64, "train": 20, "pileup": 20, "exchange": 50}[args.mode]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.mode != "infer" or args.dry):
+        ap.error("--dump-outputs writes the outputs of the inference path: --mode infer, without --dry")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_under_torchrun(args, sys.argv[1:])          # does not return
     protect_stdout()          # from here on only emit() reaches the real stdout
@@ -1008,7 +1041,9 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
 
-    res, m, P, batches = run_infer(args.arch, args.batch, args.steps, args.warmup, rank, ws, dev, variant=args.variant)
+    res, m, P, batches, out = run_infer(args.arch, args.batch, args.steps, args.warmup, rank, ws, dev, variant=args.variant)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     line = {"metric": "candidate tensors/sec", "value": res["value"], "unit": "candidates/s", "n_gpus": ws,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": res["ms_per_step"],
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
@@ -1026,7 +1061,7 @@ def main():
     # at N = 1 also at 1 250, one rank's share of that batch on 8 GPUs; at N > 1 also at 10 000 PER rank.
     if not args.no_extras and args.arch == "full" and args.variant is None:
         t_extra = time.perf_counter()
-        sres, sm, _sp, _sb = run_infer("slim", args.batch, 32, 4, rank, ws, dev, batches=batches[:16])
+        sres, sm, _sp, _sb, _so = run_infer("slim", args.batch, 32, 4, rank, ws, dev, batches=batches[:16])
         sm.close()
         line["slim"] = {"value": sres["value"], "unit": "candidates/s", "ms_per_step": sres["ms_per_step"], "steps": 32,
                         "kernels": [{"kernel_name": k["kernel_name"], "avg_ms": k["avg_ms"]} for k in sres["kernels"]],

@@ -393,16 +393,19 @@ def _dp_worker(rank, ws, port, tmp, arch, n, steps, rate):
     torch.distributed.destroy_process_group()
 
 
+# Several ranks on the one GPU: each rank and this pytest process hold the device open (so does the torch.distributed.run
+# launcher of `bench.py --gpus N`), and a shared GPU box allows at most six such processes at a time -- so these tests run
+# at most four ranks (the 8-rank sharding and merge logic is covered on the CPU by test_parallel_gloo.py).
 def _spawn(fn, args, nprocs=2):
     import torch.multiprocessing as mp
     port = 29900 + os.getpid() % 500
     mp.spawn(fn, args=(nprocs, port) + tuple(args), nprocs=nprocs, join=True)
 
 
-@pytest.mark.parametrize("arch,n,ws", [("full", 10000, 2), ("slim", 4001, 2), ("full", 10000, 8), ("slim", 4001, 3)])
+@pytest.mark.parametrize("arch,n,ws", [("full", 10000, 2), ("slim", 4001, 2), ("full", 10000, 4), ("slim", 4001, 3)])
 def test_data_parallel_step_equals_the_single_process_step(oracle, arch, n, ws, tmp_path):
-    """("full", 10000, 8) is BASELINE config 4 as it runs: train.py's batch of 10 000 split over 8 ranks = 1 250
-    candidates (79 groups, ragged) per rank, here as 8 processes on the one GPU (backend gloo)"""
+    """("full", 10000, 4): train.py's batch of 10 000 split over 4 ranks = 2 500 candidates (157 groups, ragged) per rank,
+    here as 4 processes on the one GPU (backend gloo)"""
     steps = 3
     _spawn(_dp_worker, (str(tmp_path), arch, n, steps, 0.0), nprocs=ws)
     r0 = np.load(str(tmp_path / "rank0.npz"))
@@ -432,7 +435,7 @@ def test_data_parallel_step_equals_the_single_process_step(oracle, arch, n, ws, 
         sz = P[name].size
         sl = slice(off, off + sz); off += sz
         # the sum of the shard gradients against the full-batch gradient at the SAME weights: summation order only
-        # (shards of up to 400 groups -- 1 250 on 8 ranks, 5 000 on 2 -- run the small-batch step, whose fc4 forward is
+        # (shards of up to 400 groups -- 2 500 on 4 ranks, 5 000 on 2 -- run the small-batch step, whose fc4 forward is
         # eight k ranges added in order, against ONE ascending-k chain for the whole batch: 1e-4, the bound
         # test_alpha_dropout_* uses for that variant; measured 2.9e-5 on fc4/kernel with two shards of 5 000)
         ksplit_shard = arch == "full" and ((n + ws - 1) // ws + 15) // 16 <= 400 < (n + 15) // 16
@@ -450,7 +453,7 @@ def test_data_parallel_step_equals_the_single_process_step(oracle, arch, n, ws, 
     m.close()
 
 
-@pytest.mark.parametrize("ws,n", [(2, 1), (8, 3)])
+@pytest.mark.parametrize("ws,n", [(2, 1), (4, 3)])
 def test_step_with_empty_shards(oracle, tmp_path, ws, n):
     """a global batch smaller than the rank count leaves ranks without candidates: they still take part in the
     exchange (zero gradient, zero losses) and every rank applies the same update"""
@@ -525,9 +528,9 @@ def _epoch_worker(rank, ws, port, tmp, binfn, n):
     torch.distributed.destroy_process_group()
 
 
-@pytest.mark.parametrize("ws", [2, 8])
+@pytest.mark.parametrize("ws", [2, 4])
 def test_data_parallel_epoch_equals_the_single_process_epoch(oracle, tmp_path, monkeypatch, ws):
-    """train.run_epoch under two / eight ranks: every rank walks the same schedule on its slice of each batch; training sums
+    """train.run_epoch under two / four ranks: every rank walks the same schedule on its slice of each batch; training sums
     come out of the exchanged loss header, validation sums through parallel.allreduce_scalar (train.py:113-123)"""
     from clairvoyante_amd import param, train, utils_v2
     n = 26000
@@ -585,11 +588,11 @@ def test_callvar_command_line_under_two_ranks_writes_the_single_rank_vcf(oracle,
     assert not [f for f in os.listdir(str(tmp_path)) if ".rank" in f]
 
 
-@pytest.mark.parametrize("ws,sizes", [(2, (1500, 20000, 700)), (8, (1500, 20000, 700, 90, 0, 2500, 33, 1200, 640, 17, 3100))])
+@pytest.mark.parametrize("ws,sizes", [(2, (1500, 20000, 700)), (4, (1500, 20000, 700, 90, 0, 2500, 33, 1200, 640, 17, 3100))])
 def test_callvar_command_line_under_several_ranks_over_a_list_of_files(oracle, tmp_path, ws, sizes):
-    """--tensor_fn a.gz,b.gz,c.gz,... under two / eight ranks: file k belongs to rank k % ws -- the form that scales (no
+    """--tensor_fn a.gz,b.gz,c.gz,... under two / four ranks: file k belongs to rank k % ws -- the form that scales (no
     rank inflates input it does not call; the reference's own recipe is one job per chunk, README.md:184-202); the VCF
-    equals the concatenation of the single-process runs (bodies in list order).  Eight ranks over 11 files: ranks with one
+    equals the concatenation of the single-process runs (bodies in list order).  Four ranks over 11 files: ranks with three
     and with two files, an empty file."""
     import subprocess
     import test_gpu_pipeline as tp
@@ -701,40 +704,40 @@ def test_bench_line_under_two_ranks_sharing_the_gpu(tmp_path):
 
 
 @pytest.mark.parametrize("mode", ["infer", "train", "exchange"])
-def test_bench_line_under_eight_ranks_sharing_the_gpu(mode):
-    """the driver's 8-GPU command, functionally: `python bench.py --gpus 8` with eight real ranks on the one GPU (backend
-    gloo, CV_SHARE_DEVICES) -- one line, n_gpus = rccl_ranks = 8; in train mode the line separates the exchange from the
+def test_bench_line_under_four_ranks_sharing_the_gpu(mode):
+    """the driver's N-GPU command, functionally: `python bench.py --gpus 4` with four real ranks on the one GPU (backend
+    gloo, CV_SHARE_DEVICES) -- one line, n_gpus = rccl_ranks = 4; in train mode the line separates the exchange from the
     compute (exchange_ms, compute_ms_per_step, exchange_hidden_frac)"""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CV_SHARE_DEVICES="1", CV_DIST_BACKEND="gloo", PYTHONPATH=ROOT)
     extra = ["--mode", mode] if mode != "infer" else ["--no-extras"]
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--no-cpu"] + extra,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--no-cpu"] + extra,
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     b = lines[0]
-    assert b["n_gpus"] == 8 and b["rccl_ranks"] == 8 and b["backend"] == "gloo"
+    assert b["n_gpus"] == 4 and b["rccl_ranks"] == 4 and b["backend"] == "gloo"
     if mode == "exchange":       # only the bucket all-reduce: whole bucket, its two pieces, a fifth; time + bandwidths per piece
         assert b["unit"] == "GB/s" and b["value"] > 0 and len(b["pieces"]) == 4
         assert b["pieces"][0]["bytes"] == 4 * (1631496 + 16) and b["pieces"][1]["bytes"] + b["pieces"][2]["bytes"] == b["pieces"][0]["bytes"]
-        assert all(p["ms"] > 0 and abs(p["busbw_GBps"] - p["algbw_GBps"] * 2 * 7 / 8) < 1e-9 * max(1.0, p["busbw_GBps"]) for p in b["pieces"])
+        assert all(p["ms"] > 0 and abs(p["busbw_GBps"] - p["algbw_GBps"] * 2 * 3 / 4) < 1e-9 * max(1.0, p["busbw_GBps"]) for p in b["pieces"])
         return
-    assert b["value"] > 1e3     # functional: 8 ranks share one GPU, gloo through the host
+    assert b["value"] > 1e3     # functional: 4 ranks share one GPU, gloo through the host
     if mode == "train":
         assert b["config"]["global_batch"] == 10000 and b["scaling"] == "strong"
         assert b["exchange_ms"] > 0 and b["compute_ms_per_step"] > 0 and 0.0 <= b["exchange_hidden_frac"] <= 1.0
         assert b["exchange_bytes"] == 4 * (1631496 + 16) and np.isfinite(b["final_loss"])
         # the step's own exchange as bandwidths (what the first run on real links is read by), and the rank check that ran
-        # before anything was timed: eight ranks counted, here on ONE device, flagged as shared
+        # before anything was timed: four ranks counted, here on ONE device, flagged as shared
         assert abs(b["exchange_algbw_GBps"] - b["exchange_bytes"] / (b["exchange_ms"] * 1e-3) / 1e9) <= 1e-6 * b["exchange_algbw_GBps"]
-        assert abs(b["exchange_busbw_GBps"] - b["exchange_algbw_GBps"] * 2 * 7 / 8) <= 1e-9 * max(1.0, b["exchange_busbw_GBps"])
-        assert b["counted_ranks"] == 8 and b["distinct_devices"] == 1 and b["shared_devices"] is True
-        assert b["exchange_plan"] == "one"          # 1 250 candidates per rank: one collective per step
+        assert abs(b["exchange_busbw_GBps"] - b["exchange_algbw_GBps"] * 2 * 3 / 4) <= 1e-9 * max(1.0, b["exchange_busbw_GBps"])
+        assert b["counted_ranks"] == 4 and b["distinct_devices"] == 1 and b["shared_devices"] is True
+        assert b["exchange_plan"] == "one"          # 2 500 candidates per rank: one collective per step
         assert b["other_plan"]["plan"] == "split" and b["other_plan"]["ms_per_step"] > 0      # ... and the same steps under the other plan
     else:
         assert b["scaling"] == "weak" and b["config"]["batch"] == 65536
         pr = b["per_rank_ms"]                       # a straggler would show: slowest / fastest rank, ms per step
-        assert 0 < pr["min"] <= pr["max"] and 0 <= pr["argmax_rank"] < 8 and abs(pr["max"] - b["ms_per_step"]) < 1e-6 * pr["max"]
+        assert 0 < pr["min"] <= pr["max"] and 0 <= pr["argmax_rank"] < 4 and abs(pr["max"] - b["ms_per_step"]) < 1e-6 * pr["max"]

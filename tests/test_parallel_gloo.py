@@ -42,6 +42,12 @@ def test_a_mistyped_exchange_plan_is_refused_everywhere(monkeypatch):
     assert parallel.exchange_mode(Stub()) == "split"
 
 
+def _barrier():
+    """dist.barrier() asks torch for the machine's accelerator whatever the backend, which starts the HIP runtime and
+    opens the GPU of a GPU box in every rank; these CPU ranks synchronise through a gloo all-reduce of a CPU tensor"""
+    dist.all_reduce(torch.zeros(1))
+
+
 def _worker(rank, ws, port, tmp, n):
     sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(ws),
@@ -94,7 +100,7 @@ def _worker(rank, ws, port, tmp, n):
     dec = [float(got[2 * k]) + float(got[2 * k + 1]) for k in range(5)]
     assert np.allclose(dec[0:4], parts_all[0:4], rtol=1e-7)
     assert got[10] == ws and abs(dec[4] / got[10] - l2) <= 5e-7 * l2      # fp32 sum of ws equal (hi, lo) pairs: exact at powers of two only
-    dist.barrier()
+    _barrier()
     dist.destroy_process_group()
     open(os.path.join(tmp, "ok%d" % rank), "w").write("ok")
 
@@ -133,6 +139,8 @@ def _callvar_worker(rank, ws, port, tmp, tfn, block_lines):
     import io
     import types
     from clairvoyante_amd import callVar, parallel, utils_v2
+    # pageable row buffers: the pool's page-locked ones would ask torch for a GPU and, on a GPU box, open it in all ranks
+    utils_v2._pinned.enabled = False
     from oracle import cv_oracle as O
     import common
     parallel.init_from_env(backend="gloo")
@@ -158,12 +166,12 @@ def _callvar_worker(rank, ws, port, tmp, tfn, block_lines):
     frag.close()
     with open("%s.rank%d.idx" % (call_fn, rank), "w") as f:
         f.write("".join("%d %d\n" % e for e in index))
-    dist.barrier()
+    _barrier()
     if rank == 0:
         with open(call_fn, "w") as fh:
             callVar.PrintVCFHeader(args, fh)
             callVar.merge_fragments(call_fn, ws, fh)
-    dist.barrier()
+    _barrier()
     dist.destroy_process_group()
 
 
