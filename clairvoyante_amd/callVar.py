@@ -42,11 +42,20 @@ _F = param.flankingBaseNum
 
 def _top2_products(t, z, l):
     """fp32 products of the best and second-best probabilities of the three softmax heads
-    (np.sort(x)[::-1][0/1], callVar.py:69-72); evaluated left to right in fp32 like NumPy."""
-    st = -np.sort(-t, axis=1); sz = -np.sort(-z, axis=1); sl = -np.sort(-l, axis=1)
+    (np.sort(x)[::-1][0/1], callVar.py:69-72); evaluated left to right in fp32 like NumPy.  The order is NumPy's
+    ascending sort reversed: NaN first, equal values (+0 beside -0, NaN beside NaN) the higher index first -- a
+    stable argsort, so that it does not depend on which sort NumPy picks for a row ("Decisions")."""
+    def desc(h):
+        return np.take_along_axis(h, np.argsort(h, axis=1, kind="stable")[:, ::-1], axis=1)
+    st = desc(t); sz = desc(z); sl = desc(l)
     p1 = (st[:, 0] * sz[:, 0]) * sl[:, 0]
     p2 = (st[:, 1] * sz[:, 1]) * sl[:, 1]
     return p1.astype(np.float32), p2.astype(np.float32)
+
+
+def _base_order(base):
+    """base.argsort()[::-1] per row (callVar.py:81): descending, NaN first, the higher index first among equal values"""
+    return np.argsort(base, axis=1, kind="stable")[:, ::-1]
 
 
 def _qual(p1, p2):
@@ -142,8 +151,7 @@ def Output(args, call_fh, num, XBatch, posBatch, base, z, t, l):
     varZyg = np.argmax(z, axis=1)
     varLen = np.argmax(l, axis=1)
     p1, p2 = _top2_products(t[keep], z[keep], l[keep])
-    # argsort()[::-1]: descending, the higher index first among equal values (callVar.py:81)
-    order = np.argsort(base[keep], axis=1, kind="stable")[:, ::-1]
+    order = _base_order(base[keep])
     dp = _depth(X[keep])
     lines = []
     for i, j in enumerate(keep):

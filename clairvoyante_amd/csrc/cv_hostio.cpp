@@ -763,6 +763,16 @@ int vcf_record(const vcf_job &J, int64_t i, std::string &out, int64_t *nrec)
     }
     if (varType == 0 && !J.show_ref) return 0;
     const float *q = J.qual + i * 4;
+    // callVar.py:72 computes int(quality) for every kept row before it looks at the depth: NaN raises ValueError there,
+    // +-Inf OverflowError, and a C conversion of either is undefined
+    const double ratio = ((double)q[1] + 1e-300) / ((double)q[0] + 1e-300);
+    const double qd = -4.343 * log(ratio);
+    if (!(fabs(qd) < 2.0e9)) {
+        cv_set_error("cv_format_vcf: record %lld: quality is not a finite number (top-2 products %g, %g)", (long long)i,
+                     (double)q[0], (double)q[1]);
+        return 1;
+    }
+    const int qv = (int)qd;                                                         // int(): truncation toward zero
     const float dp = q[2];
     if (dp == 0.0f) return 0;
     if (!(fabsf(dp) < 2.0e9f)) { cv_set_error("cv_format_vcf: record %lld: depth is not a finite count", (long long)i); return 1; }
@@ -835,8 +845,6 @@ int vcf_record(const vcf_job &J, int64_t i, std::string &out, int64_t *nrec)
             alt[0] = sq[F]; alt_len = 1;
         }
     }
-    const double ratio = ((double)q[1] + 1e-300) / ((double)q[0] + 1e-300);
-    const int qv = (int)(-4.343 * log(ratio));                                      // int(): truncation toward zero
     const char *gt = varType == 0 ? "0/0" : (c[1] == 0 ? "0/1" : "1/1");
     const char *filt = !J.has_qual ? "." : (qv >= J.qual_min ? "PASS" : "LowQual");
     // the line, assembled by hand (snprintf costs more than everything above): "%s\t%d\t.\t%s\t%s\t%d\t%s\t%s\tGT:GQ:DP:AF\t%s:%d:%d:%.4f"

@@ -13,8 +13,11 @@
 // 4 (4 w + r) .. +3 -- stored as [group][pooled row][tile][lane] (512 B per row and tile instead of 4 KiB).
 // ---------------------------------------------------------------------------
 
-// rows[0..P-2] = the P-1 older activated rows of the window (oldest first), v = the newest, o = their maximum
-template <int P>
+// rows[0..P-2] = the P-1 older rows of the window (oldest first), v = the newest, o = their maximum.
+// ACT: the rows are ACTIVATIONS, whose maximum orders -0 below +0 (v_max_f32); a row holds the maximum only with its sign,
+// so that a window of -0 (a pre-activation in (-2^-25, 0)) and +0 selects a +0 row -- the row whose own selu' is the one
+// cv_unpool.hpp reads off the pooled +0.  Without ACT the rows are pre-activations, whose maximum is the row.
+template <int P, bool ACT = false>
 __device__ __forceinline__ unsigned pool_code4(const f4 (&older)[P > 1 ? P - 1 : 1], f4 v, f4 o)
 {
     unsigned c = 0;
@@ -22,7 +25,11 @@ __device__ __forceinline__ unsigned pool_code4(const f4 (&older)[P > 1 ? P - 1 :
     for (int r = 0; r < 4; r++) {
         int idx = P - 1;
 #pragma unroll
-        for (int d = P - 2; d >= 0; d--) idx = older[d][r] == o[r] ? d : idx;      // the lowest offset that holds the maximum
+        for (int d = P - 2; d >= 0; d--) {
+            bool hit = older[d][r] == o[r];
+            if constexpr (ACT) hit = hit && __builtin_signbit(older[d][r]) == __builtin_signbit(o[r]);
+            idx = hit ? d : idx;                                               // the lowest offset that holds the maximum
+        }
         (void)v;
         c |= (unsigned)idx << (4 * r);
     }
@@ -122,7 +129,7 @@ __global__ __launch_bounds__(256) void conv1_tm(const float *__restrict__ x, int
                         f4 older[POOL - 1];
 #pragma unroll
                         for (int j = 0; j < POOL - 1; j++) older[j] = pw[j][w];
-                        cw[w] = pool_code4<POOL>(older, v[w], o[w]);
+                        cw[w] = pool_code4<POOL, true>(older, v[w], o[w]);
                     }
                     code_tm[((size_t)g * HOUT + (h - (POOL - 1))) * 64 + lane] = (u32x2){cw[0] | (cw[1] << 16), cw[2] | (cw[3] << 16)};
                 }
@@ -501,7 +508,7 @@ __global__ __launch_bounds__(256, 2) void conv_tm(const f4 *__restrict__ in_tm, 
                         f4 older[POOL - 1];
 #pragma unroll
                         for (int j = 0; j < POOL - 1; j++) older[j] = pw[j][w];
-                        cw[w] = pool_code4<POOL>(older, v[w], o[w]);
+                        cw[w] = pool_code4<POOL, true>(older, v[w], o[w]);
                     }
                     u32x2 *cp = reinterpret_cast<u32x2 *>(act_tm);
                     cp[(((size_t)g * HOUT + (h - (POOL - 1))) * NT + nt) * 64 + lane] = (u32x2){cw[0] | (cw[1] << 16), cw[2] | (cw[3] << 16)};
@@ -873,7 +880,7 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void conv3_rot(const f4 *__restri
 #pragma unroll
                 for (int w = 0; w < 4; w++) {
                     const f4 older[2] = {tp[(R + 1) % 3][w], tp[(R + 2) % 3][w]};
-                    cw[w] = pool_code4<3>(older, tp[R][w], max3_4(tp[0][w], tp[1][w], tp[2][w]));
+                    cw[w] = pool_code4<3, true>(older, tp[R][w], max3_4(tp[0][w], tp[1][w], tp[2][w]));   // (SAVE: activations)
                 }
                 code_tm[(((size_t)g * HOUT + (h - (POOL - 1))) * NT + nt) * 64 + lane] = (u32x2){cw[0] | (cw[1] << 16), cw[2] | (cw[3] << 16)};
             }

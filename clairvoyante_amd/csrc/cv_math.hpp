@@ -55,7 +55,8 @@ constexpr float SELU_SA = (float)(1.0507009873554804934193349852946 * 1.67326324
 // expf_fixed, y*2^z by one v_ldexp_f32 (the product is a normal number), and scale*alpha*(y - 1) as ONE fused
 // multiply-add with the product constant -- 18 element operations per value where scale*(alpha*(expf_fixed(x)-1))
 // took 21, a little MORE accurate (max |err| 1.2e-7 vs 2.0e-7 over all negative floats) and monotone over every
-// fp32 input (cv_selu_sweep).  The select is `x < 0 ? neg : pos`, which routes NaN (and -0) to pos.
+// fp32 input (cv_selu_sweep).  The select is `x < 0 ? neg : |pos|`, which routes NaN and -0 to pos; a pre-activation of -0
+// gives +0 (tf.where(x >= 0) takes the x branch there, and selu' from the output must read SCALE off it, see below).
 // The negative branch carries the SIGN of its input even where its value rounds to zero (-2^-25 < x < 0: exp(x) rounds to 1
 // and the result is -0.0, computed as -(SA - SA*y)): the backward pass takes selu' from the layer OUTPUT (cv_unpool.hpp:
 // sign bit set -> y + SA, else SCALE), and an output of +0 there would read as the x >= 0 branch -- one element in ~3e7,
@@ -70,7 +71,7 @@ __device__ __forceinline__ float selu(float x)
         const float e = __builtin_amdgcn_exp2f(x * 1.44269504088896341f);       // x <= -104: 0 (the fma then gives -SA)
         const float neg = __builtin_fmaf(e, SELU_SA, -SELU_SA);
         const float pos = SELU_SCALE * x;
-        return x < 0.0f ? neg : pos;
+        return x < 0.0f ? neg : __builtin_fabsf(pos);
     }
 #endif
     const float xc = __builtin_amdgcn_fmed3f(x, -87.33654475055310f, 0.0f);
@@ -88,7 +89,7 @@ __device__ __forceinline__ float selu(float x)
     y = __builtin_ldexpf(y, (int)z);
     const float mag = __builtin_fmaf(y, -SELU_SA, SELU_SA);      // scale*alpha*(1 - y) >= +0
     const float pos = SELU_SCALE * x;
-    return x < 0.0f ? -mag : pos;                                // (the negation is a source modifier of the select)
+    return x < 0.0f ? -mag : __builtin_fabsf(pos);               // (negation and |.| are source modifiers of the select)
 }
 
 // Two SELUs at once on the packed fp32 pipe (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: two IEEE operations per
@@ -128,8 +129,8 @@ __device__ __forceinline__ f2v selu2(f2v x)
     const f2v mag = __builtin_elementwise_fma(y, (f2v)(-SELU_SA), (f2v)(SELU_SA));
     const f2v pos = SELU_SCALE * x;
     f2v o;
-    o[0] = x[0] < 0.0f ? -mag[0] : pos[0];
-    o[1] = x[1] < 0.0f ? -mag[1] : pos[1];
+    o[0] = x[0] < 0.0f ? -mag[0] : __builtin_fabsf(pos[0]);
+    o[1] = x[1] < 0.0f ? -mag[1] : __builtin_fabsf(pos[1]);
     return o;
 }
 

@@ -12,27 +12,30 @@ __global__ void call_postproc(const float *__restrict__ x, const float *__restri
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float *o = out16 + (size_t)i * 16;
-    // np.argmax: first maximum; np.sort()[::-1]: descending values
-    auto top2 = [](const float *p, int cnt, int &am, float &v1, float &v2) {
-        am = 0; v1 = p[0]; v2 = -__builtin_inff();
+    // NumPy's order ("Decisions"): NaN sorts above every number.  np.argmax returns the FIRST maximum or
+    // the first NaN; np.sort()[::-1] and argsort()[::-1] list equal values -- NaN among NaN, +0 beside -0 -- the
+    // HIGHER index first.  `ahead(v, w)`: v, met after w, goes before it in the descending order.
+    auto ahead = [](float v, float w) { return v != v || (w == w && v >= w); };
+    auto top2 = [&](const float *p, int cnt, int &am, float &v1, float &v2) {
+        am = 0;
+        int s1 = 0, s2 = -1;
         for (int k = 1; k < cnt; k++) {
-            float v = p[k];
-            if (v > v1) { v2 = v1; v1 = v; am = k; }
-            else if (v > v2) v2 = v;
+            const float v = p[k];
+            if (p[am] == p[am] && (v != v || v > p[am])) am = k;
+            if (ahead(v, p[s1])) { s2 = s1; s1 = k; }
+            else if (s2 < 0 || ahead(v, p[s2])) s2 = k;
         }
+        v1 = p[s1]; v2 = p[s2];
     };
     int at, az, al; float t1, t2, z1, z2, l1, l2;
     top2(o + 6, 4, at, t1, t2);
     top2(o + 4, 2, az, z1, z2);
     top2(o + 10, 6, al, l1, l2);
-    // base[j].argsort()[::-1] : descending by (value, index) -- the HIGHER index
-    // wins ties (callVar.py:81-83)
+    // base[j].argsort()[::-1] (callVar.py:81-83): the same descending order
     int b1 = 0, b2 = -1;
-    for (int k = 1; k < 4; k++)
-        if (o[k] >= o[b1]) b1 = k;
-    for (int k = 0; k < 4; k++) {
-        if (k == b1) continue;
-        if (b2 < 0 || o[k] >= o[b2]) b2 = k;
+    for (int k = 1; k < 4; k++) {
+        if (ahead(o[k], o[b1])) { b2 = b1; b1 = k; }
+        else if (b2 < 0 || ahead(o[k], o[b2])) b2 = k;
     }
     int32_t *c = call + (size_t)i * 8;
     c[0] = at; c[1] = az; c[2] = al; c[3] = b1; c[4] = b2; c[5] = 0; c[6] = 0; c[7] = 0;

@@ -281,7 +281,11 @@ __global__ void b_pool_selu(const float *__restrict__ gpool, const float *__rest
         for (int d = 0; d < p; d++) {
             float v = cvm::selu(b[(size_t)(ho + d) * row]);
             int hh = ho + d;
-            if (hh < h ? v >= me_act : v > me_act) { win = false; break; }   // first maximum wins
+            // first maximum wins; -0 below +0, as in the forward pooling
+            const bool zz = v == 0.0f && me_act == 0.0f;
+            const bool gt = v > me_act || (zz && !__builtin_signbit(v) && __builtin_signbit(me_act));
+            const bool ge = (v >= me_act && !zz) || (zz && !(__builtin_signbit(v) && !__builtin_signbit(me_act)));
+            if (hh < h ? ge : gt) { win = false; break; }
         }
         if (win) acc += gpool[((size_t)i * Ho + ho) * row + e];
     }

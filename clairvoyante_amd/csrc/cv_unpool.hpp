@@ -5,7 +5,7 @@
 // stride 1 VALID):  pooled[ho] = max_d act[ho + d],  act = selu(pre).  Backward, per channel / base / candidate:
 //     gpre[h] = selu'(pre[h]) * sum over the windows ho = h-d (d = 0..P-1) whose FIRST maximum sits at offset d
 //               of gpool[ho]
-// A window's maximum IS the activation of the row it selects, so selu'(pre[h]) = selu'-from-output(pooled[ho]) for
+// A window's maximum IS the activation of the row it selects, sign of a zero included (pool_code4<P, true>), so selu'(pre[h]) = selu'-from-output(pooled[ho]) for
 // every window that selects h: the factor is applied to each window's gradient as it arrives,
 //     gs[ho] = gpool[ho] * selu'-from-output(pooled[ho]),   gpre[h] = sum_{d = P-1 .. 0} [code[h-d] == d] gs[h-d]
 // (windows in ascending order).  No pre-pool activation is read.  Differs from "sum first, multiply once" by one
@@ -17,7 +17,8 @@ typedef float unp_f4 __attribute__((ext_vector_type(4)));
 
 // d selu / d pre-activation expressed through the layer OUTPUT y = selu(pre):
 //   pre >= 0  <=>  sign bit of y clear : SCALE ;   pre < 0 : SCALE*ALPHA*exp(pre) = y + SCALE*ALPHA
-// (cvm::selu keeps the sign of a negative input on an output that rounds to zero: -0.0 is the x < 0 branch, +0.0 is x = 0.)
+// (cvm::selu keeps the sign of a negative input on an output that rounds to zero: -0.0 is the x < 0 branch, +0.0 is
+// x = +0 or -0.)
 __device__ __forceinline__ float cv_selu_grad_from_out(float y)
 {
     return (int32_t)__builtin_bit_cast(uint32_t, y) >= 0 ? cvm::SELU_SCALE : y + cvm::SELU_SCALE * cvm::SELU_ALPHA;

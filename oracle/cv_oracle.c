@@ -120,7 +120,7 @@ float cvo_expf(float x)
 static const float SELU_SA = (float)(1.0507009873554804934193349852946 * 1.6732632423543772848170429916717);
 static inline float cvo_selu(float x)
 {
-    if (x >= 0.0f) return SELU_SCALE * x;
+    if (x >= 0.0f) return fabsf(SELU_SCALE * x);               /* -0 -> +0: +0 is the x >= 0 branch (as on the device) */
     if (x != x) return SELU_SCALE * x;                          /* NaN stays NaN (the device's select does the same) */
     float xc = x < -87.33654475055310f ? -87.33654475055310f : x;   /* exp(x) - 1 is -1 below the flush threshold */
     float z = __builtin_rintf(xc * 1.44269504088896341f);
@@ -241,6 +241,16 @@ static void selu_inplace_copy(const float *pre, float *act, int n)
     for (int i = 0; i < n; i++) act[i] = cvo_selu(pre[i]);
 }
 
+/* max of two pooled values: fmaxf (a NaN loses to a number), and -0 below +0 -- a window holding both gives +0 whatever
+ * their order, as on the device (v_max_f32; the tile kernels pool pre-activations, where the +0 is the larger one), and
+ * the backward pass routes to the first +0 row: the selected row's activation is the pooled value, sign included.
+ * glibc's fmaxf returns its second operand for +0 / -0, which made the result depend on the order in the window. */
+static inline float cvo_pool_max(float m, float v)
+{
+    if (m == 0.0f && v == 0.0f) return (signbit(m) && signbit(v)) ? -0.0f : 0.0f;
+    return fmaxf(m, v);
+}
+
 /* max_pooling2d (p,1) stride 1 VALID over h; in [H][4][c] -> out [H-p+1][4][c] */
 static void pool_h(const float *in, int H, int c, int p, float *out)
 {
@@ -248,7 +258,7 @@ static void pool_h(const float *in, int H, int c, int p, float *out)
     for (int h = 0; h < Ho; h++)
         for (int i = 0; i < row; i++) {
             float m = in[(size_t)h * row + i];
-            for (int d = 1; d < p; d++) m = fmaxf(m, in[(size_t)(h + d) * row + i]);
+            for (int d = 1; d < p; d++) m = cvo_pool_max(m, in[(size_t)(h + d) * row + i]);
             out[(size_t)h * row + i] = m;
         }
 }
@@ -580,13 +590,13 @@ double cvo_loss_grad(const cvo_arch *a, const float *const *P, const float *x, c
         for (int l = 2; l >= 0; l--) {
             int H = s.hc[l], C = a->cout[l], cin = s.cin[l], kh = a->kh[l], p = a->pool[l];
             int row = CVO_W * C, Ho = s.hp[l];
-            /* pool backward: route to the first maximum in the window */
+            /* pool backward: route to the first maximum in the window, -0 below +0 as in cvo_pool_max */
             for (int h = 0; h < Ho; h++)
                 for (int e = 0; e < row; e++) {
                     int best = 0; float m = rec[L.act[l] + (size_t)h * row + e];
                     for (int d = 1; d < p; d++) {
                         float v = rec[L.act[l] + (size_t)(h + d) * row + e];
-                        if (v > m) { m = v; best = d; }
+                        if (v > m || (v == 0.0f && m == 0.0f && !signbit(v) && signbit(m))) { m = v; best = d; }
                     }
                     g[L.act[l] + (size_t)(h + best) * row + e] += g[L.pooled[l] + (size_t)h * row + e];
                 }

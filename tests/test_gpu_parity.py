@@ -209,11 +209,7 @@ def test_forced_launch_shapes_give_the_same_bits(setup, n):
     m.setOption("impl", 1); m.setOption("variant", common.DEFAULT_VARIANT); m.setOption("chunk", 65536)
     xd = synth.make_candidates(n, seed=83, device="cuda")
     want = m.predict_device(xd).cpu().numpy()
-    settings = [{"infer_flat": 0}, {"infer_flat": 2}, {"infer_fc4_one_groups": 65536}, {"infer_fc4_one_groups": 0}, {"slim_waves": 4}, {"slim_waves": 8}, {"slim_small_groups": 65536},
-                {"slim_small_groups": 0}, {"infer_slab_groups": 0},
-                {"infer_slab_groups": 65536}, {"dense_rag": -1, "infer_slab_groups": 65536}]
-    settings += [{"dense_rag": s, "infer_slab_groups": 65536, "infer_flat": 2 if s % 2 else 0} for s in range(4, 15)]
-    defaults = {"infer_flat": 1, "infer_fc4_one_groups": 80, "slim_waves": 0, "slim_small_groups": -1, "infer_slab_groups": -1, "dense_rag": 0}
+    settings, defaults = common.FORCED_LAUNCH_SETTINGS, common.FORCED_LAUNCH_DEFAULTS
     try:
         for st in settings:
             for k, v in defaults.items():
@@ -239,10 +235,9 @@ def test_small_pass_shapes_give_the_same_bits(setup, n):
     m.setOption("impl", 1); m.setOption("variant", common.DEFAULT_VARIANT); m.setOption("chunk", 65536)
     xd = synth.make_candidates(n, seed=89, device="cuda")
     want = m.predict_device(xd).cpu().numpy()
-    defaults = {"dbg0": 0, "dbg1": 0, "infer_fc4_one_groups": 80, "slim_small_groups": -1}
+    defaults = common.SMALL_PASS_DEFAULTS
     try:
-        for st in ({"dbg0": 5}, {"dbg0": 6}, {"dbg1": 4}, {"infer_fc4_one_groups": 0}, {"infer_fc4_one_groups": 65536},
-                   {"slim_small_groups": 0}, {"slim_small_groups": 65536}):
+        for st in common.SMALL_PASS_SETTINGS:
             for k, v in defaults.items():
                 m.setOption(k, v)
             for k, v in st.items():

@@ -51,11 +51,13 @@ def _split(flat, oracle, shapes):
     return out
 
 
-def compare_step(oracle, arch, n, rate, lam, lr=1e-3, seed=9, options=None, ksplit=None):
+def compare_step(oracle, arch, n, rate, lam, lr=1e-3, seed=9, options=None, ksplit=None, data=None, params=None):
     """One m.train(x, y) with default options (or `options`) vs the oracle; returns the measured distances (for the
-    logs).  ksplit: whether this step's fc4 forward runs as eight k ranges (default: what the library does at this size)."""
-    x, y = _data(n, seed=seed)
-    P = common.bench_params(oracle, arch)
+    logs).  ksplit: whether this step's fc4 forward runs as eight k ranges (default: what the library does at this size).
+    data = (x, y) / params: a batch / weight set of the caller's instead of the seeded ones."""
+    x, y = _data(n, seed=seed) if data is None else data
+    assert x.shape[0] == n
+    P = common.bench_params(oracle, arch) if params is None else params
     m = _model(arch); m.setParameters(P)
     for k, v in (options or {}).items():
         m.setOption(k, v)

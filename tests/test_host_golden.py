@@ -507,3 +507,47 @@ def test_native_formatter_rejects_malformed_positions():
         callVar.format_records(_args(False, None, None, "S"), 1, X, ["chr1:12x:" + "A" * 33], call, q)
     with pytest.raises(_lib.CvError):
         callVar.format_records(_args(False, None, None, "S"), 1, X, ["chr1:12:ACGT"], call, q)
+
+
+def test_native_formatter_refuses_a_quality_that_is_not_a_number():
+    """callVar.py:72 takes int() of the quality of every kept row before it looks at the depth: NaN raises ValueError,
+    +-Inf OverflowError.  cv_format_vcf refuses the record and names it; a row that gives no record is not looked at."""
+    from clairvoyante_amd import callVar, _lib
+    X = np.ones((3, 33, 4, 4), np.float32)
+    pos = ["chr1:%d:%s" % (100 + i, "A" * 33) for i in range(3)]
+    call = np.array([[1, 0, 0, 1, 2, 0, 0, 0]] * 3, np.int32)
+    good = np.array([[0.9, 0.1, 8, 0]] * 3, np.float32)
+    assert len(callVar.format_records(_args(False, None, None, "S"), 3, X, pos, call, good).splitlines()) == 3
+    for q1, q2, dp in ((np.nan, 0.1, 8), (0.9, np.nan, 8), (np.nan, np.nan, 0), (np.inf, 0.1, 8), (0.5, np.inf, 8)):
+        q = good.copy(); q[2] = (q1, q2, dp, 0)
+        for showRef in (False, True):
+            with pytest.raises(_lib.CvError, match="record 2: quality"):
+                callVar.format_records(_args(showRef, 30, None, "S"), 3, X, pos, call, q)
+        with pytest.raises((ValueError, OverflowError)):
+            callVar.Output(_args(False, None, None, "S"), io.StringIO(), 3, X, pos, np.tile([0.1, 0.9, 0.0, 0.0], (3, 1)),
+                           np.tile([1.0, 0.0], (3, 1)), np.array([[0, 1, 0, 0]] * 2 + [[0, 1, q1, q2]], np.float32),
+                           np.tile([1.0, 0, 0, 0, 0, 0], (3, 1)))
+    ref_row = call.copy(); ref_row[2, 0] = 0                         # REF without --showRef: no record, no quality
+    q = good.copy(); q[2, 0] = np.nan
+    assert len(callVar.format_records(_args(False, None, None, "S"), 3, X, pos, ref_row, q).splitlines()) == 2
+    with pytest.raises(_lib.CvError, match="record 2: quality"):
+        callVar.format_records(_args(True, None, None, "S"), 3, X, pos, ref_row, q)
+
+
+def test_host_decision_helpers_follow_the_reference_numpy_order():
+    """np.argmax, np.sort()[::-1] and argsort()[::-1] on ties, +-0, denormals, +-Inf and NaN (common.crafted_rows,
+    against the per-row checker common.decide): the helpers Output() uses"""
+    import common
+    from clairvoyante_amd import callVar
+    o = common.crafted_rows()
+    x = common.adversarial_inputs(o.shape[0], seed=13)
+    want_call, want_qual = common.decide_all(o, x)
+    for k, (lo, hi) in enumerate(((6, 10), (4, 6), (10, 16))):
+        assert np.array_equal(np.argmax(o[:, lo:hi], 1), want_call[:, k])
+    assert np.array_equal(callVar._base_order(o[:, 0:4])[:, :2], want_call[:, 3:5])
+    with np.errstate(all="ignore"):
+        p1, p2 = callVar._top2_products(o[:, 6:10], o[:, 4:6], o[:, 10:16])
+        dp = callVar._depth(x)
+    assert common.same_bits(p1, want_qual[:, 0]).all() and common.same_bits(p2, want_qual[:, 1]).all()
+    assert common.same_bits(dp, want_qual[:, 2]).all()
+    assert np.isnan(p1).sum() > 1000 and (want_call[:, 3] != np.argmax(o[:, 0:4], 1)).sum() > 1000

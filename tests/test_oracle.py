@@ -164,3 +164,37 @@ def test_loss_grad_does_not_depend_on_the_thread_count(oracle):
         subprocess.check_call([sys.executable, "-c", code, fn], env=dict(os.environ, OMP_NUM_THREADS=nt))
         outs.append(np.load(fn)); os.remove(fn)
     assert np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32))
+
+
+def test_adversarial_generator_is_seeded_and_holds_every_special_value():
+    a = common.adversarial_inputs(3000, seed=7)
+    b = common.adversarial_inputs(3000, seed=7)
+    assert a.shape == (3000, 33, 4, 4) and a.dtype == np.float32
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    assert not np.array_equal(a.view(np.uint32), common.adversarial_inputs(3000, seed=8).view(np.uint32))
+    bits = a.view(np.uint32).ravel()
+    for u in common.SPECIAL_BITS:                                  # the signalling NaN kept as written
+        assert (bits == u).any(), hex(int(u))
+    for d in common.DENORMALS:
+        assert (bits == np.array(d, np.float32).view(np.uint32)).any(), d
+    assert (bits == 0x80000000).mean() > 0.005                     # -0.0
+    assert (a.reshape(3000, -1) == 0).all(1).mean() > 0.05         # whole candidates zeroed
+    mag = np.abs(a[np.isfinite(a)])
+    assert mag[mag > 0].min() < 1e-30 and mag.max() > 1e30
+    for kind in ("small", "large", "sparse", "denormal"):
+        x, y = common.adversarial_batch(500, kind)
+        assert np.isfinite(x).all() and y.shape == (500, 16)
+        assert np.array_equal(x.view(np.uint32), common.adversarial_batch(500, kind)[0].view(np.uint32))
+
+
+@pytest.mark.parametrize("arch", ["full", "slim"])
+def test_oracle_keeps_candidates_independent_of_non_finite_neighbours(oracle, arch):
+    """a finite candidate gives the same bits whether or not NaN / Inf / sNaN candidates share its batch"""
+    x = common.adversarial_inputs(4000, seed=7)
+    finite = np.isfinite(x).reshape(len(x), -1).all(1)
+    assert 0 < (~finite).sum() < len(x)
+    for kind in ("bench", "init"):
+        P = common.adversarial_params(arch, kind)
+        mixed = oracle.predict(arch, P, x)
+        alone = oracle.predict(arch, P, x[finite])
+        assert np.array_equal(mixed[finite].view(np.uint32), alone.view(np.uint32)), kind
