@@ -324,11 +324,13 @@ extern "C" int cv_forward(cv_model *m, const float *x_dev, int64_t n, float *out
 extern "C" int cv_get_activation(cv_model *m, int layer, float *dst_dev, int64_t n, void *stream)
 {
     if (!m || !dst_dev) { cv_set_error("cv_get_activation: null argument"); return 1; }
-    if ((layer >= 11 && layer <= 13) || (layer >= 21 && layer <= 23)) {   // maps of the last training slice (single-slice steps)
+    if ((layer >= 11 && layer <= 13) || (layer >= 21 && layer <= 23)) {   // maps of the last training pass (single-slice passes)
         const int l = layer % 10 - 1; const bool grad = layer > 20;
         const float *src = grad ? m->last_tr_gpre[l] : m->last_tr_pool[l];
-        if (n <= 0 || n > m->last_tr_n || !src) {
-            cv_set_error("cv_get_activation: layer %d of the last training slice (%lld candidates) is not there", layer, (long long)m->last_tr_n);
+        if (n <= 0 || n > m->last_tr_map_n || !src) {
+            cv_set_error("cv_get_activation: layer %d is not there for n=%lld (the last training pass left maps of %lld "
+                         "candidates%s)", layer, (long long)n, (long long)m->last_tr_map_n,
+                         m->last_tr_map_n && !src ? "; this layer is not materialised on its path" : "");
             return 1;
         }
         CV_HIP(hipSetDevice(m->device));

@@ -142,6 +142,9 @@ struct cv_model {
     const float *last_tr_d4, *last_tr_mask;
     const float *last_tr_pool[3], *last_tr_gpre[3];   // cv_get_activation 11..13 / 21..23: maps of the last training slice (nullptr: not materialised)
     int64_t last_tr_n;
+    // candidates the map pointers above hold: the slice's count after a single-slice pass, 0 after a pass of several slices
+    // (the pointers then address the LAST slice's workspace, which option keep_activations does not extend) or an empty one
+    int64_t last_tr_map_n;
     int last_tr_tile;    // 1: tile-major buffers, 0: natural [n, fc4]
     // option keep_activations + a step of several slices: the two maps of EVERY slice, copied here slice after slice
     // (mask first, dropout output behind it), so that cv_get_activation 6 / 7 covers the whole batch

@@ -613,7 +613,7 @@ static int train_slice_plain(cv_model *m, const float *x, const float *y, int64_
     t_dense_pre<<<nblk(n * a.fc4, 256), 256, 0, st>>>(pool[2], P + o[6], P + o[7], fc4pre, n, s.flat, a.fc4);
     t_fc4_act<<<nblk(n * a.fc4, 256), 256, 0, st>>>(fc4pre, d4, amask, n, a.fc4, backward ? drop4 : 0.0f, seed,
                                                     step, cand0);
-    m->last_tr_d4 = d4; m->last_tr_mask = amask; m->last_tr_n = n; m->last_tr_tile = 0;
+    m->last_tr_d4 = d4; m->last_tr_mask = amask; m->last_tr_n = n; m->last_tr_map_n = n; m->last_tr_tile = 0;
     for (int l = 0; l < 3; l++) { m->last_tr_pool[l] = pool[l]; m->last_tr_gpre[l] = backward ? gpre[l] : nullptr; }
     t_dense_pre<<<nblk(n * a.fc5, 256), 256, 0, st>>>(d4, P + o[8], P + o[9], fc5pre, n, a.fc4, a.fc5);
     t_selu_act<<<nblk(n * a.fc5, 256), 256, 0, st>>>(fc5pre, h5, n * a.fc5);
@@ -807,7 +807,7 @@ static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t
             if (cv_tile_heads_train(m, td4, th5, y, n, backward ? 1 : 0, ghpre, tg5pre, st)) return 1;
         }
     }
-    m->last_tr_d4 = td4; m->last_tr_mask = tmask; m->last_tr_n = n; m->last_tr_tile = 1;
+    m->last_tr_d4 = td4; m->last_tr_mask = tmask; m->last_tr_n = n; m->last_tr_map_n = n; m->last_tr_tile = 1;
     for (int l = 0; l < 3; l++) { m->last_tr_pool[l] = tp[l]; m->last_tr_gpre[l] = nullptr; }
     CV_HIP(hipGetLastError());
     if (!backward) return 0;
@@ -906,6 +906,7 @@ static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t
         const bool have_gpre = (l == 2 && fused3) || nopool_fused;
         // the first layer's unpool rides inside its weight-gradient kernel (its gradient map has no other reader)
         const bool conv1_fused = l == 0 && !have_gpre && a.pool[0] == 5 && s.ntile[0] == 1 && m->dbg[4] != 4;
+        if (conv1_fused) m->last_tr_gpre[0] = nullptr;      // (cv_get_activation 21 reports it missing)
         if (!have_gpre && !conv1_fused && launch_unpool(tgin[l], tp[l], ta[l], tgpre[l], Gn, H, NT, a.pool[l], st, (m->dbg[2] == 1 || m->dbg[2] == 6) ? (1 << 30) : (m->dbg[2] == 2 ? 0 : m->tiny_g), m->dbg[2] == 1 || m->dbg[2] == 4)) return 1;
         f.st_moved();
         // The first layer's weight gradient is the LAST work of the backward pass: nothing of st is left to run beside it.
@@ -1018,7 +1019,7 @@ static int train_workspace(cv_model *m, int64_t n, int64_t *slice_out)
     if (m->t_bytes < need) {
         CV_HIP(hipDeviceSynchronize());
         if (m->t_buf) CV_HIP(hipFree(m->t_buf));
-        m->t_buf = nullptr; m->t_bytes = 0; m->last_tr_n = 0;
+        m->t_buf = nullptr; m->t_bytes = 0; m->last_tr_n = 0; m->last_tr_map_n = 0;
         CV_HIP(hipMalloc(&m->t_buf, need));
         m->t_bytes = need;
     }
@@ -1122,6 +1123,7 @@ static int train_enqueue(cv_model *m, const float *x, const float *y, int64_t n,
         m->tr_keep_floats = 2 * keep_half;
     }
     bool recorded = false;
+    m->last_tr_map_n = 0;                         // (the slice sets it; an empty batch leaves no maps)
     for (int64_t off = 0; off < n; off += slice) {
         int64_t cn = n - off < slice ? n - off : slice;
         const bool last = off + slice >= n;
@@ -1141,6 +1143,9 @@ static int train_enqueue(cv_model *m, const float *x, const float *y, int64_t n,
         }
     }
     if (keep_all && m->last_tr_d4) { m->last_tr_mask = m->tr_keep; m->last_tr_d4 = m->tr_keep + keep_half; m->last_tr_n = n; }
+    // several slices: the maps of 11..13 / 21..23 are the last slice's, in a workspace of slice + 16 candidates -- none
+    // of them is the batch's, so none is exported (option keep_activations keeps the dropout maps of 6 / 7 only)
+    if (n > slice) m->last_tr_map_n = 0;
     if (backward && comm) {
         if (!recorded) CV_HIP(hipEventRecord(m->tr_dense_ready, st));      // empty batch
         CV_HIP(hipStreamWaitEvent(comm, m->tr_dense_ready, 0));

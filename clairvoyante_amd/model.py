@@ -268,7 +268,10 @@ class Clairvoyante(object):
 
     def getActivation(self, layer, n):
         """Intermediate of the last pass in the reference's layout (debug / parity); layers 6 / 7 are the
-        alpha-dropout keep mask (times its factor a) and output of the last train / getLoss slice."""
+        alpha-dropout keep mask (times its factor a) and output of the last train / getLoss slice.  11..13 / 21..23 are
+        the pooled maps and conv1..conv3's pre-activation gradients of the last train / getLoss pass, only when it ran
+        as one slice (<= 65 536 candidates); otherwise, for n beyond that pass, for 21..23 after getLoss, and for 21 on
+        the full topology's default path (not materialised) the call raises (include/clairvoyante_amd.h)."""
         a = self._arch
         hp = [33 - (a.pool[0] - 1)]
         hp.append(hp[0] - (a.pool[1] - 1)); hp.append(hp[1] - (a.pool[2] - 1))

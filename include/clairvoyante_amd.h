@@ -115,8 +115,11 @@ int cv_format_vcf(const int32_t *call, const float *qual, int64_t n, const float
  * dropped, a where kept, 1 everywhere at rate 0), 7 = dropout4, the layer's output
  * [n, fc4] -- what the parity tests feed to / compare with the oracle.
  * layers 11..13 / 21..23: the pooled maps (slim: conv outputs) and the pre-activation gradients of conv1..conv3 of the
- * last single-slice training step, natural layout (21 of the full topology is not materialised: the first layer's
- * unpool rides in its weight-gradient kernel) -- what tools/gpu_train_map_diff.py lays beside the plain kernels'.
+ * last cv_grad / cv_loss pass, natural layout, for its first n candidates -- only when that pass ran as ONE slice
+ * (at most 65 536 candidates).  Every other request is an error, never other values: after a pass of several slices
+ * (with or without "keep_activations", which extends 6 / 7 only), for n above the pass's candidates, 21..23 after
+ * cv_loss, and 21 of the full topology on the default path (the first layer's unpool rides in its weight-gradient
+ * kernel; option dbg4 = 4 materialises it).  tests/test_gpu_train_maps.py holds them to the oracle.
  * Layers 4 / 5 of a pass that ran fc5 and the heads on the tail of the fc4 kernel exist only with option
  * "keep_activations" set before the pass (error otherwise).                        */
 int cv_get_activation(cv_model *m, int layer, float *dst_dev, int64_t n, void *stream);

@@ -463,6 +463,125 @@ void cvo_forward_all(const cvo_arch *a, const float *const *P, const float *x, i
 
 /* ---- public: loss + gradients (training oracle) -------------------------- */
 
+/* Backward pass of ONE candidate whose forward record `rec` forward_one wrote: fills the gradient record g (same
+ * layout as the record: g + L->pre[l] = d loss / d pre-activation of conv layer l + 1, g + L->pooled[l] = d loss / d
+ * its pooled map, and so on) and, when gacc is not NULL, ADDS the candidate's terms to the 18 double accumulators.
+ * mi: the candidate's fc4 keep mask (NULL = phase False); aa: alpha-dropout's factor a (1 without a mask).        */
+static void backward_one(const cvo_arch *a, const cvo_layout *L, const cvo_shape *s, const float *const *P,
+                         const float *xi, const float *yi, const float *mi, float aa, const float *rec, float *g,
+                         double *const *gacc)
+{
+    static const int hn[4] = {4, 2, 4, 6};
+    static const int ho[4] = {0, 4, 6, 10};
+    const float *o = rec + L->out;
+    memset(g, 0, sizeof(float) * L->total);
+    /* head pre-activation grads */
+    for (int k = 0; k < 4; k++) {
+        float sg = o[k];
+        g[L->hpre[0] + k] = 2.0f * (sg - yi[k]) * sg * (1.0f - sg);
+    }
+    for (int hd = 1; hd < 4; hd++) {
+        float ysum = 0; for (int k = 0; k < hn[hd]; k++) ysum += yi[ho[hd] + k];
+        for (int k = 0; k < hn[hd]; k++) {
+            float dl = o[ho[hd] + k] * ysum - yi[ho[hd] + k];
+            g[L->hpre[hd] + k] = dl * cvo_selu_grad_from_pre(rec[L->hpre[hd] + k]);
+        }
+    }
+    /* heads -> d(d4) and d(fc5) */
+    for (int k = 0; k < a->fc4; k++) {
+        float acc = 0;
+        for (int j = 0; j < 4; j++) {
+            acc += g[L->hpre[0] + j] * P[10][(size_t)k * 4 + j];
+            if (gacc) gacc[10][(size_t)k * 4 + j] += (double)rec[L->d4 + k] * g[L->hpre[0] + j];
+        }
+        g[L->d4 + k] = acc;
+    }
+    if (gacc) for (int j = 0; j < 4; j++) gacc[11][j] += g[L->hpre[0] + j];
+    for (int hd = 1; hd < 4; hd++) {
+        int N = hn[hd];
+        for (int k = 0; k < a->fc5; k++) {
+            float acc = 0;
+            for (int j = 0; j < N; j++) {
+                acc += g[L->hpre[hd] + j] * P[10 + 2 * hd][(size_t)k * N + j];
+                if (gacc) gacc[10 + 2 * hd][(size_t)k * N + j] += (double)rec[L->fc5 + k] * g[L->hpre[hd] + j];
+            }
+            g[L->fc5 + k] += acc;
+        }
+        if (gacc) for (int j = 0; j < N; j++) gacc[11 + 2 * hd][j] += g[L->hpre[hd] + j];
+    }
+    /* fc5 */
+    for (int j = 0; j < a->fc5; j++) g[L->fc5pre + j] = g[L->fc5 + j] * cvo_selu_grad_from_pre(rec[L->fc5pre + j]);
+    for (int k = 0; k < a->fc4; k++) {
+        float acc = 0;
+        const float *wr = P[8] + (size_t)k * a->fc5;
+        double *gr = gacc ? gacc[8] + (size_t)k * a->fc5 : NULL;
+        float dk = rec[L->d4 + k];
+        for (int j = 0; j < a->fc5; j++) { acc += g[L->fc5pre + j] * wr[j]; if (gr) gr[j] += (double)dk * g[L->fc5pre + j]; }
+        g[L->d4 + k] += acc;
+    }
+    if (gacc) for (int j = 0; j < a->fc5; j++) gacc[9][j] += g[L->fc5pre + j];
+    /* dropout4 backward: d(fc4) = a * m * d(d4) */
+    for (int k = 0; k < a->fc4; k++) {
+        float dd = g[L->d4 + k];
+        if (mi) dd = aa * mi[k] * dd;
+        g[L->fc4pre + k] = dd * cvo_selu_grad_from_pre(rec[L->fc4pre + k]);
+    }
+    /* fc4 */
+    {
+        const float *fin = rec + L->pooled[2];
+        float *gin = g + L->pooled[2];
+        for (int k = 0; k < s->flat; k++) {
+            float acc = 0;
+            const float *wr = P[6] + (size_t)k * a->fc4;
+            double *gr = gacc ? gacc[6] + (size_t)k * a->fc4 : NULL;
+            float fk = fin[k];
+            for (int j = 0; j < a->fc4; j++) { acc += g[L->fc4pre + j] * wr[j]; if (gr) gr[j] += (double)fk * g[L->fc4pre + j]; }
+            gin[k] = acc;
+        }
+        if (gacc) for (int j = 0; j < a->fc4; j++) gacc[7][j] += g[L->fc4pre + j];
+    }
+    /* conv stack backward */
+    for (int l = 2; l >= 0; l--) {
+        int H = s->hc[l], C = a->cout[l], cin = s->cin[l], kh = a->kh[l], p = a->pool[l];
+        int row = CVO_W * C, Ho = s->hp[l];
+        /* pool backward: route to the first maximum in the window, -0 below +0 as in cvo_pool_max */
+        for (int h = 0; h < Ho; h++)
+            for (int e = 0; e < row; e++) {
+                int best = 0; float m = rec[L->act[l] + (size_t)h * row + e];
+                for (int d = 1; d < p; d++) {
+                    float v = rec[L->act[l] + (size_t)(h + d) * row + e];
+                    if (v > m || (v == 0.0f && m == 0.0f && !signbit(v) && signbit(m))) { m = v; best = d; }
+                }
+                g[L->act[l] + (size_t)(h + best) * row + e] += g[L->pooled[l] + (size_t)h * row + e];
+            }
+        for (int e = 0; e < H * row; e++)
+            g[L->pre[l] + e] = g[L->act[l] + e] * cvo_selu_grad_from_pre(rec[L->pre[l] + e]);
+        const float *in = (l == 0) ? xi : rec + L->pooled[l - 1];
+        float *gin = (l == 0) ? NULL : g + L->pooled[l - 1];
+        int padt = (kh - 1) / 2;
+        for (int h = 0; h < H; h++)
+            for (int w = 0; w < CVO_W; w++) {
+                const float *go = g + L->pre[l] + ((size_t)h * CVO_W + w) * C;
+                if (gacc) for (int co = 0; co < C; co++) gacc[2 * l + 1][co] += go[co];
+                for (int ka = 0; ka < kh; ka++) {
+                    int hi = h + ka - padt; if (hi < 0 || hi >= H) continue;
+                    for (int kb = 0; kb < CVO_KW; kb++) {
+                        int wi = w + kb - 1; if (wi < 0 || wi >= CVO_W) continue;
+                        const float *xr = in + ((size_t)hi * CVO_W + wi) * cin;
+                        for (int ci = 0; ci < cin; ci++) {
+                            size_t wo = ((size_t)(ka * CVO_KW + kb) * cin + ci) * C;
+                            const float *wc = P[2 * l] + wo;
+                            double *gw = gacc ? gacc[2 * l] + wo : NULL;
+                            float acc = 0, xv = xr[ci];
+                            for (int co = 0; co < C; co++) { acc += go[co] * wc[co]; if (gw) gw[co] += (double)xv * go[co]; }
+                            if (gin) gin[((size_t)hi * CVO_W + wi) * cin + ci] += acc;
+                        }
+                    }
+                }
+            }
+    }
+}
+
 /* loss (v3.py:140-151), SUMS over the batch:
  *   sum (sigmoid - y[0:4])^2  +  sum -y*log_softmax(logits) for the 3 heads
  *   + lambda * sum_{non-bias kernels} sum(w^2)/2
@@ -520,112 +639,7 @@ double cvo_loss_grad(const cvo_arch *a, const float *const *P, const float *x, c
             for (int k = 0; k < hn[hd]; k++) lsum[hd] += -(double)yi[ho[hd] + k] * ((double)lg[k] - lse);
         }
         if (!grads) continue;
-        memset(g, 0, sizeof(float) * L.total);
-        /* head pre-activation grads */
-        for (int k = 0; k < 4; k++) {
-            float sg = o[k];
-            g[L.hpre[0] + k] = 2.0f * (sg - yi[k]) * sg * (1.0f - sg);
-        }
-        for (int hd = 1; hd < 4; hd++) {
-            float ysum = 0; for (int k = 0; k < hn[hd]; k++) ysum += yi[ho[hd] + k];
-            for (int k = 0; k < hn[hd]; k++) {
-                float dl = o[ho[hd] + k] * ysum - yi[ho[hd] + k];
-                g[L.hpre[hd] + k] = dl * cvo_selu_grad_from_pre(rec[L.hpre[hd] + k]);
-            }
-        }
-        /* heads -> d(d4) and d(fc5) */
-        for (int k = 0; k < a->fc4; k++) {
-            float acc = 0;
-            for (int j = 0; j < 4; j++) {
-                acc += g[L.hpre[0] + j] * P[10][(size_t)k * 4 + j];
-                gacc[10][(size_t)k * 4 + j] += (double)rec[L.d4 + k] * g[L.hpre[0] + j];
-            }
-            g[L.d4 + k] = acc;
-        }
-        for (int j = 0; j < 4; j++) gacc[11][j] += g[L.hpre[0] + j];
-        for (int hd = 1; hd < 4; hd++) {
-            int N = hn[hd];
-            for (int k = 0; k < a->fc5; k++) {
-                float acc = 0;
-                for (int j = 0; j < N; j++) {
-                    acc += g[L.hpre[hd] + j] * P[10 + 2 * hd][(size_t)k * N + j];
-                    gacc[10 + 2 * hd][(size_t)k * N + j] += (double)rec[L.fc5 + k] * g[L.hpre[hd] + j];
-                }
-                g[L.fc5 + k] += acc;
-            }
-            for (int j = 0; j < N; j++) gacc[11 + 2 * hd][j] += g[L.hpre[hd] + j];
-        }
-        /* fc5 */
-        for (int j = 0; j < a->fc5; j++) g[L.fc5pre + j] = g[L.fc5 + j] * cvo_selu_grad_from_pre(rec[L.fc5pre + j]);
-        for (int k = 0; k < a->fc4; k++) {
-            float acc = 0;
-            const float *wr = P[8] + (size_t)k * a->fc5;
-            double *gr = gacc[8] + (size_t)k * a->fc5;
-            float dk = rec[L.d4 + k];
-            for (int j = 0; j < a->fc5; j++) { acc += g[L.fc5pre + j] * wr[j]; gr[j] += (double)dk * g[L.fc5pre + j]; }
-            g[L.d4 + k] += acc;
-        }
-        for (int j = 0; j < a->fc5; j++) gacc[9][j] += g[L.fc5pre + j];
-        /* dropout4 backward: d(fc4) = a * m * d(d4) */
-        for (int k = 0; k < a->fc4; k++) {
-            float dd = g[L.d4 + k];
-            if (mi) dd = aa * mi[k] * dd;
-            g[L.fc4pre + k] = dd * cvo_selu_grad_from_pre(rec[L.fc4pre + k]);
-        }
-        /* fc4 */
-        {
-            const float *fin = rec + L.pooled[2];
-            float *gin = g + L.pooled[2];
-            for (int k = 0; k < s.flat; k++) {
-                float acc = 0;
-                const float *wr = P[6] + (size_t)k * a->fc4;
-                double *gr = gacc[6] + (size_t)k * a->fc4;
-                float fk = fin[k];
-                for (int j = 0; j < a->fc4; j++) { acc += g[L.fc4pre + j] * wr[j]; gr[j] += (double)fk * g[L.fc4pre + j]; }
-                gin[k] = acc;
-            }
-            for (int j = 0; j < a->fc4; j++) gacc[7][j] += g[L.fc4pre + j];
-        }
-        /* conv stack backward */
-        for (int l = 2; l >= 0; l--) {
-            int H = s.hc[l], C = a->cout[l], cin = s.cin[l], kh = a->kh[l], p = a->pool[l];
-            int row = CVO_W * C, Ho = s.hp[l];
-            /* pool backward: route to the first maximum in the window, -0 below +0 as in cvo_pool_max */
-            for (int h = 0; h < Ho; h++)
-                for (int e = 0; e < row; e++) {
-                    int best = 0; float m = rec[L.act[l] + (size_t)h * row + e];
-                    for (int d = 1; d < p; d++) {
-                        float v = rec[L.act[l] + (size_t)(h + d) * row + e];
-                        if (v > m || (v == 0.0f && m == 0.0f && !signbit(v) && signbit(m))) { m = v; best = d; }
-                    }
-                    g[L.act[l] + (size_t)(h + best) * row + e] += g[L.pooled[l] + (size_t)h * row + e];
-                }
-            for (int e = 0; e < H * row; e++)
-                g[L.pre[l] + e] = g[L.act[l] + e] * cvo_selu_grad_from_pre(rec[L.pre[l] + e]);
-            const float *in = (l == 0) ? xi : rec + L.pooled[l - 1];
-            float *gin = (l == 0) ? NULL : g + L.pooled[l - 1];
-            int padt = (kh - 1) / 2;
-            for (int h = 0; h < H; h++)
-                for (int w = 0; w < CVO_W; w++) {
-                    const float *go = g + L.pre[l] + ((size_t)h * CVO_W + w) * C;
-                    for (int co = 0; co < C; co++) gacc[2 * l + 1][co] += go[co];
-                    for (int ka = 0; ka < kh; ka++) {
-                        int hi = h + ka - padt; if (hi < 0 || hi >= H) continue;
-                        for (int kb = 0; kb < CVO_KW; kb++) {
-                            int wi = w + kb - 1; if (wi < 0 || wi >= CVO_W) continue;
-                            const float *xr = in + ((size_t)hi * CVO_W + wi) * cin;
-                            for (int ci = 0; ci < cin; ci++) {
-                                size_t wo = ((size_t)(ka * CVO_KW + kb) * cin + ci) * C;
-                                const float *wc = P[2 * l] + wo;
-                                double *gw = gacc[2 * l] + wo;
-                                float acc = 0, xv = xr[ci];
-                                for (int co = 0; co < C; co++) { acc += go[co] * wc[co]; gw[co] += (double)xv * go[co]; }
-                                if (gin) gin[((size_t)hi * CVO_W + wi) * cin + ci] += acc;
-                            }
-                        }
-                    }
-                }
-        }
+        backward_one(a, &L, &s, P, xi, yi, mi, aa, rec, g, gacc);
     }
     free(rec); free(g);
     }   /* omp parallel */
@@ -666,6 +680,29 @@ double cvo_loss_grad(const cvo_arch *a, const float *const *P, const float *x, c
     double total = lsum[0] + lsum[1] + lsum[2] + lsum[3] + l2;
     free(lsum_t); free(gacc_t);
     return total;
+}
+
+
+/* Every candidate's forward record (recs[n][record_size], as cvo_forward_all) and gradient record (grecs, same layout:
+ * grecs + pre[l] holds d loss / d conv pre-activation l + 1) of the training loss under mask4 / rate4 -- the per-candidate
+ * backward of cvo_loss_grad, whose sums over the batch are its weight and bias gradients.  (lambda adds to the weights'
+ * gradients only, never to a record.)  Candidates are independent: OpenMP over them, the same bits at any thread count. */
+void cvo_backward_all(const cvo_arch *a, const float *const *P, const float *x, const float *y, int64_t n,
+                      const float *mask4, float rate4, float *recs, float *grecs)
+{
+    cvo_layout L; cvo_make_layout(a, &L);
+    cvo_shape s; cvo_shapes(a, &s);
+    const float ap = -1.7580993408473766f;
+    float q = 1.0f - rate4;
+    float aa = mask4 ? sqrtf(1.0f / (q * ((1.0f - q) * (ap * ap) + 1.0f))) : 1.0f;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) {
+        const float *xi = x + (size_t)i * CVO_H * CVO_W * CVO_CIN;
+        const float *mi = mask4 ? mask4 + (size_t)i * a->fc4 : NULL;
+        float *rec = recs + (size_t)i * L.total;
+        forward_one(a, &L, P, xi, rec, mi, rate4);
+        backward_one(a, &L, &s, P, xi, y + (size_t)i * CVO_NOUT, mi, aa, rec, grecs + (size_t)i * L.total, NULL);
+    }
 }
 
 /* TF1 AdamOptimizer step (beta1 .9, beta2 .999, eps 1e-8, "epsilon hat" form):

@@ -159,6 +159,12 @@ def forward_all(arch_name, params, x, mask4=None, rate4=0.0):
         mptr = ctypes.c_void_p(mask4.ctypes.data)
     lib().cvo_forward_all(ctypes.byref(a), ptrs, ctypes.c_void_p(x.ctypes.data), ctypes.c_int64(n),
                           ctypes.c_void_p(recs.ctypes.data), mptr, ctypes.c_float(rate4))
+    return _split_records(a, recs, off)
+
+
+def _split_records(a, recs, off):
+    """records [n, record_size] -> dict of views by _REC_FIELDS (conv maps reshaped to [n,h,4,c])"""
+    n = recs.shape[0]
     res = {}
     for i, f in enumerate(_REC_FIELDS):
         res[f] = recs[:, off[i]:off[i + 1]]
@@ -168,6 +174,35 @@ def forward_all(arch_name, params, x, mask4=None, rate4=0.0):
         for f in ("pre", "act"):
             res["%s%d" % (f, l + 1)] = res["%s%d" % (f, l + 1)].reshape(n, hc[l], W, c)
         res["pool%d" % (l + 1)] = res["pool%d" % (l + 1)].reshape(n, hc[l] - (a.pool[l] - 1), W, c)
+    return res
+
+
+def backward_maps(arch_name, params, x, y, mask4=None, rate4=0.0):
+    """Per candidate, the training loss's gradient with respect to each conv layer's pre-activation (cvo_backward_all:
+    the backward pass of loss_grad before it sums over the batch).  Returns forward_all's dict plus gpre1..gpre3, each
+    shaped like pre1..pre3 ([n, h, 4, c]).  lambda does not enter these maps."""
+    a = ARCH[arch_name]
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, H, W, CIN)
+    y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1, NOUT)
+    n = x.shape[0]
+    assert y.shape[0] == n
+    off = (ctypes.c_int64 * 20)()
+    lib().cvo_record_offsets(ctypes.byref(a), off)
+    off = list(off)
+    recs = np.empty((n, off[19]), dtype=np.float32)
+    grecs = np.empty((n, off[19]), dtype=np.float32)
+    arrs, ptrs = _parr(params)
+    mptr = None
+    if mask4 is not None:
+        mask4 = np.ascontiguousarray(mask4, dtype=np.float32).reshape(n, a.fc4)
+        mptr = ctypes.c_void_p(mask4.ctypes.data)
+    lib().cvo_backward_all(ctypes.byref(a), ptrs, ctypes.c_void_p(x.ctypes.data), ctypes.c_void_p(y.ctypes.data),
+                           ctypes.c_int64(n), mptr, ctypes.c_float(rate4), ctypes.c_void_p(recs.ctypes.data),
+                           ctypes.c_void_p(grecs.ctypes.data))
+    res = _split_records(a, recs, off)
+    hc = [H, H - (a.pool[0] - 1), H - (a.pool[0] - 1) - (a.pool[1] - 1)]
+    for l in range(3):
+        res["gpre%d" % (l + 1)] = grecs[:, off[3 * l]:off[3 * l + 1]].reshape(n, hc[l], W, a.cout[l])
     return res
 
 

@@ -128,7 +128,8 @@ def compare_step(oracle, arch, n, rate, lam, lr=1e-3, seed=9, options=None, kspl
 def test_training_step_matches_oracle_at_training_sizes(oracle, arch, n):
     """320 / 480 = 20 / 30 groups: the two smallest workgroup shapes of fc4's data gradient (4 waves, 4 / 2 row parts;
     640 with this seed is a case of the k-split note in compare_step: one selu' flip, conv1/kernel off by 3e-4 of its
-    largest entry in the eight-range order, 2.4e-7 as a single chain -- it runs in the single-chain test below);
+    largest entry in the eight-range order, 2.4e-7 as a single chain -- it runs in the single-chain test below; the flip
+    is fc5 unit 121 of candidate 413, tests/test_gpu_train_maps.py);
     1 250 = a rank's share of train.py's batch on 8 GPUs (BASELINE config 4 as it runs: 79 groups, the tiny-batch
     kernel set); 2 561 = the first size past the position parts of the convolutions (161 groups, ragged last group: the
     rest of the small-batch kernel set on flat convolution ranges); 5 000 = a rank's share on 2 GPUs; 6 401 = the first size

@@ -198,3 +198,67 @@ def test_oracle_keeps_candidates_independent_of_non_finite_neighbours(oracle, ar
         mixed = oracle.predict(arch, P, x)
         alone = oracle.predict(arch, P, x[finite])
         assert np.array_equal(mixed[finite].view(np.uint32), alone.view(np.uint32)), kind
+
+
+def _training_batch(oracle, arch, n, seed):
+    from clairvoyante_amd import synth
+    xt, cls, rf, alt, il = synth.make_candidates(n, seed=seed, return_class=True)
+    mask = (np.random.RandomState(seed).uniform(size=(n, oracle.ARCH[arch].fc4)) < 0.5).astype(np.float32)
+    return xt.numpy(), synth.make_labels(cls, rf, alt, il).numpy(), mask
+
+
+@pytest.mark.parametrize("arch", ["full", "slim"])
+def test_backward_maps_match_torch_autograd(oracle, arch):
+    """Each candidate's gradient with respect to the conv pre-activations (oracle.backward_maps, the per-candidate
+    backward of loss_grad) against float64 autograd through tests/torch_ref.py under the same dropout mask.  bench_params
+    (nonzero biases): no pre-activation sits at exactly 0, where selu' takes a side.  Measured: 5.1e-6 of the
+    candidate's largest entry in that layer."""
+    n = 16
+    x, y, mask = _training_batch(oracle, arch, n, seed=12)
+    P = common.bench_params(oracle, arch)
+    got = oracle.backward_maps(arch, P, x, y, mask4=mask, rate4=0.5)
+    ref = torch_ref.pre_grads(arch, P, x, y, mask4=mask, rate4=0.5)
+    fa = oracle.forward_all(arch, P, x, mask4=mask, rate4=0.5)
+    for l in range(3):
+        g, r = got["gpre%d" % (l + 1)], ref[l]
+        assert g.shape == r.shape == fa["pre%d" % (l + 1)].shape, (l, g.shape, r.shape)
+        assert np.array_equal(got["pre%d" % (l + 1)], fa["pre%d" % (l + 1)])
+        err = np.abs(g - r).reshape(n, -1).max(1)
+        scale = np.abs(r).reshape(n, -1).max(1)
+        assert (scale > 0).all() and (err <= 2e-5 * scale).all(), (l + 1, float((err / scale).max()))
+
+
+@pytest.mark.parametrize("arch", ["full", "slim"])
+def test_backward_maps_sum_to_the_bias_gradients(oracle, arch):
+    """A conv layer's bias gradient is the sum over candidates and positions of its pre-activation gradient map: the
+    maps are the terms loss_grad adds up (in doubles), so the two agree to the rounding of the float result"""
+    n = 40
+    x, y, mask = _training_batch(oracle, arch, n, seed=13)
+    P = common.bench_params(oracle, arch)
+    maps = oracle.backward_maps(arch, P, x, y, mask4=mask, rate4=0.5)
+    _, _, grads = oracle.loss_grad(arch, P, x, y, lam=0.01, mask4=mask, rate4=0.5)
+    for l in range(3):
+        g = maps["gpre%d" % (l + 1)].astype(np.float64)
+        s, mag = g.sum((0, 1, 2)), np.abs(g).sum((0, 1, 2))
+        b = grads["conv%d/bias" % (l + 1)].astype(np.float64)
+        assert (np.abs(s - b) <= 1e-6 * np.abs(b) + 1e-12 * mag).all(), (l + 1, np.abs(s - b).max())
+
+
+def test_backward_maps_do_not_depend_on_the_thread_count(oracle):
+    """cvo_backward_all: one OpenMP iteration per candidate and nothing shared -- the same bits at 1 and 7 threads"""
+    import subprocess
+    import sys
+    code = ("import sys, numpy as np; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import common\nfrom oracle import cv_oracle as O\nfrom test_oracle import _training_batch\n"
+            "out = []\n"
+            "for arch in ('full', 'slim'):\n"
+            "    x, y, mask = _training_batch(O, arch, 61, seed=14)\n"
+            "    r = O.backward_maps(arch, common.bench_params(O, arch), x, y, mask4=mask, rate4=0.5)\n"
+            "    out += [r[k].ravel() for k in ('gpre1', 'gpre2', 'gpre3', 'pool3', 'out')]\n"
+            "np.save(sys.argv[1], np.concatenate(out))\n") % (ROOT, os.path.join(ROOT, "tests"))
+    outs = []
+    for nt in ("1", "7"):
+        fn = os.path.join(os.environ.get("TMPDIR", "/tmp"), "cvo_bm_%s_%d.npy" % (nt, os.getpid()))
+        subprocess.check_call([sys.executable, "-c", code, fn], env=dict(os.environ, OMP_NUM_THREADS=nt))
+        outs.append(np.load(fn)); os.remove(fn)
+    assert np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32))

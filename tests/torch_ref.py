@@ -27,9 +27,11 @@ def same_pad(k):
     return before, total - before
 
 
-def forward(arch, params, x, dtype=torch.float64, mask4=None, rate4=0.0, want_logits=False, device=None):
+def forward(arch, params, x, dtype=torch.float64, mask4=None, rate4=0.0, want_logits=False, device=None,
+            retain_pre=False):
     """x [n,33,4,4] (NHWC) -> dict with out16 and intermediates (NHWC).  device: where the torch ops run (default: CPU;
-    bench.py runs the float64 formulation over all timed candidates with stock torch ops on the GPU)."""
+    bench.py runs the float64 formulation over all timed candidates with stock torch ops on the GPU).  retain_pre: the
+    conv pre-activations, as the NCHW tensors of the graph ("pre1_t".."pre3_t"), keep their gradient (pre_grads)."""
     cfg = CFG[arch]
     p = {k: torch.as_tensor(v).to(device=device, dtype=dtype) for k, v in params.items()}
     t = torch.as_tensor(x).to(device=device, dtype=dtype).permute(0, 3, 1, 2)  # NCHW: C=matrix, H=position, W=base
@@ -39,6 +41,12 @@ def forward(arch, params, x, dtype=torch.float64, mask4=None, rate4=0.0, want_lo
         pt, pb = same_pad(cfg["kh"][l])
         pl, pr = same_pad(4)
         t = F.conv2d(F.pad(t, (pl, pr, pt, pb)), w, p["conv%d/bias" % (l + 1)])
+        if retain_pre:
+            if t.requires_grad:
+                t.retain_grad()
+            else:
+                t.requires_grad_()
+            inter["pre%d_t" % (l + 1)] = t
         inter["pre%d" % (l + 1)] = t.permute(0, 2, 3, 1)
         t = selu(t)
         inter["act%d" % (l + 1)] = t.permute(0, 2, 3, 1)
@@ -71,14 +79,27 @@ def forward(arch, params, x, dtype=torch.float64, mask4=None, rate4=0.0, want_lo
     return inter
 
 
-def loss(arch, params, x, y, lam, dtype=torch.float64, mask4=None, rate4=0.0):
-    """Scalar loss of clairvoyante_v3.py:140-151 (sums over the batch)."""
-    r = forward(arch, params, x, dtype, mask4, rate4, want_logits=True)
+def _data_losses(r, y, dtype):
     y = torch.as_tensor(y).to(dtype)
     lz, lt, ll = r["logits"]
     l1 = ((r["base"] - y[:, 0:4]) ** 2).sum()
     l2 = (-y[:, 4:6] * torch.log_softmax(lz, 1)).sum()
     l3 = (-y[:, 6:10] * torch.log_softmax(lt, 1)).sum()
     l4 = (-y[:, 10:16] * torch.log_softmax(ll, 1)).sum()
+    return l1, l2, l3, l4
+
+
+def loss(arch, params, x, y, lam, dtype=torch.float64, mask4=None, rate4=0.0):
+    """Scalar loss of clairvoyante_v3.py:140-151 (sums over the batch)."""
+    r = forward(arch, params, x, dtype, mask4, rate4, want_logits=True)
+    l1, l2, l3, l4 = _data_losses(r, y, dtype)
     reg = sum((torch.as_tensor(v).to(dtype) ** 2).sum() / 2 for k, v in params.items() if "bias" not in k)
     return l1 + l2 + l3 + l4 + lam * reg, (l1, l2, l3, l4, lam * reg)
+
+
+def pre_grads(arch, params, x, y, mask4=None, rate4=0.0):
+    """Per candidate, d loss / d pre-activation of conv1..conv3 by float64 autograd: three [n,h,4,c] (NHWC) arrays.
+    The L2 term does not depend on the pre-activations, so lambda does not enter."""
+    r = forward(arch, params, x, torch.float64, mask4, rate4, want_logits=True, retain_pre=True)
+    sum(_data_losses(r, y, torch.float64)).backward()
+    return [r["pre%d_t" % (l + 1)].grad.permute(0, 2, 3, 1).numpy() for l in range(3)]

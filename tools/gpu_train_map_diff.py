@@ -50,7 +50,8 @@ if len(bad):
     for ix in bad[:4]:
         ix = tuple(ix)
         print(ix, "pre", float(fa["pre2"][ix]).hex(), "act", float(fa["act2"][ix]).hex())
-    # the oracle's own pre-activation gradient is not exported: compare weight gradients instead
+    # weight gradients of both paths against the oracle (each candidate's maps against oracle.backward_maps:
+    # tests/test_gpu_train_maps.py)
     l_or, parts, g_or = O.loss_grad(arch, P, x1.cpu().numpy(), y1.cpu().numpy(), lam=0.0)
     def flat(m, which):
         t = torch.empty(m.numParameters, device="cuda")
