@@ -124,7 +124,6 @@ extern "C" int cv_create(const cv_arch *arch, int device, cv_model **out)
     // (rounds 1-4: 160 / 256 / 2 048, set where each kernel was first tuned; a ladder of batch sizes showed steps of 75 us,
     // 105 us and 840 us in the time of a call one group past each line: profiles/r05/infer_size_sweep.txt)
     m->inf_small_g = 256; m->inf_fc4_small_g = 288; m->inf_slab_g = -1; m->inf_flat = 1; m->inf_slim_small_g = -1; m->inf_fc4_one_g = 80;      // (-1: fc4's kernel form by estimate, cv_mfma_forward)
-    m->sched = 3839;
     alloc(&m->wp_conv1, 4 * 64);
     for (int l = 1; l < 3; l++) alloc(&m->wp_conv[l], (size_t)s.ntile[l] * arch->kh[l] * 4 * s.cinb[l] * 256);
     alloc(&m->wp_fc4, (size_t)s.kb4 * ((s.nb4 + 3) / 4 * 4) * 256);   // fragments padded to the wave count
@@ -175,7 +174,7 @@ extern "C" int cv_destroy(cv_model *m)
         for (int i = 0; i < CV_TR_EVENTS; i++) (void)hipEventDestroy(m->tr_ev[i]);
         (void)hipEventDestroy(m->tr_dense_ready);
         (void)hipEventDestroy(m->tr_l2_done);
-        (void)hipEventDestroy(m->tr_pack_fork); (void)hipEventDestroy(m->tr_pack_done);
+        (void)hipEventDestroy(m->tr_pack_done);
     }
     cv_prof_free(m);
     delete m;
@@ -265,7 +264,6 @@ extern "C" int cv_set_option(cv_model *m, const char *key, int64_t value)
     if (!strcmp(key, "dense_rag")) { m->inf_rag_s = value < 0 ? -1 : (value > 14 ? 14 : (int)value); return 0; }
     if (!strcmp(key, "train_tiny_groups")) { m->tiny_g = value < 0 ? 0 : (value > 4096 ? 4096 : (int)value); return 0; }
     if (!strcmp(key, "variant")) { m->variant = (int)value; return 0; }
-    if (!strcmp(key, "train_sched")) { m->sched = (int)value & 8191; return 0; }
     if (!strncmp(key, "dbg", 3) && key[3] >= '0' && key[3] <= '7' && !key[4]) { m->dbg[key[3] - '0'] = (int)value; cv_layouts_stale(m, CVL_BACKWARD); return 0; }
     if (!strcmp(key, "chunk")) {
         if (value < 16 || value > (1 << 22)) { cv_set_error("chunk must be in [16, 4194304]"); return 1; }
@@ -295,7 +293,6 @@ extern "C" int cv_get_option(const cv_model *m, const char *key, int64_t *value)
     if (!strcmp(key, "slim_small_groups")) { *value = m->inf_slim_small_g; return 0; }
     if (!strcmp(key, "dense_rag")) { *value = m->inf_rag_s; return 0; }
     if (!strcmp(key, "train_tiny_groups")) { *value = m->tiny_g; return 0; }
-    if (!strcmp(key, "train_sched")) { *value = m->sched; return 0; }
     if (!strcmp(key, "variant")) { *value = m->variant; return 0; }
     if (!strncmp(key, "dbg", 3) && key[3] >= '0' && key[3] <= '7' && !key[4]) { *value = m->dbg[key[3] - '0']; return 0; }
     cv_set_error("unknown option '%s'", key);

@@ -119,7 +119,7 @@ struct cv_model {
     hipEvent_t tr_ev[16];
     hipEvent_t tr_dense_ready;
     hipEvent_t tr_l2_done;         // recorded on the side stream behind the L2 kernel of a step
-    hipEvent_t tr_pack_fork, tr_pack_done;   // weight packing on the side stream (cv_pack_for_training)
+    hipEvent_t tr_pack_done;       // weight packing on the side stream (cv_pack_for_training)
     int train_overlap;   // option: weight gradients on the side stream (default 1)
     int train_ksplit;    // option: k-split fc4 forward at tiny batches (default 1)
     // cv_forward picks kernels by the number of groups (options "infer_small_groups", "infer_fc4_small_groups",
@@ -161,25 +161,6 @@ struct cv_model {
     //   dbg5 = 1: all weight packing in one launch in stream order (>= 16: dbg5 >> 4 candidate ranges of fc4's weight gradient, bit 3 / bit 2: one / two input fragments per wave there)      dbg6 = n: row parts of dense_dgrad_unpool (few groups; + 100: 4-wave workgroups; 0 = chosen by the number of groups)
     //   dbg7 = 1: training-forward conv3 on conv_tm instead of conv3_rot
     int dbg[8];
-    // option "train_sched": the round-5 re-cut of the step's schedule, one bit per change (default 3839 = all but bit 8; A/B runs and
-    // the variant tests switch them off one by one -- same arithmetic either way):
-    //   1  loss header behind the heads kernel on a side stream (tiny batches: the first, larger ones: the second, idle one)
-    //      instead of at the tail of the step
-    //   2  conv1's weight gradient on the main stream at tiny batches instead of a side stream
-    //   4  ONE marker on the main stream for the L2 term and the weight packing instead of one each
-    //   8  launch sites at the same point of the main stream share a marker (not for the full topology above 512 groups:
-    //      at train.py's 625 the step is 39 us SLOWER with it, at 313 groups 50 us faster -- profiles/r05/step_ab_session4_sched_bits.txt)
-    //   16 a pass packs only the weight layouts its kernels read instead of every forward layout
-    //   32 the base head's data gradient, the dropout factor and selu'(fc4) on the store of fc5's data-gradient kernel
-    //      instead of a pass of their own
-    //   64 no memset of the gradient at the head of a step: the second passes of the first slice store instead of adding
-    //   128 tiny batches: the side streams chained before the ONE wait of the main stream at the end of the step
-    //   512 conv1's weight gradient on the main stream at EVERY batch size (the chain's tail: -11 us at 5 000, -12 us at 10 000)
-    //   2048 full topology up to 512 groups: the side stream's L2 term and weight packing start BEHIND conv1's forward kernel
-    //      instead of beside it (-20 us at 79 groups, -5 at 313; +8 at 625 and +25 us for slim at 79, hence the bounds)
-    //   1024 batches above the tiny range (up to 2 048 groups): fc5 + heads + losses + head gradients as one kernel (-12 us at
-    //      5 000, -10 us at 10 000)
-    int sched;
     int profile;
     void *prof;          // cv_prof*, owned
     const char *stage_kernel[CV_NUM_STAGES];   // kernel (template instance) each stage of the last cv_forward chunk ran
@@ -234,9 +215,9 @@ int cv_launch_heads(cv_model *m, const float *h4, const float *h5, int tm, int64
                     hipStream_t st);
 bool cv_tile_supported(const cv_model *m);
 int cv_pack_train_weights(cv_model *m, hipStream_t st);
-// what a training pass over G groups will read and is stale; sw_ordered: sw already runs behind st (the caller forked)
-int cv_pack_for_training(cv_model *m, hipStream_t st, bool backward, int G, hipStream_t sw = nullptr, hipEvent_t fork = nullptr,
-                         hipEvent_t done = nullptr, bool *wait_before_dense = nullptr, bool sw_ordered = false, int phase = 0);
+// what a training pass over G groups will read and is stale; sw (== st: all of it on st) already runs behind st
+int cv_pack_for_training(cv_model *m, hipStream_t st, bool backward, int G, hipStream_t sw, hipEvent_t done,
+                         bool *wait_before_dense, int phase = 0);
 int cv_tile_train_convs(cv_model *m, const float *x, int64_t n, float *p1, float *a1, float *p2, float *a2,
                         float *p3, float *a3, hipStream_t st, const std::function<int()> *after_conv1 = nullptr);
 #define CV_DENSE_KSPLIT 8      // k ranges of the fc4 training forward at tiny batches (cv_tile_dense_fwd)
@@ -250,8 +231,8 @@ int cv_tile_train_tail(cv_model *m, const float *p3_tm, float *h4_tm, float *h5_
                        float *g16, float *g5pre_tm, float *part, const cv_train_dropout *drop, hipStream_t st, bool *done);
 int cv_tile_train_fc5_heads(cv_model *m, float *d4_tm, float *h5_tm, const float *y, int64_t n, int want_grad, float *g16,
                             float *g5pre_tm, hipStream_t st, bool *done);
-int cv_tile_fc5_dgrad(cv_model *m, const float *g_tm, float *gin_tm, int64_t n, hipStream_t st, const float *g16 = nullptr,
-                      const float *mask_tm = nullptr, const float *act_tm = nullptr);
+int cv_tile_fc5_dgrad(cv_model *m, const float *g_tm, float *gin_tm, int64_t n, hipStream_t st, const float *g16,
+                      const float *mask_tm, const float *act_tm);
 // act_below (layers without pooling, slim): the layer-below output; the result is then times selu' = its pre-activation gradient
 int cv_tile_fc4_dgrad(cv_model *m, const float *g_tm, float *gin_tm, int64_t n, hipStream_t st, const float *act_below = nullptr);
 int cv_tile_fc4_dgrad_unpool(cv_model *m, const float *g_tm, const float *pooled, const float *codes, float *gpre, int64_t n,

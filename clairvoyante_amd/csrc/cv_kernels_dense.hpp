@@ -139,8 +139,8 @@ struct heads_args {
     float *out16;
     const f4 *dact = nullptr;            // EPI 1 only: the output is multiplied by selu'-from-output of this map (same layout)
     // EPI 1, fc5's data gradient of a training pass (round 5): the base head's contribution, the dropout factor and
-    // selu'(fc4 output) follow on the store -- b_head_dgrad_tm's mode 1 arithmetic, one launch and one round trip of the
-    // map less.  hg_g16 == NULL: none.  g16 [n][16] head pre-activation gradients, wb [K][4] base-head weights,
+    // selu'(fc4 output) follow on the store, per value (v + sum_j g16[cand][j] * wb[k][j]) * mask * selu'(act), the sum
+    // as an ascending-j fma chain.  hg_g16 == NULL: none.  g16 [n][16] head pre-activation gradients, wb [K][4] base-head weights,
     // mask / act: tile-major maps in the output's layout.
     const float *hg_g16 = nullptr, *hg_wb = nullptr; const f4 *hg_mask = nullptr, *hg_act = nullptr; int64_t hg_n = 0; int hg_K = 0;
     // EPI 3 only (fc4 with fc5 and the heads on its tail): fc5's weights in k PAIRS [kp][24][64] (pack_dense_kpairs),
@@ -688,7 +688,7 @@ __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_t
 #pragma unroll
                     for (int k = 0; k < 4; k++) v[k] *= cv_selu_grad_from_out(y[k]);
                 }
-                if (hd.hg_g16) {             // + base head, * dropout factor, * selu'(fc4 output): b_head_dgrad_tm mode 1
+                if (hd.hg_g16) {             // + base head (fma chain over its 4 weights), * dropout factor, * selu'(fc4 output)
                     const size_t t = (size_t)(op - out_tm) + ob * 64;
                     const f4 mk = hd.hg_mask[t], y = hd.hg_act[t];
                     const int64_t cand = (int64_t)(g + r) * 16 + (lane & 15);
@@ -1459,8 +1459,8 @@ __global__ __launch_bounds__(256) void heads_train_tm(const f4 *__restrict__ d4,
 // Arithmetic and order per value are those of the three kernels (same bits); the loss sums leave as ONE ROW PER GROUP
 // (heads_train_tm: one per four groups), which t_loss_header adds in its fixed order.
 // ---------------------------------------------------------------------------
-// NWV waves per workgroup; PART: the fc4 output arrives as k-range partial sums (tiny batches) -- else (larger batches,
-// train_sched bit 10) fc4's own kernel has stored the dropped-out output (dr.d4) and step 1 only brings it into LDS.
+// NWV waves per workgroup; PART: the fc4 output arrives as k-range partial sums (tiny batches) -- else (larger batches)
+// fc4's own kernel has stored the dropped-out output (dr.d4) and step 1 only brings it into LDS.
 // (four-wave form: three workgroups per CU -- 168 registers, 40 dwords of them spilled -- so that the 625 workgroups of
 // train.py's batch are ONE round on 256 CUs instead of two: 52.7 -> 40.6 us, the step 2.060 -> 2.054 ms, 12 288: 2.574 ->
 // 2.559; profiles/r06/train_tail_occupancy_ab.txt)

@@ -650,21 +650,16 @@ static unsigned fc5_train_layout(const cv_model *m, int G)
 // inference pass that follows packs what it reads).  One launch on `st`; or, with a side stream, the convolution
 // fragments on `st` (the first kernels need them) and the dense / data-gradient fragments on `sw` next to the
 // convolution forward pass -- *wait_before_dense is then the event `st` has to wait for before the first dense layer.
-// phase 0: all of it; 1: only the convolution fragments on st; 2: only the rest on sw (the caller has ordered sw)
-int cv_pack_for_training(cv_model *m, hipStream_t st, bool backward, int G, hipStream_t sw, hipEvent_t fork, hipEvent_t done,
-                         bool *wait_before_dense, bool sw_ordered, int phase)
+// The caller has ordered sw behind st.  phase 0: all of it; 1: only the convolution fragments on st; 2: only the rest on sw
+int cv_pack_for_training(cv_model *m, hipStream_t st, bool backward, int G, hipStream_t sw, hipEvent_t done,
+                         bool *wait_before_dense, int phase)
 {
-    if (wait_before_dense) *wait_before_dense = false;
+    *wait_before_dense = false;
     unsigned need = CVL_CONV | CVL_HEADS | fc4_train_layout(m, G) | fc5_train_layout(m, G);
-    if (!(m->sched & 16)) need = CVL_FORWARD;          // every forward layout, as before round 5
     if (backward) need |= CVL_BACKWARD;
     const unsigned todo = need & ~m->packed_valid;
     if (!todo) return 0;
-    if (sw == st || !sw || !wait_before_dense) return pack_launch(m, st, todo);
-    if (!sw_ordered && phase != 1) {
-        CV_HIP(hipEventRecord(fork, st));              // behind the optimizer update of the previous step
-        CV_HIP(hipStreamWaitEvent(sw, fork, 0));
-    }
+    if (sw == st) return pack_launch(m, st, todo);
     if (phase != 2 && pack_launch(m, st, todo & CVL_CONV)) return 1;
     if (phase == 1) return 0;
     if (todo & ~CVL_CONV) {
@@ -1230,7 +1225,7 @@ int cv_tile_train_tail(cv_model *m, const float *p3_tm, float *h4_tm, float *h5_
     return 0;
 }
 
-// Larger batches of the full topology (up to 2 048 groups; train_sched bit 10): fc5, the heads, losses, head gradients and
+// Larger batches of the full topology (up to 2 048 groups): fc5, the heads, losses, head gradients and
 // the fc5-side data gradient in one kernel behind fc4's own (which has stored the dropped-out output d4_tm) -- the same
 // kernel as the tiny-batch tail without its first step, four waves per group.  *done = false: not this regime.
 int cv_tile_train_fc5_heads(cv_model *m, float *d4_tm, float *h5_tm, const float *y, int64_t n, int want_grad, float *g16,
@@ -1240,7 +1235,7 @@ int cv_tile_train_fc5_heads(cv_model *m, float *d4_tm, float *h5_tm, const float
     const cv_shapes &s = m->sh; const cv_arch &a = m->arch;
     const float *P = m->params; const int64_t *o = m->poff;
     const int G = (int)((n + 15) / 16);
-    if (G <= 0 || !is_full(a) || !(m->sched & 1024) || fc5_train_layout(m, G) != CVL_FC5S3 || s.nb4 != 21 || s.nb5 != 11) return 0;
+    if (G <= 0 || !is_full(a) || fc5_train_layout(m, G) != CVL_FC5S3 || s.nb4 != 21 || s.nb5 != 11) return 0;
     if (cv_layout_current(m, CVL_FC5S3 | CVL_HEADS, "training forward fc5 + heads")) return 1;
     if (m->loss_rows_used + G > m->loss_rows_cap) { cv_set_error("train_tail_tm: loss row buffer too small (internal)"); return 1; }
     double *rows = m->loss_rows + (size_t)m->loss_rows_used * 4;
@@ -1325,8 +1320,8 @@ int cv_tile_fc4_dgrad(cv_model *m, const float *g_tm, float *gin_tm, int64_t n, 
 }
 
 // g(d4)[k] = sum_j g5pre[j] W5[k][j]  (input TM with nb5 fragments, output TM with nb4 fragments)
-// g16 != NULL: the result is already fc4's PRE-ACTIVATION gradient -- the base head's contribution (g16, the base head's
-// weights), the dropout factor (mask_tm) and selu'(fc4 output act_tm) ride on the store
+// The result is fc4's PRE-ACTIVATION gradient: the base head's contribution (g16, the base head's weights), the dropout
+// factor (mask_tm) and selu'(fc4 output act_tm) ride on the store
 int cv_tile_fc5_dgrad(cv_model *m, const float *g_tm, float *gin_tm, int64_t n, hipStream_t st, const float *g16,
                       const float *mask_tm, const float *act_tm)
 {
@@ -1334,10 +1329,8 @@ int cv_tile_fc5_dgrad(cv_model *m, const float *g_tm, float *gin_tm, int64_t n, 
     const int G = (int)((n + 15) / 16);
     if (cv_layout_current(m, CVL_DFC5, "fc5 data gradient")) return 1;
     heads_args hd;
-    if (g16) {
-        hd.hg_g16 = g16; hd.hg_wb = m->params + m->poff[10]; hd.hg_mask = (const f4 *)mask_tm; hd.hg_act = (const f4 *)act_tm;
-        hd.hg_n = n; hd.hg_K = m->arch.fc4;
-    }
+    hd.hg_g16 = g16; hd.hg_wb = m->params + m->poff[10]; hd.hg_mask = (const f4 *)mask_tm; hd.hg_act = (const f4 *)act_tm;
+    hd.hg_n = n; hd.hg_K = m->arch.fc4;
     // full: three slabs of 7 output fragments -- as one workgroup per 8 groups with all 21 the kernel took 32 us at ANY
     // batch (2 waves x 11 k steps x 84 MFMAs per SIMD on 10 .. 79 CUs); the values do not depend on the slab width
     if (is_full(m->arch)) return launch_dense<7, 8, 1>(g_tm, s.nb5, m->wpd_fc5, nullptr, 0, gin_tm, G, st, 3, 1, nullptr, hd);

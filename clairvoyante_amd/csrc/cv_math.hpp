@@ -61,19 +61,8 @@ constexpr float SELU_SA = (float)(1.0507009873554804934193349852946 * 1.67326324
 // and the result is -0.0, computed as -(SA - SA*y)): the backward pass takes selu' from the layer OUTPUT (cv_unpool.hpp:
 // sign bit set -> y + SA, else SCALE), and an output of +0 there would read as the x >= 0 branch -- one element in ~3e7,
 // a flip of selu' from 1.758 to 1.051 that the reference (selu.py:21-25 through tf.where's gradient) does not have.
-// (Development build flag CV_FAST_SELU: the negative branch through the hardware exponential, v_exp_f32(x * log2 e) and
-// one fma -- 5 element operations instead of 18, ~1 ulp of 2^t instead of the fixed sequence: NOT the canonical
-// arithmetic, no bitwise parity with the CPU checker; measured against the exact path by tools/gpu_fast_selu_ab.sh.)
 __device__ __forceinline__ float selu(float x)
 {
-#ifdef CV_FAST_SELU
-    {
-        const float e = __builtin_amdgcn_exp2f(x * 1.44269504088896341f);       // x <= -104: 0 (the fma then gives -SA)
-        const float neg = __builtin_fmaf(e, SELU_SA, -SELU_SA);
-        const float pos = SELU_SCALE * x;
-        return x < 0.0f ? neg : __builtin_fabsf(pos);
-    }
-#endif
     const float xc = __builtin_amdgcn_fmed3f(x, -87.33654475055310f, 0.0f);
     float z = __builtin_rintf(xc * 1.44269504088896341f);
     float r = __builtin_fmaf(z, -0.69314718055994530942f, xc);
@@ -101,13 +90,6 @@ typedef float f2v __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ f2v selu2(f2v x)
 {
-#ifdef CV_FAST_SELU
-    {
-        f2v o;
-        o[0] = selu(x[0]); o[1] = selu(x[1]);
-        return o;
-    }
-#endif
     f2v xc;
     xc[0] = __builtin_amdgcn_fmed3f(x[0], -87.33654475055310f, 0.0f);
     xc[1] = __builtin_amdgcn_fmed3f(x[1], -87.33654475055310f, 0.0f);

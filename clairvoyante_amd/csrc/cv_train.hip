@@ -523,41 +523,6 @@ static int launch_unpool(const float *gpool, const float *pooled, const float *c
     return 0;
 }
 
-// heads: data gradients in TM layout, fused with the SELU' (and dropout) factor of the layer they flow into.
-//   mode 0: g5pre = (sum over the three fc5-side heads) * selu'(h5)                      -- all entries written, padding = 0
-//   mode 1: g4pre = (gd4 + base-head contribution) * amask * selu'(h4)                   -- gd4 = fc5's data gradient
-// (one pass instead of a head-gradient pass plus an element-wise pass per layer)
-__global__ void b_head_dgrad_tm(const float *__restrict__ ghpre, const float *__restrict__ wb,
-                                const float *__restrict__ wz, const float *__restrict__ wt,
-                                const float *__restrict__ wl, int K, int KB, int64_t n, int64_t G, int mode,
-                                const float *__restrict__ gin_tm, const float *__restrict__ act_tm,
-                                const float *__restrict__ mask_tm, float *__restrict__ out_tm)
-{
-    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= G * KB * 256) return;
-    int s = (int)(t & 3), lane = (int)((t >> 2) & 63);
-    int64_t frag = t >> 8;
-    int kb = (int)(frag % KB);
-    int64_t g = frag / KB;
-    int c = lane & 15, kq = lane >> 4;
-    int k = 16 * kb + 4 * s + kq;
-    int64_t cand = g * 16 + c;
-    float acc = 0.0f;
-    if (cand < n && k < K) {
-        const float *gi = ghpre + (size_t)cand * 16;
-        if (mode == 0) {
-            for (int j = 0; j < 2; j++) acc = __builtin_fmaf(gi[4 + j], wz[(size_t)k * 2 + j], acc);
-            for (int j = 0; j < 4; j++) acc = __builtin_fmaf(gi[6 + j], wt[(size_t)k * 4 + j], acc);
-            for (int j = 0; j < 6; j++) acc = __builtin_fmaf(gi[10 + j], wl[(size_t)k * 6 + j], acc);
-        } else {
-            for (int j = 0; j < 4; j++) acc = __builtin_fmaf(gi[j], wb[(size_t)k * 4 + j], acc);
-        }
-    }
-    float gact = mode == 0 ? acc : gin_tm[t] + acc;
-    if (mask_tm) gact *= mask_tm[t];
-    out_tm[t] = gact * selu_grad_from_out(act_tm[t]);
-}
-
 struct slab {
     float *base; size_t used, cap;
     float *take(size_t nfloat) { float *p = base + used; used += (nfloat + 63) / 64 * 64; return used <= cap ? p : nullptr; }
@@ -674,10 +639,10 @@ struct tr_fork {
     int tail_first;
     hipEvent_t mark;       // the newest marker recorded on st; mark_fresh: nothing was enqueued on st since
     bool mark_fresh;
-    bool share;            // launch sites at the same point of st share a marker (train_sched bit 3; see cv_internal.hpp)
+    bool share;            // launch sites at the same point of st share a marker
     hipEvent_t next_event() { return m->tr_ev[k++ % (CV_TR_EVENTS - 1)]; }
     int side_of(int site) const { return tail_only ? (site >= tail_first && nside > 1 ? 1 : 0) : site % nside; }
-    // side stream of launch site `site` (0 heads, 1 fc5, 2 fc4, 3 conv3, 4 conv2, 5 conv1), made to wait for
+    // side stream of launch site `site` (0 heads, 1 fc5, 2 fc4, 3 conv3, 4 conv2; conv1's stays on st), made to wait for
     // everything enqueued on st so far; st itself when the step runs in stream order.  A marker costs the main stream
     // ~6 us (a barrier packet between two kernels: profiles/r05/train_1250_timeline_before.txt), so two launch sites with
     // no kernel of st between them share one (`same_point`).
@@ -731,8 +696,8 @@ struct tr_fork {
 
 // the fixed-order loss sums + the bucket's loss header (t_loss_header, below) launched from inside a slice
 struct tr_header { double lambda; bool l2; };
-// train_sched bit 11: the side stream's work ahead of the backward pass (L2 term, the dense / data-gradient weight packing)
-// is forked behind conv1's forward kernel (first slice of a step) instead of at the head of the step
+// the side stream's work ahead of the backward pass (L2 term, the dense / data-gradient weight packing) forked behind
+// conv1's forward kernel (first slice of a step) instead of at the head of the step
 struct tr_defer { bool on; float lambda; bool tile_path; };
 static int launch_l2(cv_model *m, hipStream_t sw, bool tile_path);
 
@@ -751,11 +716,10 @@ __global__ __launch_bounds__(256) void t_loss_header(double *__restrict__ loss, 
 // backward pass -- instead of at the tail of the step on st (8 us + a launch off the critical path).
 static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t n, int64_t cand0, bool backward,
                             float drop4, uint64_t seed, uint64_t step, hipStream_t st, hipStream_t sw,
-                            hipEvent_t dense_ready, bool sw_ordered, const tr_header *hdr_now, const tr_defer *defer,
+                            hipEvent_t dense_ready, const tr_header *hdr_now, const tr_defer *defer,
                             bool *hdr_launched)
 {
     const cv_shapes &s = m->sh; const cv_arch &a = m->arch;
-    const float *P = m->params; const int64_t *o = m->poff;
     const int64_t np = (n + 15) / 16 * 16;             // TM buffers hold whole groups
     const int64_t Gn = np / 16;
     slab sb{m->t_buf, 0, m->t_bytes / sizeof(float)};
@@ -775,16 +739,16 @@ static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t
     bool pack_wait = false;       // dbg5 = 1: all packing in one launch on st, as before
     if (defer && defer->on && sw != st && m->dbg[5] != 1) {
         // convolution fragments now; the marker, the L2 term and the rest of the packing behind conv1's kernel
-        if (cv_pack_for_training(m, st, backward, (int)Gn, sw, m->tr_pack_fork, m->tr_pack_done, &pack_wait, false, 1)) return 1;
+        if (cv_pack_for_training(m, st, backward, (int)Gn, sw, m->tr_pack_done, &pack_wait, 1)) return 1;
         const std::function<int()> hook = [&]() -> int {
             CV_HIP(hipEventRecord(m->tr_ev[CV_TR_EVENTS - 1], st));
             CV_HIP(hipStreamWaitEvent(sw, m->tr_ev[CV_TR_EVENTS - 1], 0));
             if (defer->lambda != 0.0f && launch_l2(m, sw, defer->tile_path)) return 1;
-            return cv_pack_for_training(m, st, backward, (int)Gn, sw, m->tr_pack_fork, m->tr_pack_done, &pack_wait, true, 2);
+            return cv_pack_for_training(m, st, backward, (int)Gn, sw, m->tr_pack_done, &pack_wait, 2);
         };
         if (cv_tile_train_convs(m, x, n, tp[0], ta[0], tp[1], ta[1], tp[2], ta[2], st, &hook)) return 1;
     } else {
-        if (cv_pack_for_training(m, st, backward, (int)Gn, m->dbg[5] == 1 ? st : sw, m->tr_pack_fork, m->tr_pack_done, &pack_wait, sw_ordered)) return 1;
+        if (cv_pack_for_training(m, st, backward, (int)Gn, m->dbg[5] == 1 ? st : sw, m->tr_pack_done, &pack_wait)) return 1;
         if (cv_tile_train_convs(m, x, n, tp[0], ta[0], tp[1], ta[1], tp[2], ta[2], st)) return 1;
     }
     if (pack_wait) CV_HIP(hipStreamWaitEvent(st, m->tr_pack_done, 0));
@@ -812,7 +776,7 @@ static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t
     CV_HIP(hipGetLastError());
     if (!backward) return 0;
     // ---- backward buffers (TM gradients; the weight-gradient kernels transpose their operands on the way in)
-    float *tgd4 = sb.take(np * f4u), *tg4pre = sb.take(np * f4u);
+    float *tg4pre = sb.take(np * f4u);
     float *tgpre[3], *tgin[3];
     for (int l = 0; l < 3; l++) { tgpre[l] = sb.take(np * fa[l]); tgin[l] = sb.take(np * fp[l]); }
     if (!tgin[2]) { cv_set_error("training workspace too small"); return 1; }
@@ -823,7 +787,7 @@ static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t
     // (measured, one box, alternating: at 625 groups of the full topology a shared marker lets the main stream run 6 us
     // ahead and the step comes out 39 us LONGER -- the weight gradients then meet the fc4 / conv3 data gradients on the
     // CUs at another moment; 2 500 and 5 000 candidates and the slim topology gain with it)
-    f.share = (m->sched & 8) && (Gn <= 512 || !m->wpr_fc4);
+    f.share = Gn <= 512 || !m->wpr_fc4;
     for (int i = 0; i < CV_TR_SIDES; i++) { f.side[i] = nullptr; f.used[i] = false; }
     if (sw != st) {
         f.side[f.nside++] = sw;
@@ -866,15 +830,9 @@ static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t
     if (f.to_side(1, &sx, true)) return 1;
     if (cv_tile_dense_wgrad(m, 5, td4, tg5pre, n, sx)) return 1;
     f.st_moved();
-    // fc5's data gradient + the base head's contribution, then dropout4 + selu' (h4 is the SELU output before dropout): on
-    // the kernel's store, or (train_sched bit 5 off) as an element-wise pass behind it -- the same operations per value
-    if (m->sched & 32) {
-        if (cv_tile_fc5_dgrad(m, tg5pre, tg4pre, n, st, ghpre, tmask, th4)) return 1;
-    } else {
-        if (cv_tile_fc5_dgrad(m, tg5pre, tgd4, n, st)) return 1;
-        b_head_dgrad_tm<<<nblk(Gn * s.nb4 * 256, 256), 256, 0, st>>>(ghpre, P + o[10], P + o[12], P + o[14], P + o[16], a.fc4,
-                                                                   s.nb4, n, Gn, 1, tgd4, th4, tmask, tg4pre);
-    }
+    // fc5's data gradient + the base head's contribution, then dropout4 + selu' (h4 is the SELU output before dropout), all
+    // on the kernel's store
+    if (cv_tile_fc5_dgrad(m, tg5pre, tg4pre, n, st, ghpre, tmask, th4)) return 1;
     f.st_moved();
     // fc4's data gradient; full topology: fused with conv3's max-pool backward + SELU' (dbg3 = 1: as two kernels)
     const bool fused3 = m->wpr_fc4 != nullptr && m->dbg[3] != 1;
@@ -909,13 +867,12 @@ static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t
         if (conv1_fused) m->last_tr_gpre[0] = nullptr;      // (cv_get_activation 21 reports it missing)
         if (!have_gpre && !conv1_fused && launch_unpool(tgin[l], tp[l], ta[l], tgpre[l], Gn, H, NT, a.pool[l], st, (m->dbg[2] == 1 || m->dbg[2] == 6) ? (1 << 30) : (m->dbg[2] == 2 ? 0 : m->tiny_g), m->dbg[2] == 1 || m->dbg[2] == 4)) return 1;
         f.st_moved();
-        // The first layer's weight gradient is the LAST work of the backward pass: nothing of st is left to run beside it.
-        // At tiny batches it stays on st (a marker, the hand-over to the side stream and the wait for it back cost ~25 us
-        // of an otherwise idle chip for a 17 us kernel); at large ones the side stream keeps it off the chain's tail.
-        if (l == 0 && ((Gn <= m->tiny_g && (m->sched & 2)) || (m->sched & 512))) sx = st;
-        else {
-            if (f.to_side(5 - l, &sx)) return 1;
-        }
+        // The first layer's weight gradient is the LAST work of the backward pass: nothing of st is left to run beside it,
+        // so it stays on st.  (At tiny batches a marker, the hand-over to the side stream and the wait for it back cost ~25 us
+        // of an otherwise idle chip for a 17 us kernel; at large ones the side stream put it on the chain's tail: -11 us at
+        // 5 000 candidates, -12 us at 10 000 on st.)
+        if (l == 0) sx = st;
+        else if (f.to_side(5 - l, &sx)) return 1;
         if (l == 0) {        // first layer: X viewed as [33][16] fragments, read in place
             bool done1 = false;
             if (conv1_fused && cv_tile_conv1_wgrad_unpool(m, x, tgin[0], tp[0], ta[0], n, sx, &done1)) return 1;
@@ -926,17 +883,17 @@ static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t
             else if (cv_tile_conv_dgrad(m, l, tgpre[l], tgin[l - 1], n, st)) return 1;
         }
     }
-    if ((Gn <= m->tiny_g && Gn <= CV_TINY_PARTS_MAX_G && (m->sched & 2) && (m->sched & 128)) ? f.join_chained() : f.join()) return 1;
+    if ((Gn <= m->tiny_g && Gn <= CV_TINY_PARTS_MAX_G) ? f.join_chained() : f.join()) return 1;
     CV_HIP(hipGetLastError());
     return 0;
 }
 
 static int train_slice(cv_model *m, const float *x, const float *y, int64_t n, int64_t cand0, bool backward,
                        float drop4, uint64_t seed, uint64_t step, hipStream_t st, hipStream_t sw, hipEvent_t dense_ready,
-                       bool sw_ordered, const tr_header *hdr_now, const tr_defer *defer, bool *hdr_launched)
+                       const tr_header *hdr_now, const tr_defer *defer, bool *hdr_launched)
 {
     if (m->impl == 1 && cv_tile_supported(m))
-        return train_slice_tile(m, x, y, n, cand0, backward, drop4, seed, step, st, sw, dense_ready, sw_ordered, hdr_now, defer, hdr_launched);
+        return train_slice_tile(m, x, y, n, cand0, backward, drop4, seed, step, st, sw, dense_ready, hdr_now, defer, hdr_launched);
     if (train_slice_plain(m, x, y, n, cand0, backward, drop4, seed, step, st)) return 1;
     if (dense_ready) CV_HIP(hipEventRecord(dense_ready, st));
     return 0;
@@ -1044,7 +1001,6 @@ static int train_workspace(cv_model *m, int64_t n, int64_t *slice_out)
         CV_HIP(hipEventCreateWithFlags(&m->tr_dense_ready, hipEventDisableTiming));
         CV_HIP(hipEventCreateWithFlags(&m->tr_l2_done, hipEventDisableTiming));
         CV_HIP(hipEventRecord(m->tr_l2_done, m->tr_side));       // (recorded once, so that a wait before any L2 kernel passes)
-        CV_HIP(hipEventCreateWithFlags(&m->tr_pack_fork, hipEventDisableTiming));
         CV_HIP(hipEventCreateWithFlags(&m->tr_pack_done, hipEventDisableTiming));
     }
     *slice_out = slice;
@@ -1071,7 +1027,7 @@ static int train_enqueue(cv_model *m, const float *x, const float *y, int64_t n,
     // the first slice of a step and adds for the later ones (cv_model::tr_accumulate), and t_loss_header replaces the
     // loss sums -- nothing needs zeroing (the 6.5 MB memset was the first 5-7 us of every step).  An empty batch (a rank
     // without candidates) runs no kernel: its gradient is zeroed here.  All-plain path: atomics into zeroed buffers.
-    const bool no_memset = tile_path && backward && n > 0 && (m->sched & 64);
+    const bool no_memset = tile_path && backward && n > 0;
     m->tr_accumulate = no_memset ? 0 : 1;
     if (no_memset) {
         /* nothing */
@@ -1085,14 +1041,13 @@ static int train_enqueue(cv_model *m, const float *x, const float *y, int64_t n,
         if (backward) CV_HIP(hipMemsetAsync(m->grads, 0, sizeof(float) * m->poff[CV_NUM_PARAMS], st));      // (a caller's bucket)
     }
     // ONE marker for everything the side stream does ahead of the backward pass -- the L2 term and the weight packing
-    // both depend on the weights alone, i.e. on the optimizer update of the previous step (cv_pack_for_training is
-    // told that sw is ordered already)
-    const bool one_marker = (m->sched & 4) != 0;
+    // both depend on the weights alone, i.e. on the optimizer update of the previous step (cv_pack_for_training relies
+    // on sw being ordered already)
     // (full topology up to 512 groups: -20 us at 79 groups, -5 at 313, +8 at 625 -- profiles/r05/step_ab_session11_side_work_behind_conv1.txt;
     // slim, whose first layer is a quarter of the work and whose fc4 needs its weights sooner: +25 us at 79 groups, so not there)
-    const tr_defer defer{(m->sched & 2048) != 0 && one_marker && tile_path && sw != st && n > 0 && m->dbg[5] != 1 &&
+    const tr_defer defer{tile_path && sw != st && n > 0 && m->dbg[5] != 1 &&
                          m->wpr_fc4 != nullptr && (n < slice ? n : slice) <= 512 * 16, lambda, tile_path};
-    const bool sw_ordered = sw != st && n > 0 && (one_marker || lambda != 0.0f);
+    const bool sw_ordered = sw != st && n > 0;
     if (sw_ordered && !defer.on) {
         CV_HIP(hipEventRecord(m->tr_ev[CV_TR_EVENTS - 1], st));
         CV_HIP(hipStreamWaitEvent(sw, m->tr_ev[CV_TR_EVENTS - 1], 0));
@@ -1108,7 +1063,7 @@ static int train_enqueue(cv_model *m, const float *x, const float *y, int64_t n,
     const tr_header hdr_early{(double)lambda, lambda != 0.0f};
     // (tiny batches: behind the heads kernel on sw; larger ones: on the second side stream -- at train.py's batch sw is as
     // long as the main chain, and 14 us of header at its head made the step 33 us longer, profiles/r05/step_ab_session3.txt)
-    const bool early = backward && tile_path && sw_ordered && n <= slice && (l2_done || lambda == 0.0f) && (m->sched & 1);
+    const bool early = backward && tile_path && sw_ordered && n <= slice && (l2_done || lambda == 0.0f);
     bool hdr_launched = false;
     // option keep_activations and several slices: the dropout maps of every slice are kept (cv_get_activation 6 / 7 then
     // covers the whole batch, and the oracle tests can feed a multi-slice step's own keep mask back); one slice: in place
@@ -1131,7 +1086,7 @@ static int train_enqueue(cv_model *m, const float *x, const float *y, int64_t n,
         // gradients final", so the side streams are not gathered for it)
         hipEvent_t ev = (backward && last && comm) ? m->tr_dense_ready : nullptr;
         if (train_slice(m, x + (size_t)off * (CV_INPUT_H * 16), y + (size_t)off * 16, cn, off, backward, drop4,
-                        seed, step, st, sw, ev, sw_ordered && one_marker, early ? &hdr_early : nullptr, off == 0 ? &defer : nullptr,
+                        seed, step, st, sw, ev, early ? &hdr_early : nullptr, off == 0 ? &defer : nullptr,
                         &hdr_launched))
             return 1;
         recorded = recorded || ev != nullptr;

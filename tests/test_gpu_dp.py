@@ -235,28 +235,17 @@ def test_backward_kernel_variants_give_the_same_bits(oracle, arch, n):
         return out
     ref = run({})
     # (dbg5 = 8 / 4: fc4's weight-gradient kernel with one / two input fragments per wave over the same candidate ranges)
-    # (round 5: dbg2 = 4 the thread-per-row unpool at tiny batches instead of row segments; option train_sched: the bits of
-    # the re-cut schedule -- early loss header, conv1's weight gradient on the main stream, one fork marker, shared launch-site
-    # markers, per-layout packing -- switched off in groups)
+    # (round 5: dbg2 = 4 the thread-per-row unpool at tiny batches instead of row segments)
     # (round 6: dbg6 = row parts of fc4's data gradient + unpool, + 100 = 4-wave workgroups; the default picks them by the
     # number of groups -- 83 candidates: 4 waves x 4 parts, 640: 4 waves x 2, 1 250: 8 waves x 2, larger: 8 waves x 1)
     variants = ({"dbg3": 1}, {"train_side_streams": 1}, {"dbg5": 1}, {"dbg6": 3}, {"dbg6": 1}, {"dbg6": 104}, {"dbg6": 102}, {"dbg7": 1},
                 {"dbg0": 9, "dbg1": 9}, {"dbg0": 7, "dbg1": 7}, {"dbg1": 8}, {"dbg2": 3}, {"dbg3": 1, "train_overlap": 0},
-                {"dbg2": 4}, {"train_sched": 0}, {"train_sched": 254}, {"train_sched": 21}, {"train_sched": 42}, {"train_sched": 223}, {"train_sched": 191}, {"train_sched": 127}, {"train_sched": 511}, {"train_sched": 255}, {"train_sched": 1023}, {"train_sched": 1791}, {"dbg4": 4}, {"dbg2": 1}, {"dbg2": 2}, {"dbg5": 8}, {"dbg5": 4}) if arch == "full" else \
+                {"dbg2": 4}, {"dbg4": 4}, {"dbg2": 1}, {"dbg2": 2}, {"dbg5": 8}, {"dbg5": 4}) if arch == "full" else \
                ({"dbg4": 3}, {"dbg4": 9}, {"train_side_streams": 1}, {"dbg0": 9, "dbg1": 9}, {"dbg0": 7, "dbg1": 7},
-                {"dbg5": 1, "dbg4": 3, "train_overlap": 0}, {"train_sched": 0}, {"train_sched": 21}, {"train_sched": 42}, {"train_sched": 223}, {"train_sched": 191}, {"train_sched": 127}, {"train_sched": 255}, {"train_sched": 1791})
-    # (batches above the tiny range: fc5 + heads + losses + head gradients are one kernel behind fc4's by default, train_sched
-    # bit 10; its loss sums leave as one row per group instead of one per four, so a variant that switches it off -- every
-    # explicit train_sched value here -- may differ from the default in the last bits of the reported loss)
-    big = arch == "full" and n > 2560
-    if big:
-        variants = variants + ({"train_sched": 767},)
+                {"dbg5": 1, "dbg4": 3, "train_overlap": 0})
     for opts in variants:
         got = run(opts)
-        if big and "train_sched" in opts and not (opts["train_sched"] & 1024):
-            assert np.allclose(ref[0], got[0], rtol=1e-12, atol=0), opts
-        else:
-            assert ref[0] == got[0], opts
+        assert ref[0] == got[0], opts
         assert np.array_equal(ref[1].view(np.uint32), got[1].view(np.uint32)), opts
         assert np.array_equal(ref[2].view(np.uint32), got[2].view(np.uint32)), opts
 
@@ -300,28 +289,32 @@ def test_packed_layouts_follow_the_weights_through_mixed_passes(oracle, arch):
 
 
 @pytest.mark.parametrize("arch,n", [("full", 1250), ("full", 10000), ("slim", 3000), ("full", 70001)])
-def test_a_step_writes_every_gradient_element(oracle, arch, n):
+def test_a_step_gives_the_same_bits_whatever_the_bucket_held(oracle, arch, n):
     """the step does not zero its gradient bucket (the second passes of the weight gradients STORE for the first slice of
-    a step): with the bucket full of NaN beforehand every element must come out finite and equal to the step that starts
-    from a zeroed bucket (train_sched bit 6 off) -- one slice, and two (the second one adds)"""
+    a step): whatever the bucket held beforehand -- NaN, 0.0, 1e30 -- every element must come out finite and the step must
+    give the same bits; an element that the first slice added to instead of storing, or that no kernel wrote, would carry
+    the old contents -- one slice, and two (the second one adds)"""
     import torch
-    from clairvoyante_amd import synth
+    from clairvoyante_amd import _lib, synth
     xt, cls, rf, alt, il = synth.make_candidates(n, seed=49, device="cuda", return_class=True)
     y = synth.make_labels(cls, rf, alt, il)
     P = common.bench_params(oracle, arch)
     out = []
-    for sched in (3839, 3775):
-        m = _model(arch); m.setParameters(P); m.setOption("train_sched", sched)
+    for fill in (float("nan"), 0.0, 1e30):
+        m = _model(arch); m.setParameters(P)
+        with pytest.raises(_lib.CvError, match="unknown option"):
+            m.setOption("train_sched", 3839)          # retired: the step's schedule is fixed
         m._dropout_seed = 7; m.setLearningRate(1e-3); m.setL2RegularizationLambda(1e-3)
-        m._ensure_bucket().fill_(float("nan"))
+        m._ensure_bucket().fill_(fill)
         loss = float(m.train(xt, y)[0])
         g = _flat(m, 1)
         assert np.isfinite(g).all() and np.isfinite(loss)
         out.append((loss, g, _flat(m, 0)))
         m.close()
-    assert out[0][0] == out[1][0]
-    assert np.array_equal(out[0][1].view(np.uint32), out[1][1].view(np.uint32))
-    assert np.array_equal(out[0][2].view(np.uint32), out[1][2].view(np.uint32))
+    for o in out[1:]:
+        assert out[0][0] == o[0]
+        assert np.array_equal(out[0][1].view(np.uint32), o[1].view(np.uint32))
+        assert np.array_equal(out[0][2].view(np.uint32), o[2].view(np.uint32))
 
 
 def test_deferred_losses_sum_to_the_per_step_losses(oracle):

@@ -1,6 +1,6 @@
 """Development: a second build of the library with extra compile flags, next to the in-tree one, for same-box A/B runs
-through CV_HIP_LIB (tools/gpu_lib_ab.sh, tools/gpu_fast_selu_ab.sh):
-    python tools/build_variant_lib.py fast -DCV_FAST_SELU     ->  clairvoyante_amd/csrc/libclairvoyante_hip_fast.so
+through CV_HIP_LIB (tools/gpu_lib_ab.sh, tools/gpu_lib_step_ab.sh):
+    python tools/build_variant_lib.py phases -DCV_WG_STAMP -DCV_ROW_PHASES  ->  clairvoyante_amd/csrc/libclairvoyante_hip_phases.so
 Objects go to a temporary directory; the in-tree objects and library are not touched."""
 import os
 import subprocess

@@ -2,7 +2,7 @@
 # Training-step A/B on ONE box, alternating (box-to-box differences are as large as the effects measured): the base
 # library (csrc/libclairvoyante_hip_base.so, built from that commit with clairvoyante_amd/build.py's flags) against the
 # in-tree build, plus any number of in-tree settings given as "label|bench flags".  How profiles/r05/step_ab_*.txt were made.
-#   bash tools/gpu_step_ab.sh TAG "1250 10000" 3 "sched 255|--sched 255" "two kernels for conv1|--dbg 4=4"
+#   bash tools/gpu_step_ab.sh TAG "1250 10000" 3 "one side stream|--sides 1" "two kernels for conv1|--dbg 4=4"
 set -u
 TAG=${1:-stepab}; BATCHES=${2:-"1250 10000"}; R=${3:-3}; shift 3 || true
 OUT=gpurun_out/$TAG
