@@ -7,6 +7,10 @@ batch of 65 536 synthetic [33,4,4] pileup tensors that are already resident in H
 64 steps = the 4 194 304-tensor set).  With --gpus N every rank runs the same number of
 steps on its own shard (candidates are independent: no data-path collective) and the value
 is the whole-job rate.  One JSON line is printed by rank 0.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  What else the line can carry
+(the slim and training legs, the training parity check, the host legs, the CPU baselines and the parity block; in
+--mode pileup the CPU leg) runs only with --full, outside every timed region.
 """
 import argparse
 import ctypes
@@ -378,7 +382,7 @@ def pileup_main(args):
                 "candidate_ms": ms["candidate_ms"], "scatter_ms": ms["scatter_ms"], "finalize_ms": ms["finalize_ms"],
                 "finalize_GBps": pl.n * (33 * 9 * 4 + 33 * 64) / (ms["finalize_ms"] * 1e-3) / 1e9}
         cpu = None
-        if not args.no_cpu and ws == 1:          # the CPU leg runs at N = 1 only
+        if args.full and not args.no_cpu and ws == 1:          # the CPU leg runs at N = 1 only
             from oracle import create_tensor as oct_, extract_candidates as oec
             lines = text[:100000 * (len(text) // n_reads)].decode().splitlines()        # first 100 000 reads
             span = int(lines[-1].split("\t")[3]) + read_len
@@ -990,9 +994,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--arch", default="full", choices=["full", "slim"])
     ap.add_argument("--batch", type=int, default=BATCH)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="infer mode: skip the slim / training legs (configs 4, 5)")
-    ap.add_argument("--no-host", action="store_true", help="infer mode: skip the host legs (predict(numpy), callVar over a text file, TrainAll over a .bin)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what else the line can carry: infer mode: the slim / training legs, "
+                         "the training parity check, the host legs, the CPU baselines and the parity block; pileup mode: the "
+                         "CPU leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="--full, infer mode: skip the slim / training legs (configs 4, 5)")
+    ap.add_argument("--no-host", action="store_true", help="--full, infer mode: skip the host legs (predict(numpy), callVar over a text file, TrainAll over a .bin)")
     ap.add_argument("--dry", action="store_true", help="start the ranks, count them, print the skeleton; no GPU work")
     ap.add_argument("--sync-loss", action="store_true", help="train mode: read the losses back after every step (m.train)")
     ap.add_argument("--variant", type=int, default=None, help="infer mode: option variant (kernel selection, A/B)")
@@ -1059,7 +1067,7 @@ def main():
     # Configs 5 and 4 under the same clock, OUTSIDE the headline's timed region: slim inference at the same batch, and
     # optimizer steps on train.py's global batch of 10 000 split over the ranks (one gradient all-reduce per step) --
     # at N = 1 also at 1 250, one rank's share of that batch on 8 GPUs; at N > 1 also at 10 000 PER rank.
-    if not args.no_extras and args.arch == "full" and args.variant is None:
+    if args.full and not args.no_extras and args.arch == "full" and args.variant is None:
         t_extra = time.perf_counter()
         sres, sm, _sp, _sb, _so = run_infer("slim", args.batch, 32, 4, rank, ws, dev, batches=batches[:16])
         sm.close()
@@ -1092,7 +1100,7 @@ def main():
             line["host"]["seconds"] = time.perf_counter() - t_host
 
     if rank == 0:
-        if not args.no_cpu and ws == 1:          # the CPU leg (and the parity block it feeds) runs at N = 1 only
+        if args.full and not args.no_cpu and ws == 1:          # the CPU leg (and the parity block it feeds) runs at N = 1 only
             xs = torch.cat([b_ for b_ in batches[:4]])[:262144].cpu().numpy()
             cb, ref, n = cpu_baseline(args.arch, P, xs)
             got = m.predict_device(torch.from_numpy(xs[:n]).to(dev)).cpu().numpy()

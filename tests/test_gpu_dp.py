@@ -676,14 +676,14 @@ def test_rccl_code_path_with_one_rank_equals_the_plain_step(oracle, tmp_path):
 
 
 def test_bench_line_under_two_ranks_sharing_the_gpu(tmp_path):
-    """`python bench.py --gpus 2` end to end with two real ranks (backend gloo, both on the one GPU: CV_SHARE_DEVICES): it
-    starts its own ranks, rank 0 prints one line with n_gpus = rccl_ranks = 2, the slim leg and the training legs (global
-    batch 10 000 split over the ranks, and 10 000 per rank) -- the flow the driver runs at N > 1, timings aside"""
+    """`python bench.py --gpus 2 --full` end to end with two real ranks (backend gloo, both on the one GPU: CV_SHARE_DEVICES):
+    it starts its own ranks, rank 0 prints one line with n_gpus = rccl_ranks = 2, the slim leg and the training legs (global
+    batch 10 000 split over the ranks, and 10 000 per rank) -- the --full flow at N > 1, timings aside"""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CV_SHARE_DEVICES="1", CV_DIST_BACKEND="gloo", PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-cpu"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--full", "--no-cpu"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -694,6 +694,30 @@ def test_bench_line_under_two_ranks_sharing_the_gpu(tmp_path):
     assert set(b["train"]) == {"10000", "10000_per_rank", "slim_10000"}
     assert b["train"]["10000"]["per_rank_batch"] == 5000 and b["train"]["10000_per_rank"]["per_rank_batch"] == 10000
     assert all(np.isfinite(v["final_loss"]) for v in b["train"].values())
+
+
+def test_plain_bench_line_carries_the_headline_only(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the headline line (metric, value,
+    unit, higher_is_better, dtype, ms_per_step with value = batch / ms_per_step) and the last step's outputs; none of the
+    legs that only --full runs (slim, training, parity, CPU baselines, host)"""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(PYTHONPATH=ROOT)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    b = lines[0]
+    assert b["metric"] == "candidate tensors/sec" and b["unit"] == "candidates/s" and b["higher_is_better"] is True
+    assert b["dtype"] == "f32" and b["n_gpus"] == 1 and b["steps"] == 3 and b["warmup"] == 1
+    assert b["value"] > 1e6 and abs(b["value"] - 65536 / (b["ms_per_step"] * 1e-3)) <= 1e-6 * b["value"]
+    assert not {"slim", "train", "extras_seconds", "host", "cpu_baseline", "cpu_baseline_torch", "parity"} & set(b)
+    got = np.load(out / "out16.npy")
+    assert got.shape == (65536, 16) and got.dtype == np.float32 and np.isfinite(got).all()
+    assert not (out / "out16_rows.npy").exists()
 
 
 @pytest.mark.parametrize("mode", ["infer", "train", "exchange"])

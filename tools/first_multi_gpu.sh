@@ -8,7 +8,7 @@
 #                the step / the dense 95 % under the backward pass): step time, exchange alone, compute alone, hidden fraction,
 #                exchange_busbw_GBps of the step's own exchange                                   bench.py --mode train
 #   4 train at 10 000 per rank (the efficient operating point)                                    bench.py --mode train --batch
-#   5 infer      the headline line with its slim / training legs                                  bench.py
+#   5 infer      the headline line with its slim / training legs                                  bench.py --full
 # usage: bash tools/first_multi_gpu.sh [N=8] [OUT=gpurun_out/first_multi_gpu]      (one node; run where the GPUs are)
 set -u
 N=${1:-8}
@@ -32,7 +32,7 @@ CV_EXCHANGE=one stage 3_train_one_collective 600 --mode train --steps 40 --warmu
 CV_EXCHANGE=split stage 3_train_split 600 --mode train --steps 40 --warmup 4
 stage 3_train_planned 600 --mode train --steps 40 --warmup 4
 stage 4_train_10000_per_rank 600 --mode train --batch $((10000 * N)) --steps 40 --warmup 4
-stage 5_infer 1200 --steps 20 --warmup 3 --no-cpu
+stage 5_infer 1200 --steps 20 --warmup 3 --full --no-cpu
 python - $OUT <<'PY'
 import glob, json, os, sys
 o = sys.argv[1]

@@ -25,7 +25,7 @@ python tools/gpu_infer_stage_ladder.py full > $OUT/infer_stage_ladder_full.txt 2
 python tools/gpu_infer_stage_ladder.py slim > $OUT/infer_stage_ladder_slim.txt 2>> $OUT/bench.err
 SIZES="320 640 1250 2500 5000 8000 10000 12288 16384 32768" STEPS=30 bash tools/gpu_step_size_sweep.sh $(basename $OUT)_steps > /dev/null 2>&1
 cp gpurun_out/$(basename $OUT)_steps/step_sizes.txt $OUT/step_size_ladder.txt 2>/dev/null
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 python bench.py --arch slim --no-cpu > $OUT/bench_slim.json 2>> $OUT/bench.err
 for b in 1250 10000; do python bench.py --mode train --batch $b --steps 50 --warmup 5 >> $OUT/bench_train.jsonl 2>> $OUT/bench.err; done
 python bench.py --mode train --batch 10000 --steps 50 --warmup 5 --arch slim >> $OUT/bench_train.jsonl 2>> $OUT/bench.err
