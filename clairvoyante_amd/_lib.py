@@ -53,6 +53,8 @@ _SIGS = {
     "cv_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                ctypes.c_float, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64,
                                ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]),
+    "cv_set_dropout5": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float]),
+    "cv_get_dropout5": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
     "cv_grad_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
                                       ctypes.POINTER(ctypes.c_int64)]),
     "cv_grad_bucket_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),

@@ -241,6 +241,21 @@ extern "C" int cv_params_changed(cv_model *m)
     return 0;
 }
 
+extern "C" int cv_set_dropout5(cv_model *m, float rate)
+{
+    if (!m) { cv_set_error("cv_set_dropout5: null model"); return 1; }
+    if (!(rate >= 0.0f && rate < 1.0f)) { cv_set_error("cv_set_dropout5: rate %g not in [0,1)", (double)rate); return 1; }
+    m->drop5 = rate;
+    return 0;
+}
+
+extern "C" int cv_get_dropout5(const cv_model *m, float *rate)
+{
+    if (!m || !rate) { cv_set_error("cv_get_dropout5: null argument"); return 1; }
+    *rate = m->drop5;
+    return 0;
+}
+
 extern "C" int cv_set_option(cv_model *m, const char *key, int64_t value)
 {
     if (!m || !key) { cv_set_error("cv_set_option: null argument"); return 1; }
@@ -336,7 +351,20 @@ extern "C" int cv_get_activation(cv_model *m, int layer, float *dst_dev, int64_t
         CV_HIP(hipMemcpyAsync(dst_dev, src, sizeof(float) * (size_t)npos * m->arch.cout[l] * n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return 0;
     }
-    if (layer < 1 || layer > 7) { cv_set_error("cv_get_activation: layer %d not in 1..7, 11..13, 21..23", layer); return 1; }
+    if (layer < 1 || layer > 9) { cv_set_error("cv_get_activation: layer %d not in 1..9, 11..13, 21..23", layer); return 1; }
+    if (layer >= 8) {        // fc5's: 8 = keep mask scaled by a, 9 = dropout output (training passes with cv_set_dropout5 > 0)
+        if (n <= 0 || n > m->last_tr_n || !m->last_tr_d5) {
+            cv_set_error("cv_get_activation: layer %d is not there for n=%lld (the last training slice held %lld candidates%s)",
+                         layer, (long long)n, (long long)m->last_tr_n,
+                         m->last_tr_d5 ? "" : " and ran no fc5 dropout");
+            return 1;
+        }
+        CV_HIP(hipSetDevice(m->device));
+        const float *src = layer == 8 ? m->last_tr_mask5 : m->last_tr_d5;
+        if (m->last_tr_tile) return cv_tm_to_natural(src, m->sh.nb5, m->sh.nb5 * 16, m->arch.fc5, 1, n, dst_dev, (hipStream_t)stream);
+        CV_HIP(hipMemcpyAsync(dst_dev, src, sizeof(float) * (size_t)m->arch.fc5 * n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return 0;
+    }
     if (layer >= 6) {        // training-pass tensors: 6 = keep mask scaled by a (0 where dropped), 7 = dropout output
         if (n <= 0 || n > m->last_tr_n || !m->last_tr_d4) {
             cv_set_error("cv_get_activation: n=%lld but the last training slice held %lld candidates", (long long)n,

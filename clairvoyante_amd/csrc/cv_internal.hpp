@@ -140,6 +140,9 @@ struct cv_model {
                          // kernel variants of the training step (default 400; 0 = never)
     // fc4 dropout output / keep mask (a*keep) of the LAST training slice, for cv_get_activation 6 / 7
     const float *last_tr_d4, *last_tr_mask;
+    // the same for fc5 (cv_get_activation 8 / 9); nullptr after a pass that ran no fc5 dropout
+    const float *last_tr_d5, *last_tr_mask5;
+    float drop5;         // cv_set_dropout5: alpha-dropout rate on fc5 of the cv_grad / cv_grad_async passes (default 0)
     const float *last_tr_pool[3], *last_tr_gpre[3];   // cv_get_activation 11..13 / 21..23: maps of the last training slice (nullptr: not materialised)
     int64_t last_tr_n;
     // candidates the map pointers above hold: the slice's count after a single-slice pass, 0 after a pass of several slices
@@ -147,7 +150,8 @@ struct cv_model {
     int64_t last_tr_map_n;
     int last_tr_tile;    // 1: tile-major buffers, 0: natural [n, fc4]
     // option keep_activations + a step of several slices: the two maps of EVERY slice, copied here slice after slice
-    // (mask first, dropout output behind it), so that cv_get_activation 6 / 7 covers the whole batch
+    // (mask first, dropout output behind it; then fc5's two when the step ran its dropout), so that cv_get_activation
+    // 6 / 7 (8 / 9) covers the whole batch
     float *tr_keep; size_t tr_keep_floats;
     int tr_accumulate;   // the weight-gradient second passes ADD to the gradient (1) or store 0 + sum (0: first slice of a step)
     // optional per-kernel timing (option "profile")
@@ -224,13 +228,17 @@ int cv_tile_train_convs(cv_model *m, const float *x, int64_t n, float *p1, float
 // part: scratch of CV_DENSE_KSPLIT * groups * nb4 fragments, or NULL = always the single ascending-k chain
 // drop / drop_done (fc4 of a training pass): where the kernel set allows it the alpha-dropout is applied by the layer's
 // last kernel (*drop_done = true); otherwise the caller runs cv_dropout_tm
-struct cv_train_dropout { float *d4, *amask; float rate; uint64_t seed, step; int64_t cand0; };
+// fc5's alpha-dropout draws from the stream of fc4's with bit 39 of the counter set: a counter cand * units + unit stays
+// below 2^39 and the step sits at bit 40 and above, so no fc5 counter equals an fc4 counter of any step
+#define CV_DROP5_SALT (1ull << 39)
+// d5 / amask5 / rate5: fc5's alpha-dropout (rate5 > 0: the training tail applies it and the heads read d5)
+struct cv_train_dropout { float *d4, *amask; float rate; uint64_t seed, step; int64_t cand0; float *d5, *amask5; float rate5; };
 int cv_tile_dense_fwd(cv_model *m, int layer, const float *in_tm, float *out_tm, int64_t n, hipStream_t st,
                       float *part = nullptr, const cv_train_dropout *drop = nullptr, bool *drop_done = nullptr);
 int cv_tile_train_tail(cv_model *m, const float *p3_tm, float *h4_tm, float *h5_tm, const float *y, int64_t n, int want_grad,
                        float *g16, float *g5pre_tm, float *part, const cv_train_dropout *drop, hipStream_t st, bool *done);
 int cv_tile_train_fc5_heads(cv_model *m, float *d4_tm, float *h5_tm, const float *y, int64_t n, int want_grad, float *g16,
-                            float *g5pre_tm, hipStream_t st, bool *done);
+                            float *g5pre_tm, hipStream_t st, bool *done, const cv_train_dropout *drop = nullptr);
 int cv_tile_fc5_dgrad(cv_model *m, const float *g_tm, float *gin_tm, int64_t n, hipStream_t st, const float *g16,
                       const float *mask_tm, const float *act_tm);
 // act_below (layers without pooling, slim): the layer-below output; the result is then times selu' = its pre-activation gradient
@@ -247,8 +255,10 @@ int cv_tile_conv1_wgrad_unpool(cv_model *m, const float *x, const float *gpool, 
 int cv_wgrad_scratch_reserve(cv_model *m);      // scratch of the weight-gradient kernels at its upper bound
 int cv_tile_heads_wgrad(cv_model *m, const float *d4_tm, const float *h5_tm, const float *g16, int64_t n, hipStream_t st);
 int cv_tile_heads_pre(cv_model *m, const float *d4_tm, const float *h5_tm, int64_t n, float *pre16, hipStream_t st);
+// drop with rate5 > 0: the kernel applies fc5's alpha-dropout to h5_tm on the way in (d5 / amask5 stored), the products
+// read d5 and the fc5-side data gradient is times a*keep before selu'(h5)
 int cv_tile_heads_train(cv_model *m, const float *d4_tm, const float *h5_tm, const float *y, int64_t n, int want_grad,
-                        float *g16, float *g5pre_tm, hipStream_t st);
+                        float *g16, float *g5pre_tm, hipStream_t st, const cv_train_dropout *drop = nullptr);
 int cv_dropout_tm(cv_model *m, const float *h4, float *d4, float *amask, int64_t n, float rate, uint64_t seed,
                   uint64_t step, int64_t cand0, hipStream_t st);
 int cv_tm_to_natural(const float *tm, int KB, int feat_per_pos_padded, int feat_per_pos, int npos,

@@ -1318,8 +1318,11 @@ __global__ __launch_bounds__(256) void heads_pre_tm(const f4 *__restrict__ h4, c
 //   3. the data gradient of the three fc5-side heads, times selu'(fc5 output) -- the fc5 fragments are still in the
 //      registers they were loaded into for step 1 -- straight into the tile-major pre-activation gradient of fc5.
 // The arithmetic per value is that of the three kernels it replaces (same order): same bits.
+// DROP5 (a training pass with fc5's alpha-dropout): each fc5 value is dropped out as it is loaded (dr5: d5 / a*keep
+// stored, candidate dr5.cand0 + 16 g + c); the products read d5, and step 3 multiplies by a*keep -- drawn again from the
+// counter, not kept in registers -- before selu'(h5).
 // ---------------------------------------------------------------------------
-template <int NB5>
+template <int NB5, bool DROP5 = false>
 __global__ __launch_bounds__(256) void heads_train_tm(const f4 *__restrict__ d4, const f4 *__restrict__ h5, int NB4,
                                                        const f4 *__restrict__ wp0, const f4 *__restrict__ wp1,
                                                        const float *__restrict__ bb, const float *__restrict__ bz,
@@ -1328,7 +1331,7 @@ __global__ __launch_bounds__(256) void heads_train_tm(const f4 *__restrict__ d4,
                                                        const float *__restrict__ wl, int K5, const float *__restrict__ y,
                                                        int64_t n, int want_grad, float *__restrict__ g16,
                                                        f4 *__restrict__ g5pre_tm, double *__restrict__ loss_rows, int G,
-                                                       const float *__restrict__ w12)
+                                                       const float *__restrict__ w12, cv_dropout_args dr5)
 {
     __shared__ float sh[4][16][17];
     __shared__ double part[4][4];          // [wave][head]: the four loss sums of a wave's 16 candidates
@@ -1360,8 +1363,25 @@ __global__ __launch_bounds__(256) void heads_train_tm(const f4 *__restrict__ d4,
     for (int kb = 0; kb < NB5; kb++) {
         H5[kb] = p5[(size_t)kb * 64];
         const f4 A = wp1[(size_t)kb * 64 + lane];
+        if constexpr (DROP5) {
+            f4 d, mk;
 #pragma unroll
-        for (int s = 0; s < 4; s++) a1 = mfma4(A[s], H5[kb][s], a1);
+            for (int s = 0; s < 4; s++) {
+                float x = H5[kb][s], k;
+                dropout_value(x, k, 16 * kb + 4 * s + q, dr5.nunits, dr5.cand0 + (int64_t)gc * 16 + c, dr5.rate, dr5.seed, dr5.step,
+                              CV_DROP5_SALT);
+                d[s] = x; mk[s] = k;
+            }
+            if (live) {
+                reinterpret_cast<f4 *>(dr5.d4)[((size_t)g * NB5 + kb) * 64 + lane] = d;
+                reinterpret_cast<f4 *>(dr5.amask)[((size_t)g * NB5 + kb) * 64 + lane] = mk;
+            }
+#pragma unroll
+            for (int s = 0; s < 4; s++) a1 = mfma4(A[s], d[s], a1);
+        } else {
+#pragma unroll
+            for (int s = 0; s < 4; s++) a1 = mfma4(A[s], H5[kb][s], a1);
+        }
     }
     float (*S)[17] = sh[wave];
     // rows of the second tile: q 0 = zygosity (2), q 1 = type (4), q 2 = length 0..3, q 3 = length 4..5
@@ -1436,6 +1456,11 @@ __global__ __launch_bounds__(256) void heads_train_tm(const f4 *__restrict__ d4,
 #pragma unroll
                 for (int jj = 0; jj < 12; jj++) acc = __builtin_fmaf(gi[4 + jj], wk[jj], acc);
             }
+            if constexpr (DROP5) {
+                float x = 0.0f, mk;
+                dropout_value(x, mk, k, dr5.nunits, dr5.cand0 + (int64_t)g * 16 + c, dr5.rate, dr5.seed, dr5.step, CV_DROP5_SALT);
+                acc *= mk;
+            }
             o[s] = acc * cv_selu_grad_from_out(H5[kb][s]);
         }
         g5pre_tm[((size_t)g * NB5 + kb) * 64 + lane] = o;
@@ -1464,7 +1489,9 @@ __global__ __launch_bounds__(256) void heads_train_tm(const f4 *__restrict__ d4,
 // (four-wave form: three workgroups per CU -- 168 registers, 40 dwords of them spilled -- so that the 625 workgroups of
 // train.py's batch are ONE round on 256 CUs instead of two: 52.7 -> 40.6 us, the step 2.060 -> 2.054 ms, 12 288: 2.574 ->
 // 2.559; profiles/r06/train_tail_occupancy_ab.txt)
-template <int NB4, int NB5, int NWV, bool PART>
+// DROP5 (fc5's alpha-dropout, dr5): step 2 drops the fc5 output out on its store -- h5 and d5 / a*keep stored, d5 to LDS
+// for the heads -- and step 4 multiplies by a*keep, drawn again from the counter, before selu'(h5).
+template <int NB4, int NB5, int NWV, bool PART, bool DROP5 = false>
 __global__ __launch_bounds__(NWV * 64, (PART ? 1 : 3)) void train_tail_tm(const f4 *__restrict__ part, int KS, int G, const float *__restrict__ bias4,
                                                       int nout4, f4 *__restrict__ h4_out, cv_dropout_args dr,
                                                       const f4 *__restrict__ w5s, const float *__restrict__ bias5, int nout5,
@@ -1475,7 +1502,8 @@ __global__ __launch_bounds__(NWV * 64, (PART ? 1 : 3)) void train_tail_tm(const 
                                                       const float *__restrict__ wt, const float *__restrict__ wl,
                                                       const float *__restrict__ y, int64_t n, int want_grad,
                                                       float *__restrict__ g16, f4 *__restrict__ g5pre_tm,
-                                                      double *__restrict__ loss_rows, const float *__restrict__ w12)
+                                                      double *__restrict__ loss_rows, const float *__restrict__ w12,
+                                                      cv_dropout_args dr5)
 {
     constexpr int NBW = 4, D = 7;                 // fc5 slab width and operand ring depth of dense_small<4, 7>
     static_assert(NB4 % D == 0 && NB5 <= 3 * NBW, "three slabs of four fc5 tiles, 21 k fragments in rings of 7");
@@ -1618,7 +1646,21 @@ __global__ __launch_bounds__(NWV * 64, (PART ? 1 : 3)) void train_tail_tm(const 
             if (ob >= NB5) break;
             H5[j] = selu4(acc[j] + load_bias4(bias5, ob, q, nout5));
             h5_out[((size_t)g * NB5 + ob) * 64 + lane] = H5[j];
-            sh5[ob][lane] = H5[j];
+            if constexpr (DROP5) {
+                f4 d, mk;
+#pragma unroll
+                for (int s4 = 0; s4 < 4; s4++) {
+                    float x = H5[j][s4], k;
+                    dropout_value(x, k, 16 * ob + 4 * s4 + q, dr5.nunits, dr5.cand0 + (int64_t)g * 16 + c, dr5.rate, dr5.seed,
+                                  dr5.step, CV_DROP5_SALT);
+                    d[s4] = x; mk[s4] = k;
+                }
+                reinterpret_cast<f4 *>(dr5.d4)[((size_t)g * NB5 + ob) * 64 + lane] = d;
+                reinterpret_cast<f4 *>(dr5.amask)[((size_t)g * NB5 + ob) * 64 + lane] = mk;
+                sh5[ob][lane] = d;
+            } else {
+                sh5[ob][lane] = H5[j];
+            }
         }
     } else if (wave == 3) {
         f4 a0 = zero;
@@ -1712,6 +1754,11 @@ __global__ __launch_bounds__(NWV * 64, (PART ? 1 : 3)) void train_tail_tm(const 
                 const float wk[12] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3], w2[0], w2[1], w2[2], w2[3]};
 #pragma unroll
                 for (int jj = 0; jj < 12; jj++) acc = __builtin_fmaf(gi[4 + jj], wk[jj], acc);
+            }
+            if constexpr (DROP5) {
+                float x = 0.0f, mk;
+                dropout_value(x, mk, k, dr5.nunits, dr5.cand0 + (int64_t)g * 16 + c, dr5.rate, dr5.seed, dr5.step, CV_DROP5_SALT);
+                acc *= mk;
             }
             o[s4] = acc * cv_selu_grad_from_out(H5[j][s4]);
         }

@@ -1189,6 +1189,16 @@ int cv_tile_dense_fwd(cv_model *m, int layer, const float *in_tm, float *out_tm,
     return launch_dense<2, 4>(in_tm, s.nb4, m->wp_fc5, P + o[9], a.fc5, out_tm, G, st);
 }
 
+// fc5's alpha-dropout of a training pass as kernel arguments; rate 0 (no dropout, or none asked for) when drop is null
+static cv_dropout_args drop5_args(const cv_model *m, const cv_train_dropout *drop)
+{
+    cv_dropout_args dr = cv_dropout_args();
+    if (!drop || !(drop->rate5 > 0.0f)) return dr;
+    dr.d4 = drop->d5; dr.amask = drop->amask5; dr.nunits = m->arch.fc5; dr.rate = drop->rate5; dr.seed = drop->seed;
+    dr.step = drop->step; dr.cand0 = drop->cand0;
+    return dr;
+}
+
 // Tiny batches of the full topology with the k-split fc4 forward: fc4's eight k ranges, then ONE kernel for their sum,
 // bias, SELU, alpha-dropout, fc5, the heads, the losses, the head gradients and the fc5-side data gradient
 // (train_tail_tm).  *done = false: not this regime (or dbg2 = 5) -- the caller runs the layers one by one.
@@ -1216,10 +1226,13 @@ int cv_tile_train_tail(cv_model *m, const float *p3_tm, float *h4_tm, float *h5_
     cv_dropout_args dr = cv_dropout_args();
     dr.d4 = drop->d4; dr.amask = drop->amask; dr.nunits = a.fc4; dr.rate = drop->rate; dr.seed = drop->seed;
     dr.step = drop->step; dr.cand0 = drop->cand0;
-    train_tail_tm<21, 11, 8, true><<<G, 512, 0, st>>>((const f4 *)part, KR, G, P + o[7], a.fc4, (f4 *)h4_tm, dr, (const f4 *)m->wps3_fc5,
-                                             P + o[9], a.fc5, (f4 *)h5_tm, (const f4 *)m->wp_heads0, (const f4 *)m->wp_heads1, P + o[11],
-                                             P + o[13], P + o[15], P + o[17], P + o[12], P + o[14], P + o[16], y, n, want_grad, g16,
-                                             (f4 *)g5pre_tm, rows, m->wp_heads12);
+    const cv_dropout_args dr5 = drop5_args(m, drop);
+    // (fc5's dropout is its own instantiation: a step without it runs the kernel it ran before)
+    auto tail = dr5.rate > 0.0f ? train_tail_tm<21, 11, 8, true, true> : train_tail_tm<21, 11, 8, true>;
+    tail<<<G, 512, 0, st>>>((const f4 *)part, KR, G, P + o[7], a.fc4, (f4 *)h4_tm, dr, (const f4 *)m->wps3_fc5,
+                            P + o[9], a.fc5, (f4 *)h5_tm, (const f4 *)m->wp_heads0, (const f4 *)m->wp_heads1, P + o[11],
+                            P + o[13], P + o[15], P + o[17], P + o[12], P + o[14], P + o[16], y, n, want_grad, g16,
+                            (f4 *)g5pre_tm, rows, m->wp_heads12, dr5);
     CV_HIP(hipGetLastError());
     *done = true;
     return 0;
@@ -1229,7 +1242,7 @@ int cv_tile_train_tail(cv_model *m, const float *p3_tm, float *h4_tm, float *h5_
 // the fc5-side data gradient in one kernel behind fc4's own (which has stored the dropped-out output d4_tm) -- the same
 // kernel as the tiny-batch tail without its first step, four waves per group.  *done = false: not this regime.
 int cv_tile_train_fc5_heads(cv_model *m, float *d4_tm, float *h5_tm, const float *y, int64_t n, int want_grad, float *g16,
-                            float *g5pre_tm, hipStream_t st, bool *done)
+                            float *g5pre_tm, hipStream_t st, bool *done, const cv_train_dropout *drop)
 {
     *done = false;
     const cv_shapes &s = m->sh; const cv_arch &a = m->arch;
@@ -1242,10 +1255,12 @@ int cv_tile_train_fc5_heads(cv_model *m, float *d4_tm, float *h5_tm, const float
     m->loss_rows_used += G;
     cv_dropout_args dr = cv_dropout_args();
     dr.d4 = d4_tm;
-    train_tail_tm<21, 11, 4, false><<<G, 256, 0, st>>>(nullptr, 1, G, P + o[7], a.fc4, nullptr, dr, (const f4 *)m->wps3_fc5,
-                                                       P + o[9], a.fc5, (f4 *)h5_tm, (const f4 *)m->wp_heads0, (const f4 *)m->wp_heads1,
-                                                       P + o[11], P + o[13], P + o[15], P + o[17], P + o[12], P + o[14], P + o[16], y, n,
-                                                       want_grad, g16, (f4 *)g5pre_tm, rows, m->wp_heads12);
+    const cv_dropout_args dr5 = drop5_args(m, drop);
+    auto tail = dr5.rate > 0.0f ? train_tail_tm<21, 11, 4, false, true> : train_tail_tm<21, 11, 4, false>;
+    tail<<<G, 256, 0, st>>>(nullptr, 1, G, P + o[7], a.fc4, nullptr, dr, (const f4 *)m->wps3_fc5,
+                            P + o[9], a.fc5, (f4 *)h5_tm, (const f4 *)m->wp_heads0, (const f4 *)m->wp_heads1,
+                            P + o[11], P + o[13], P + o[15], P + o[17], P + o[12], P + o[14], P + o[16], y, n,
+                            want_grad, g16, (f4 *)g5pre_tm, rows, m->wp_heads12, dr5);
     CV_HIP(hipGetLastError());
     *done = true;
     return 0;
@@ -1362,15 +1377,17 @@ int cv_tile_conv_dgrad(cv_model *m, int layer, const float *g_tm, float *gin_tm,
 // heads of the training pass in one launch: products, losses (added to loss[0..3]), gradients w.r.t. the 16
 // pre-activations (g16 [n][16], when want_grad) and the fc5-side data gradient times selu'(fc5) (g5pre_tm, when not null)
 int cv_tile_heads_train(cv_model *m, const float *d4_tm, const float *h5_tm, const float *y, int64_t n, int want_grad,
-                        float *g16, float *g5pre_tm, hipStream_t st)
+                        float *g16, float *g5pre_tm, hipStream_t st, const cv_train_dropout *drop)
 {
     const cv_shapes &s = m->sh; const cv_arch &a = m->arch;
     const float *P = m->params; const int64_t *o = m->poff;
     const int G = (int)((n + 15) / 16);
     if (G <= 0) return 0;
-#define CV_HT(NB5) heads_train_tm<NB5><<<nblk(G, 4), 256, 0, st>>>((const f4 *)d4_tm, (const f4 *)h5_tm, s.nb4, (const f4 *)m->wp_heads0, \
+    const cv_dropout_args dr5 = drop5_args(m, drop);
+#define CV_HT(NB5) (dr5.rate > 0.0f ? heads_train_tm<NB5, true> : heads_train_tm<NB5>)<<<nblk(G, 4), 256, 0, st>>>( \
+        (const f4 *)d4_tm, (const f4 *)h5_tm, s.nb4, (const f4 *)m->wp_heads0, \
         (const f4 *)m->wp_heads1, P + o[11], P + o[13], P + o[15], P + o[17], P + o[12], P + o[14], P + o[16], a.fc5, y, n, want_grad, \
-        g16, (f4 *)g5pre_tm, rows, G, m->wp_heads12)
+        g16, (f4 *)g5pre_tm, rows, G, m->wp_heads12, dr5)
     // the block sums of this slice: rows [loss_rows_used, + blocks) of the step's row buffer (cv_train.hip t_loss_finish)
     const int64_t blocks = nblk(G, 4);
     if (m->loss_rows_used + blocks > m->loss_rows_cap) { cv_set_error("heads_train_tm: loss row buffer too small (internal)"); return 1; }

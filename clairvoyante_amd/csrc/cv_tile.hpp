@@ -127,11 +127,11 @@ __device__ __forceinline__ f4 load_bias4(const float *__restrict__ bias, int ob,
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // alpha-dropout of one fc4 value (selu.py:34-69): d4 = a*(h4*keep + alpha'*(1-keep)) + b; mk = a*keep is kept for the
-// backward pass.  Counter-based stream of (seed, step, candidate, unit).
+// backward pass.  Counter-based stream of (seed, step, candidate, unit).  salt: CV_DROP5_SALT for fc5's stream, 0 for fc4's.
 struct cv_dropout_args { float *d4, *amask; int nunits; float rate; uint64_t seed, step; int64_t cand0; };
 
 __device__ __forceinline__ void dropout_value(float &v, float &mk, int unit, int nunits, int64_t cand, float rate, uint64_t seed,
-                                              uint64_t step)
+                                              uint64_t step, uint64_t salt = 0)
 {
     mk = 1.0f;
     if (unit >= nunits) { v = 0.0f; mk = 0.0f; }
@@ -140,7 +140,7 @@ __device__ __forceinline__ void dropout_value(float &v, float &mk, int unit, int
         float q = 1.0f - rate;
         float a = sqrtf(1.0f / (q * ((1.0f - q) * (ap * ap) + 1.0f)));
         float b = 0.0f - a * ((1.0f - q) * ap);
-        uint64_t ctr = (seed * 0x9E3779B97F4A7C15ull) ^ (step << 40) ^ (uint64_t)(cand * nunits + unit);
+        uint64_t ctr = (seed * 0x9E3779B97F4A7C15ull) ^ (step << 40) ^ (uint64_t)(cand * nunits + unit) ^ salt;
         ctr += 0x9E3779B97F4A7C15ull;
         ctr = (ctr ^ (ctr >> 30)) * 0xBF58476D1CE4E5B9ull;
         ctr = (ctr ^ (ctr >> 27)) * 0x94D2049BB133111Bull;

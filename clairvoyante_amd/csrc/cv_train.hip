@@ -5,9 +5,9 @@
 // (/root/reference/clairvoyante/clairvoyante_v3.py:183-227):
 //   loss (v3.py:140-151)  = sum (sigmoid - y)^2 + sum -y*log_softmax(logits) x3
 //                           + lambda * sum_{kernels} sum(w^2)/2      -- SUMS over the batch
-//   alpha-dropout on fc4 (selu.py:34-69): keep mask from a counter-based hash of
-//   (seed, step, candidate, unit) -- the reference's stream is unseeded TF state, so
-//   only the distribution can match.
+//   alpha-dropout on fc4 and fc5 (selu.py:34-69, v3.py:117-121): keep mask from a counter-based
+//   hash of (seed, step, candidate, unit), fc5's in a domain of its own (CV_DROP5_SALT) -- the
+//   reference's stream is unseeded TF state, so only the distribution can match.
 // Forward pass, data gradients and weight gradients all run on the MFMA tile kernels
 // (cv_kernels_mfma.hip: conv_tm MODE 1/2, dense_tm EPI 1, wgrad_*_cm); this file holds the
 // element-wise steps on tile-major buffers (SELU', max-pool routing, dropout, loss, head data
@@ -92,9 +92,9 @@ __global__ void t_dense_pre(const float *__restrict__ x, const float *__restrict
     y[t] = acc + bias[j];
 }
 
-// d4 = alpha-dropout(selu(fc4pre)); mask stored as a*keep (0 when dropped)
+// d4 = alpha-dropout(selu(fc4pre)); mask stored as a*keep (0 when dropped).  fc5's (d5) with salt = CV_DROP5_SALT.
 __global__ void t_fc4_act(const float *__restrict__ pre, float *__restrict__ d4, float *__restrict__ amask,
-                          int64_t n, int N, float rate, uint64_t seed, uint64_t step, int64_t cand0)
+                          int64_t n, int N, float rate, uint64_t seed, uint64_t step, int64_t cand0, uint64_t salt)
 {
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n * N) return;
@@ -104,7 +104,7 @@ __global__ void t_fc4_act(const float *__restrict__ pre, float *__restrict__ d4,
         float q = 1.0f - rate;
         float a = sqrtf(1.0f / (q * ((1.0f - q) * (ap * ap) + 1.0f)));
         float b = 0.0f - a * ((1.0f - q) * ap);
-        uint64_t ctr = (seed * 0x9E3779B97F4A7C15ull) ^ (step << 40) ^ (uint64_t)(cand0 * N + t);
+        uint64_t ctr = (seed * 0x9E3779B97F4A7C15ull) ^ (step << 40) ^ (uint64_t)(cand0 * N + t) ^ salt;
         float u = (float)(hash_u32(ctr) >> 8) * (1.0f / 16777216.0f);   // [0,1)
         float keep = floorf(q + u);                                     // selu.py:53-56
         v = a * (v * keep + ap * (1.0f - keep)) + b;
@@ -530,7 +530,8 @@ struct slab {
 
 }  // namespace
 
-static size_t train_floats_per_cand(const cv_model *m)
+// drop5: the step runs fc5's alpha-dropout -- two more fc5 maps (d5, a*keep)
+static size_t train_floats_per_cand(const cv_model *m, bool drop5)
 {
     const cv_shapes &s = m->sh; const cv_arch &a = m->arch;
     size_t f = 0;
@@ -543,12 +544,13 @@ static size_t train_floats_per_cand(const cv_model *m)
     // padded channel counts, plus the dense TM buffers
     for (int l = 0; l < 3; l++) f += (size_t)(2 * s.hc[l] + 2 * s.hp[l]) * 4 * s.ntile[l] * 16;
     f += (6 + CV_DENSE_KSPLIT) * (size_t)s.nb4 * 16 + 2 * (size_t)s.nb5 * 16;
+    if (drop5) f += 2 * (size_t)s.nb5 * 16;      // (nb5 * 16 >= fc5: the plain path's rows fit as well)
     return f + 64 * 80;
 }
 
 // forward (+ optional backward) of one slice of the batch: all-plain path
 static int train_slice_plain(cv_model *m, const float *x, const float *y, int64_t n, int64_t cand0, bool backward,
-                       float drop4, uint64_t seed, uint64_t step, hipStream_t st)
+                       float drop4, float drop5, uint64_t seed, uint64_t step, hipStream_t st)
 {
     const cv_shapes &s = m->sh; const cv_arch &a = m->arch;
     const float *P = m->params; float *G = m->grads; const int64_t *o = m->poff;
@@ -565,7 +567,10 @@ static int train_slice_plain(cv_model *m, const float *x, const float *y, int64_
     float *fc5pre = sb.take((size_t)n * a.fc5), *h5 = sb.take((size_t)n * a.fc5);
     float *gh5 = sb.take((size_t)n * a.fc5), *gfc5pre = sb.take((size_t)n * a.fc5);
     float *ghpre = sb.take((size_t)n * 16);
-    if (!ghpre) { cv_set_error("training workspace too small"); return 1; }
+    // fc5's alpha-dropout (backward passes with drop5 > 0 only): its output d5 and a*keep
+    const bool on5 = backward && drop5 > 0.0f;
+    float *d5 = on5 ? sb.take((size_t)n * a.fc5) : nullptr, *amask5 = on5 ? sb.take((size_t)n * a.fc5) : nullptr;
+    if (!ghpre || (on5 && !amask5)) { cv_set_error("training workspace too small"); return 1; }
     // ---- forward
     const float *in = x;
     for (int l = 0; l < 3; l++) {
@@ -577,29 +582,33 @@ static int train_slice_plain(cv_model *m, const float *x, const float *y, int64_
     }
     t_dense_pre<<<nblk(n * a.fc4, 256), 256, 0, st>>>(pool[2], P + o[6], P + o[7], fc4pre, n, s.flat, a.fc4);
     t_fc4_act<<<nblk(n * a.fc4, 256), 256, 0, st>>>(fc4pre, d4, amask, n, a.fc4, backward ? drop4 : 0.0f, seed,
-                                                    step, cand0);
+                                                    step, cand0, 0);
     m->last_tr_d4 = d4; m->last_tr_mask = amask; m->last_tr_n = n; m->last_tr_map_n = n; m->last_tr_tile = 0;
+    m->last_tr_d5 = d5; m->last_tr_mask5 = amask5;
     for (int l = 0; l < 3; l++) { m->last_tr_pool[l] = pool[l]; m->last_tr_gpre[l] = backward ? gpre[l] : nullptr; }
     t_dense_pre<<<nblk(n * a.fc5, 256), 256, 0, st>>>(d4, P + o[8], P + o[9], fc5pre, n, a.fc4, a.fc5);
     t_selu_act<<<nblk(n * a.fc5, 256), 256, 0, st>>>(fc5pre, h5, n * a.fc5);
-    t_heads<<<nblk(n, 16), 256, 0, st>>>(d4, h5, a.fc4, a.fc5, P + o[10], P + o[11], P + o[12], P + o[13],
+    if (on5)
+        t_fc4_act<<<nblk(n * a.fc5, 256), 256, 0, st>>>(fc5pre, d5, amask5, n, a.fc5, drop5, seed, step, cand0, CV_DROP5_SALT);
+    const float *o5 = on5 ? d5 : h5;          // what the heads read: fc5's output after its dropout
+    t_heads<<<nblk(n, 16), 256, 0, st>>>(d4, o5, a.fc4, a.fc5, P + o[10], P + o[11], P + o[12], P + o[13],
                                          P + o[14], P + o[15], P + o[16], P + o[17], y, n,
                                          backward ? ghpre : nullptr, m->loss_dev);
     CV_HIP(hipGetLastError());
     if (!backward) return 0;
     // ---- backward
     const int NS = 128;     // candidate-range slices of the weight-gradient reductions (short serial loops, few atomics)
-    // heads: columns of ghpre: 0..3 base (input d4), 4..5 / 6..9 / 10..15 (input h5)
+    // heads: columns of ghpre: 0..3 base (input d4), 4..5 / 6..9 / 10..15 (input h5, or d5 behind fc5's dropout)
     b_dense_wgrad<<<dim3(nblk((a.fc4 + 1) * 4, 256), NS), 256, 0, st>>>(d4, a.fc4, ghpre + 0, 16, n, a.fc4, 4, G + o[10], G + o[11]);
-    b_dense_wgrad<<<dim3(nblk((a.fc5 + 1) * 2, 256), NS), 256, 0, st>>>(h5, a.fc5, ghpre + 4, 16, n, a.fc5, 2, G + o[12], G + o[13]);
-    b_dense_wgrad<<<dim3(nblk((a.fc5 + 1) * 4, 256), NS), 256, 0, st>>>(h5, a.fc5, ghpre + 6, 16, n, a.fc5, 4, G + o[14], G + o[15]);
-    b_dense_wgrad<<<dim3(nblk((a.fc5 + 1) * 6, 256), NS), 256, 0, st>>>(h5, a.fc5, ghpre + 10, 16, n, a.fc5, 6, G + o[16], G + o[17]);
+    b_dense_wgrad<<<dim3(nblk((a.fc5 + 1) * 2, 256), NS), 256, 0, st>>>(o5, a.fc5, ghpre + 4, 16, n, a.fc5, 2, G + o[12], G + o[13]);
+    b_dense_wgrad<<<dim3(nblk((a.fc5 + 1) * 4, 256), NS), 256, 0, st>>>(o5, a.fc5, ghpre + 6, 16, n, a.fc5, 4, G + o[14], G + o[15]);
+    b_dense_wgrad<<<dim3(nblk((a.fc5 + 1) * 6, 256), NS), 256, 0, st>>>(o5, a.fc5, ghpre + 10, 16, n, a.fc5, 6, G + o[16], G + o[17]);
     b_dense_dgrad<<<nblk(n * a.fc4, 256), 256, 0, st>>>(ghpre + 0, 16, P + o[10], n, a.fc4, 4, gd4, 0);
     b_dense_dgrad<<<nblk(n * a.fc5, 256), 256, 0, st>>>(ghpre + 4, 16, P + o[12], n, a.fc5, 2, gh5, 0);
     b_dense_dgrad<<<nblk(n * a.fc5, 256), 256, 0, st>>>(ghpre + 6, 16, P + o[14], n, a.fc5, 4, gh5, 1);
     b_dense_dgrad<<<nblk(n * a.fc5, 256), 256, 0, st>>>(ghpre + 10, 16, P + o[16], n, a.fc5, 6, gh5, 1);
-    // fc5
-    b_selu<<<nblk(n * a.fc5, 256), 256, 0, st>>>(gh5, fc5pre, nullptr, gfc5pre, n * a.fc5);
+    // (dropout5 +) selu'
+    b_selu<<<nblk(n * a.fc5, 256), 256, 0, st>>>(gh5, fc5pre, amask5, gfc5pre, n * a.fc5);
     b_dense_wgrad<<<dim3(nblk((int64_t)(a.fc4 + 1) * a.fc5, 256), NS), 256, 0, st>>>(d4, a.fc4, gfc5pre, a.fc5, n, a.fc4, a.fc5, G + o[8], G + o[9]);
     b_dense_dgrad<<<nblk(n * a.fc4, 256), 256, 0, st>>>(gfc5pre, a.fc5, P + o[8], n, a.fc4, a.fc5, gd4, 1);
     // dropout4 + selu'
@@ -715,7 +724,7 @@ __global__ __launch_bounds__(256) void t_loss_header(double *__restrict__ loss, 
 // behind the heads kernel -- it needs the heads' block sums and the L2 sums (that stream carries t_l2), nothing of the
 // backward pass -- instead of at the tail of the step on st (8 us + a launch off the critical path).
 static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t n, int64_t cand0, bool backward,
-                            float drop4, uint64_t seed, uint64_t step, hipStream_t st, hipStream_t sw,
+                            float drop4, float drop5, uint64_t seed, uint64_t step, hipStream_t st, hipStream_t sw,
                             hipEvent_t dense_ready, const tr_header *hdr_now, const tr_defer *defer,
                             bool *hdr_launched)
 {
@@ -752,9 +761,12 @@ static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t
         if (cv_tile_train_convs(m, x, n, tp[0], ta[0], tp[1], ta[1], tp[2], ta[2], st)) return 1;
     }
     if (pack_wait) CV_HIP(hipStreamWaitEvent(st, m->tr_pack_done, 0));
-    const cv_train_dropout drop{td4, tmask, backward ? drop4 : 0.0f, seed, step, cand0};
     float *tg5pre = backward ? sb.take(np * f5u) : nullptr;
-    if (backward && !tg5pre) { cv_set_error("training workspace too small"); return 1; }
+    // fc5's alpha-dropout (backward passes with drop5 > 0 only): its output d5 and a*keep, tile-major
+    const bool on5 = backward && drop5 > 0.0f;
+    float *td5 = on5 ? sb.take(np * f5u) : nullptr, *tmask5 = on5 ? sb.take(np * f5u) : nullptr;
+    if ((backward && !tg5pre) || (on5 && !tmask5)) { cv_set_error("training workspace too small"); return 1; }
+    const cv_train_dropout drop{td4, tmask, backward ? drop4 : 0.0f, seed, step, cand0, td5, tmask5, on5 ? drop5 : 0.0f};
     // tiny batches (full topology, k-split fc4): everything behind fc4's k ranges -- their sum, dropout, fc5, the heads,
     // losses, head gradients, fc5-side data gradient -- is one kernel
     bool tail_done = false;
@@ -764,14 +776,16 @@ static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t
         if (cv_tile_dense_fwd(m, 4, tp[2], th4, n, st, m->train_ksplit ? kpart : nullptr, &drop, &drop_done)) return 1;
         if (!drop_done && cv_dropout_tm(m, th4, td4, tmask, n, drop.rate, seed, step, cand0, st)) return 1;
         bool fused_fc5 = false;
-        if (Gn > m->tiny_g && cv_tile_train_fc5_heads(m, td4, th5, y, n, backward ? 1 : 0, ghpre, tg5pre, st, &fused_fc5)) return 1;
+        if (Gn > m->tiny_g && cv_tile_train_fc5_heads(m, td4, th5, y, n, backward ? 1 : 0, ghpre, tg5pre, st, &fused_fc5, &drop)) return 1;
         if (!fused_fc5) {
             if (cv_tile_dense_fwd(m, 5, td4, th5, n, st)) return 1;
-            // heads: products, losses, head gradients and the fc5-side data gradient (times selu'(h5)) in one launch
-            if (cv_tile_heads_train(m, td4, th5, y, n, backward ? 1 : 0, ghpre, tg5pre, st)) return 1;
+            // heads: products, losses, head gradients and the fc5-side data gradient (times selu'(h5)) in one launch; fc5's
+            // dropout (on5) on its way in
+            if (cv_tile_heads_train(m, td4, th5, y, n, backward ? 1 : 0, ghpre, tg5pre, st, &drop)) return 1;
         }
     }
     m->last_tr_d4 = td4; m->last_tr_mask = tmask; m->last_tr_n = n; m->last_tr_map_n = n; m->last_tr_tile = 1;
+    m->last_tr_d5 = td5; m->last_tr_mask5 = tmask5;
     for (int l = 0; l < 3; l++) { m->last_tr_pool[l] = tp[l]; m->last_tr_gpre[l] = nullptr; }
     CV_HIP(hipGetLastError());
     if (!backward) return 0;
@@ -825,7 +839,7 @@ static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t
             *hdr_launched = true;
         }
     }
-    if (cv_tile_heads_wgrad(m, td4, th5, ghpre, n, sx)) return 1;
+    if (cv_tile_heads_wgrad(m, td4, on5 ? td5 : th5, ghpre, n, sx)) return 1;
     // fc5 (its pre-activation gradient came out of the heads kernel: the same point of st as the heads' launch site)
     if (f.to_side(1, &sx, true)) return 1;
     if (cv_tile_dense_wgrad(m, 5, td4, tg5pre, n, sx)) return 1;
@@ -889,12 +903,13 @@ static int train_slice_tile(cv_model *m, const float *x, const float *y, int64_t
 }
 
 static int train_slice(cv_model *m, const float *x, const float *y, int64_t n, int64_t cand0, bool backward,
-                       float drop4, uint64_t seed, uint64_t step, hipStream_t st, hipStream_t sw, hipEvent_t dense_ready,
+                       float drop4, float drop5, uint64_t seed, uint64_t step, hipStream_t st, hipStream_t sw, hipEvent_t dense_ready,
                        const tr_header *hdr_now, const tr_defer *defer, bool *hdr_launched)
 {
     if (m->impl == 1 && cv_tile_supported(m))
-        return train_slice_tile(m, x, y, n, cand0, backward, drop4, seed, step, st, sw, dense_ready, hdr_now, defer, hdr_launched);
-    if (train_slice_plain(m, x, y, n, cand0, backward, drop4, seed, step, st)) return 1;
+        return train_slice_tile(m, x, y, n, cand0, backward, drop4, drop5, seed, step, st, sw, dense_ready, hdr_now, defer,
+                                hdr_launched);
+    if (train_slice_plain(m, x, y, n, cand0, backward, drop4, drop5, seed, step, st)) return 1;
     if (dense_ready) CV_HIP(hipEventRecord(dense_ready, st));
     return 0;
 }
@@ -965,14 +980,14 @@ static int launch_l2(cv_model *m, hipStream_t sw, bool tile_path)
     return 0;
 }
 
-static int train_workspace(cv_model *m, int64_t n, int64_t *slice_out)
+static int train_workspace(cv_model *m, int64_t n, bool drop5, int64_t *slice_out)
 {
     // one pass for train.py's batch of 10 000; larger batches go in equal slices of at most 65 536 candidates
     // (the kernels are at their best on thousands of groups, and HBM has room: ~0.4 MB of workspace per candidate)
     const int64_t max_slice = 65536;
     const int64_t nslice = n > 0 ? (n + max_slice - 1) / max_slice : 1;
     const int64_t slice = n > 0 ? ((n + nslice - 1) / nslice + 15) / 16 * 16 : 16;
-    const size_t need = train_floats_per_cand(m) * (size_t)(slice + 16) * sizeof(float);
+    const size_t need = train_floats_per_cand(m, drop5) * (size_t)(slice + 16) * sizeof(float);
     if (m->t_bytes < need) {
         CV_HIP(hipDeviceSynchronize());
         if (m->t_buf) CV_HIP(hipFree(m->t_buf));
@@ -1015,9 +1030,12 @@ static int train_enqueue(cv_model *m, const float *x, const float *y, int64_t n,
     if (n < 0) { cv_set_error("negative batch"); return 1; }
     if (n > 0 && (!x || !y)) { cv_set_error("null buffer"); return 1; }
     if (drop4 < 0.0f || drop4 >= 1.0f) { cv_set_error("dropout rate must be in [0,1)"); return 1; }
+    // fc5's rate (cv_set_dropout5) applies to training passes only; cv_loss runs without it
+    const float drop5 = backward ? m->drop5 : 0.0f;
+    if (!(drop5 >= 0.0f && drop5 < 1.0f)) { cv_set_error("fc5 dropout rate must be in [0,1)"); return 1; }
     CV_HIP(hipSetDevice(m->device));
     int64_t slice = 16;
-    if (train_workspace(m, n, &slice)) return 1;
+    if (train_workspace(m, n, drop5 > 0.0f, &slice)) return 1;
     if (backward && cv_wgrad_scratch_reserve(m)) return 1;
     // the side stream exists for the tile path only (its slices join it back into st before they return); the
     // all-plain path runs everything, the L2 term included, in stream order
@@ -1068,24 +1086,28 @@ static int train_enqueue(cv_model *m, const float *x, const float *y, int64_t n,
     // option keep_activations and several slices: the dropout maps of every slice are kept (cv_get_activation 6 / 7 then
     // covers the whole batch, and the oracle tests can feed a multi-slice step's own keep mask back); one slice: in place
     const size_t keep_per = tile_path ? (size_t)m->sh.nb4 * 16 : (size_t)m->arch.fc4;       // floats per candidate of a map
+    const size_t keep5_per = tile_path ? (size_t)m->sh.nb5 * 16 : (size_t)m->arch.fc5;     // ... of an fc5 map
     const bool keep_all = m->keep_act && n > slice;
     const size_t keep_half = keep_all ? (size_t)(n + 16) * keep_per : 0;
-    if (keep_all && m->tr_keep_floats < 2 * keep_half) {
+    const size_t keep5_half = keep_all && drop5 > 0.0f ? (size_t)(n + 16) * keep5_per : 0;
+    if (keep_all && m->tr_keep_floats < 2 * keep_half + 2 * keep5_half) {
         CV_HIP(hipDeviceSynchronize());
         if (m->tr_keep) CV_HIP(hipFree(m->tr_keep));
         m->tr_keep = nullptr; m->tr_keep_floats = 0;
-        CV_HIP(hipMalloc(&m->tr_keep, sizeof(float) * 2 * keep_half));
-        m->tr_keep_floats = 2 * keep_half;
+        CV_HIP(hipMalloc(&m->tr_keep, sizeof(float) * (2 * keep_half + 2 * keep5_half)));
+        m->tr_keep_floats = 2 * keep_half + 2 * keep5_half;
     }
+    float *keep5 = m->tr_keep + 2 * keep_half;    // (fc5's mask, then d5, behind fc4's two)
     bool recorded = false;
     m->last_tr_map_n = 0;                         // (the slice sets it; an empty batch leaves no maps)
+    m->last_tr_d5 = nullptr; m->last_tr_mask5 = nullptr;
     for (int64_t off = 0; off < n; off += slice) {
         int64_t cn = n - off < slice ? n - off : slice;
         const bool last = off + slice >= n;
         // (no communication stream -- one rank, or the whole bucket exchanged behind the step: nobody waits for "dense
         // gradients final", so the side streams are not gathered for it)
         hipEvent_t ev = (backward && last && comm) ? m->tr_dense_ready : nullptr;
-        if (train_slice(m, x + (size_t)off * (CV_INPUT_H * 16), y + (size_t)off * 16, cn, off, backward, drop4,
+        if (train_slice(m, x + (size_t)off * (CV_INPUT_H * 16), y + (size_t)off * 16, cn, off, backward, drop4, drop5,
                         seed, step, st, sw, ev, early ? &hdr_early : nullptr, off == 0 ? &defer : nullptr,
                         &hdr_launched))
             return 1;
@@ -1095,9 +1117,15 @@ static int train_enqueue(cv_model *m, const float *x, const float *y, int64_t n,
             const size_t cnt = (size_t)(tile_path ? (cn + 15) / 16 * 16 : cn) * keep_per;
             CV_HIP(hipMemcpyAsync(m->tr_keep + (size_t)off * keep_per, m->last_tr_mask, sizeof(float) * cnt, hipMemcpyDeviceToDevice, st));
             CV_HIP(hipMemcpyAsync(m->tr_keep + keep_half + (size_t)off * keep_per, m->last_tr_d4, sizeof(float) * cnt, hipMemcpyDeviceToDevice, st));
+            if (keep5_half && m->last_tr_d5) {
+                const size_t cnt5 = cnt / keep_per * keep5_per;
+                CV_HIP(hipMemcpyAsync(keep5 + (size_t)off * keep5_per, m->last_tr_mask5, sizeof(float) * cnt5, hipMemcpyDeviceToDevice, st));
+                CV_HIP(hipMemcpyAsync(keep5 + keep5_half + (size_t)off * keep5_per, m->last_tr_d5, sizeof(float) * cnt5, hipMemcpyDeviceToDevice, st));
+            }
         }
     }
     if (keep_all && m->last_tr_d4) { m->last_tr_mask = m->tr_keep; m->last_tr_d4 = m->tr_keep + keep_half; m->last_tr_n = n; }
+    if (keep5_half && m->last_tr_d5) { m->last_tr_mask5 = keep5; m->last_tr_d5 = keep5 + keep5_half; }
     // several slices: the maps of 11..13 / 21..23 are the last slice's, in a workspace of slice + 16 candidates -- none
     // of them is the batch's, so none is exported (option keep_activations keeps the dropout maps of 6 / 7 only)
     if (n > slice) m->last_tr_map_n = 0;

@@ -54,8 +54,8 @@ class Clairvoyante(object):
         for ks in (kernelSize1, kernelSize2, kernelSize3):
             if ks[1] != 4:
                 raise ValueError("kernel width must be 4 (one tap per base)")
-        if dropoutRateFC5 != 0.0:
-            raise ValueError("dropoutRateFC5 other than 0.0 is not supported (reference default, param.py:25)")
+        if not 0.0 <= dropoutRateFC5 < 1.0:
+            raise ValueError("dropoutRateFC5 must be in [0, 1), got %r" % (dropoutRateFC5,))
         self.inputShape = inputShape
         self.outputShape1 = outputShape1; self.outputShape2 = outputShape2
         self.outputShape3 = outputShape3; self.outputShape4 = outputShape4
@@ -268,7 +268,8 @@ class Clairvoyante(object):
 
     def getActivation(self, layer, n):
         """Intermediate of the last pass in the reference's layout (debug / parity); layers 6 / 7 are the
-        alpha-dropout keep mask (times its factor a) and output of the last train / getLoss slice.  11..13 / 21..23 are
+        alpha-dropout keep mask (times its factor a) and output of the last train / getLoss slice, 8 / 9 the same for
+        fc5 after a train step that ran its dropout.  11..13 / 21..23 are
         the pooled maps and conv1..conv3's pre-activation gradients of the last train / getLoss pass, only when it ran
         as one slice (<= 65 536 candidates); otherwise, for n beyond that pass, for 21..23 after getLoss, and for 21 on
         the full topology's default path (not materialised) the call raises (include/clairvoyante_amd.h)."""
@@ -278,6 +279,7 @@ class Clairvoyante(object):
         shp = {1: (n, hp[0], 4, a.cout[0]), 2: (n, hp[1], 4, a.cout[1]), 3: (n, hp[2], 4, a.cout[2]),
                4: (n, a.fc4), 5: (n, a.fc5),
                6: (n, a.fc4), 7: (n, a.fc4),            # last TRAINING slice: a*keep mask of fc4, dropout4 output
+               8: (n, a.fc5), 9: (n, a.fc5),            # ... of fc5 (steps with dropoutRateFC5Val > 0 only)
                11: (n, hp[0], 4, a.cout[0]), 12: (n, hp[1], 4, a.cout[1]), 13: (n, hp[2], 4, a.cout[2]),   # its pooled maps
                21: (n, 33, 4, a.cout[0]), 22: (n, hp[0], 4, a.cout[1]), 23: (n, hp[1], 4, a.cout[2])}[layer]   # its pre-activation gradients
         dst = torch.empty(shp, dtype=torch.float32, device=self.device)
@@ -332,6 +334,8 @@ class Clairvoyante(object):
         self._train_step += 1
         self._ensure_bucket()
         comm = parallel.comm_stream(self)
+        # fc5's rate as it stands now (v3.py:190-191): a value set on the instance after construction applies too
+        _lib.check(self._lib.cv_set_dropout5(self._h, ctypes.c_float(self.dropoutRateFC5Val)))
         _lib.check(self._lib.cv_grad_async(self._h, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()),
                                            x.shape[0], ctypes.c_float(self.dropoutRateFC4Val),
                                            ctypes.c_float(self.l2RegularizationLambdaVal),

@@ -114,10 +114,12 @@ int cv_format_vcf(const int32_t *call, const float *qual, int64_t n, const float
  * keep mask of fc4 times its affine factor a (selu.py:53-62; 0 where a unit was
  * dropped, a where kept, 1 everywhere at rate 0), 7 = dropout4, the layer's output
  * [n, fc4] -- what the parity tests feed to / compare with the oracle.
+ * layer 8 / 9: the same for fc5's alpha-dropout (cv_set_dropout5): 8 = its keep mask times a, 9 = dropout5 [n, fc5];
+ * an error after a pass that ran it at rate 0 (cv_loss, or cv_grad with cv_set_dropout5 0).
  * layers 11..13 / 21..23: the pooled maps (slim: conv outputs) and the pre-activation gradients of conv1..conv3 of the
  * last cv_grad / cv_loss pass, natural layout, for its first n candidates -- only when that pass ran as ONE slice
  * (at most 65 536 candidates).  Every other request is an error, never other values: after a pass of several slices
- * (with or without "keep_activations", which extends 6 / 7 only), for n above the pass's candidates, 21..23 after
+ * (with or without "keep_activations", which extends 6..9 only), for n above the pass's candidates, 21..23 after
  * cv_loss, and 21 of the full topology on the default path (the first layer's unpool rides in its weight-gradient
  * kernel; option dbg4 = 4 materialises it).  tests/test_gpu_train_maps.py holds them to the oracle.
  * Layers 4 / 5 of a pass that ran fc5 and the heads on the tail of the fc4 kernel exist only with option
@@ -198,12 +200,17 @@ int cv_kernel_name(const cv_model *m, int stage, const char **name);
  * (v3.py:140-151).  Synchronises `stream`.                                      */
 int cv_loss(cv_model *m, const float *x_dev, const float *y_dev, int64_t n, double *losses_host,
             void *stream);
-/* forward (phase True: alpha-dropout rate `drop4` on fc4, selu.py:34-69; rate on
- * fc5 is 0.0 = identity) + backward into the flat gradient buffer (data terms
- * only, no lambda term).  seed/step select the counter-based dropout stream.
+/* forward (phase True: alpha-dropout rate `drop4` on fc4, selu.py:34-69; on fc5 the
+ * rate of cv_set_dropout5, 0.0 = identity by default) + backward into the flat gradient
+ * buffer (data terms only, no lambda term).  seed/step select the counter-based dropout
+ * streams (fc5's a domain of its own).
  * losses_host as above with lossL2 = lambda*sum(w^2)/2.  Synchronises.          */
 int cv_grad(cv_model *m, const float *x_dev, const float *y_dev, int64_t n, float drop4,
             float lambda, uint64_t seed, uint64_t step, double *losses_host, void *stream);
+/* alpha-dropout rate on fc5 (v3.py:121, dropoutRateFC5) of the cv_grad / cv_grad_async passes that follow; never of
+ * cv_forward or cv_loss.  [0, 1) is accepted, anything else fails with a message.  Default 0.                   */
+int cv_set_dropout5(cv_model *m, float rate);
+int cv_get_dropout5(const cv_model *m, float *rate);
 /* flat gradient buffer, same order/size as cv_param_buffer (for RCCL all-reduce) */
 int cv_grad_buffer(cv_model *m, float **flat_dev, int64_t *count);
 
