@@ -560,6 +560,30 @@ class _OrderedWriter(object):
                 self.write(self.next, text)
 
 
+# Smallest input (bytes on disk) whose text rows are parsed on the device: (plain text, compressed); None = never.
+# Measured (profiles/r07/text_parse_device.txt): plain text wins from the 65 536-row rung (150 MB) upwards -- below it
+# the fixed cost of the device path (streams, buffers, a round trip per slab) outweighs the host parser's time; a
+# compressed file arrives at one core's inflate rate and the device path wins at no size.
+TEXT_DEVICE_MIN_BYTES = (150000000, None)
+
+
+def parses_on_device(tensor_fn):
+    """Which text reader a one-file run uses is decided from the input, not by the user: the device parser
+    (utils_v2.GetTensorDevice) for a regular file of at least TEXT_DEVICE_MIN_BYTES, the host parser below that and for
+    PIPE.  CV_TEXT_PARSE=host|device forces one side for a regular file -- it exists so that tests and
+    tools/gpu_callvar_text_probe.py can run both readers over the same input, like CV_TEXT=stream."""
+    from . import utils_v2
+    if tensor_fn == "PIPE" or not os.path.isfile(tensor_fn):
+        return False
+    forced = os.environ.get("CV_TEXT_PARSE")
+    if forced in ("host", "device"):
+        return forced == "device"
+    if forced:
+        raise ValueError("CV_TEXT_PARSE must be 'host' or 'device', got %r" % forced)
+    floor = TEXT_DEVICE_MIN_BYTES[1 if utils_v2.is_compressed(tensor_fn) else 0]
+    return floor is not None and os.path.getsize(tensor_fn) >= max(floor, 1)
+
+
 def Test(args, m, utils):
     """callVar.py:180-216 re-cut for the GPU: reader thread(s) (inflate, parse) || GPU (predict + per-candidate
     reductions) || writer (format); the records of a file stay in the order of its rows, files in list order, so the VCF
@@ -573,7 +597,8 @@ def Test(args, m, utils):
     files = tensor_files(args.tensor_fn)
     # plain text is parsed where the page cache holds it at millions of rows/s: batches of 65 536 (the pass size of
     # the network); a compressed stream arrives at one core's inflate rate: smaller batches keep the stages overlapped
-    mapped = utils._map_plain_text(files[0]) is not None if hasattr(utils, "_map_plain_text") else False
+    on_device = len(files) == 1 and parses_on_device(files[0])
+    mapped = on_device or utils._map_plain_text(files[0]) is not None      # (either way the rows arrive at millions per second)
     batch = getattr(args, "batch_size", None) or (65536 if mapped else max(param.predictBatchSize, 16384))
     q_in = Queue(maxsize=2 if mapped else 4)
 
@@ -583,7 +608,11 @@ def Test(args, m, utils):
                 for item in utils.GetTensorFiles(files, batch, 0, 1, ordered=False):     # batches taken as they complete
                     q_in.put(item)
             else:
-                for _end, c, X, pos in utils.GetTensor(files[0], batch):
+                side = "device" if on_device else "host"
+                utils.text_parse_counts[side] += 1
+                logging.info("Text tensors are parsed on the %s" % side)
+                batches = utils.GetTensorDevice(files[0], batch, m.device) if on_device else utils.GetTensor(files[0], batch)
+                for _end, c, X, pos in batches:
                     q_in.put((0, c, X, pos))
                 q_in.put((0, None, None, None))
         except BaseException as e:   # surfaced on the consumer side (the reference loses it)
@@ -603,13 +632,17 @@ def Test(args, m, utils):
             nxt = None
             if item is not None and item[1] is not None and item[1] > 0:
                 k, num, X, pos = item
-                xd = torch.from_numpy(X).to(m.device, non_blocking=True)
+                xd = X if torch.is_tensor(X) else torch.from_numpy(X).to(m.device, non_blocking=True)
                 call, qual = predict_and_reduce(m, xd)
                 nxt = (k, num, X, pos, call, qual, fetcher.mark())
             if pending is not None:      # format batch j while the GPU works on batch j+1
                 pk, pnum, pX, ppos, pcall, pqual, pev = pending
-                hcall, hqual = fetcher.fetch(pev, pcall, pqual)
-                out.add(pk, format_records(args, pnum, pX, ppos, hcall, hqual))
+                if torch.is_tensor(pX):  # rows parsed on the device: only those that give a record come to the host
+                    hcall, hqual, rows, xrow = fetcher.fetch(pev, pcall, pqual, pX, bool(args.showRef))
+                    out.add(pk, format_records(args, pnum, rows, ppos, hcall, hqual, xrow))
+                else:
+                    hcall, hqual = fetcher.fetch(pev, pcall, pqual)
+                    out.add(pk, format_records(args, pnum, pX, ppos, hcall, hqual))
             pending = nxt
             if item is not None and item[1] is None:      # end of file k (its last batch was formatted just above)
                 out.end(item[0])

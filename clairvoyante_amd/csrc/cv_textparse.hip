@@ -1,0 +1,362 @@
+// cv_textparse.hip -- the text-tensor reader on the device: a slab of text in HBM -> rows [lines,528] fp32.
+// The host reader (cv_hostio.cpp, cv_parse_tensor_text) is the checker of this one and the only parser of lines that
+// are not in the producer's format (dataPrepScripts/CreateTensor.py:24,56: "%s %d %s" + 528 x " %0.1f"): such a line
+// gets status HOST here and is neither accepted nor rejected.
+//
+//   tp_count_newlines   per 4 KiB tile of the slab: number of '\n' (16-byte loads, a grid-stride loop over tiles)
+//   hipcub ExclusiveSum tile counts -> number of the first line that ENDS in each tile (+ the total behind the last)
+//   tp_line_ends        the tiles again: line_end[i] = byte offset of the newline that closes line i (i < max_lines)
+//   tp_begin            info = {bytes consumed, lines, 0, 0}
+//   tp_parse_rows       one wave per line: the line goes to LDS in 1 KiB steps, 64 bytes are classified at a time,
+//                       __ballot gives the masks of blanks and token starts, the lane that owns a token start parses
+//                       that token (<= 12 bytes) from LDS into an LDS row, the wave checks the row, subtracts matrix 0
+//                       and stores it with 16-byte stores
+//   tp_gather_rows      rows named by an index list, in list order, into a dense tensor (cv_text_gather_rows)
+//
+// The slab may start at any address: the kernels read the 16-byte granules that CONTAIN the slab (so up to 15 bytes in
+// front of it and behind it, inside the granules the allocation owns anyway) and mask what lies outside.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+#include <stdint.h>
+#include "../../include/clairvoyante_amd.h"
+
+void cv_set_error(const char *fmt, ...);
+
+#define TP_HIP(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t _e = (expr);                                                                        \
+        if (_e != hipSuccess) {                                                                        \
+            cv_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
+            return 1;                                                                                  \
+        }                                                                                              \
+    } while (0)
+
+namespace {
+
+constexpr int NV = CV_INPUT_H * CV_INPUT_W * CV_INPUT_C;     // 528
+constexpr int TILE_THREADS = 256;
+constexpr int TILE = TILE_THREADS * 16;                      // bytes of the slab one block looks at per step
+constexpr int INDEX_GRID = 2048;
+constexpr int WAVE = 64;
+constexpr int PARSE_WAVES = 4;                               // waves (= lines in flight) per block of tp_parse_rows
+constexpr int LINE_LDS = CV_TEXT_LINE_CAP + 32;              // a line of the cap at any offset inside its first granule
+constexpr int PARSE_GRID = 2048;
+
+__device__ __forceinline__ uint32_t newline_mask(const uint4 v, int64_t g0, int64_t lo, int64_t hi)
+{
+    // bit k = byte k of the granule at granule-relative offset g0 is '\n' and lies inside [lo, hi)
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const uint32_t b = (w[k >> 2] >> (8 * (k & 3))) & 0xffu;
+        m |= (uint32_t)(b == 10u) << k;
+    }
+    if (g0 < lo) { const int64_t d = lo - g0; m = d >= 16 ? 0u : m & (0xffffu << d); }
+    if (g0 + 16 > hi) { const int64_t d = hi - g0; m = d <= 0 ? 0u : m & (0xffffu >> (16 - d)); }
+    return m;
+}
+
+// `gran` = the 16-byte granule that holds the slab's first byte, `shift` = offset of that byte inside it
+__global__ __launch_bounds__(TILE_THREADS) void tp_count_newlines(const uint4 *gran, int shift, int64_t len, int64_t ntiles,
+                                                                   uint32_t *tile_cnt)
+{
+    using Reduce = hipcub::BlockReduce<uint32_t, TILE_THREADS>;
+    __shared__ typename Reduce::TempStorage tmp;
+    const int64_t lo = shift, hi = shift + len;
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int64_t g0 = t * TILE + (int64_t)threadIdx.x * 16;
+        uint32_t c = 0;
+        if (g0 < hi) c = (uint32_t)__popc(newline_mask(gran[g0 >> 4], g0, lo, hi));
+        const uint32_t sum = Reduce(tmp).Sum(c);
+        if (threadIdx.x == 0) tile_cnt[t] = sum;
+        __syncthreads();
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) tile_cnt[ntiles] = 0;        // its scanned value is the total
+}
+
+__global__ __launch_bounds__(TILE_THREADS) void tp_line_ends(const uint4 *gran, int shift, int64_t len, int64_t ntiles,
+                                                              const uint32_t *tile_first, int64_t max_lines, int64_t *line_end)
+{
+    using Scan = hipcub::BlockScan<uint32_t, TILE_THREADS>;
+    __shared__ typename Scan::TempStorage tmp;
+    const int64_t lo = shift, hi = shift + len;
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int64_t first = tile_first[t];
+        if (first >= max_lines) continue;                                  // (uniform over the block)
+        const int64_t g0 = t * TILE + (int64_t)threadIdx.x * 16;
+        uint32_t m = 0;
+        if (g0 < hi) m = newline_mask(gran[g0 >> 4], g0, lo, hi);
+        uint32_t before = 0;
+        Scan(tmp).ExclusiveSum((uint32_t)__popc(m), before);
+        int64_t line = first + before;
+        while (m && line < max_lines) {
+            const int k = __ffs(m) - 1;
+            line_end[line++] = g0 + k - shift;
+            m &= m - 1;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void tp_begin(const uint32_t *tile_first, int64_t ntiles, int64_t max_lines, const int64_t *line_end, int64_t *info)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    int64_t lines = ntiles > 0 ? (int64_t)tile_first[ntiles] : 0;
+    if (lines > max_lines) lines = max_lines;
+    info[0] = lines > 0 ? line_end[lines - 1] + 1 : 0;
+    info[1] = lines;
+    info[2] = 0;
+    info[3] = 0;
+}
+
+// LDS written by some lanes of a wave is read by others: order the accesses within the wave
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint64_t lanes_below() { return (1ull << (threadIdx.x & (WAVE - 1))) - 1ull; }
+
+// the ten constants of cv_hostio.cpp's parse_row_fast (copied to LDS by tp_parse_rows: a lane looks its digit up there,
+// a divergent load from global memory per token cost more than the rest of the token)
+__device__ const double tp_tenth[10] = {0.0 / 10.0, 1.0 / 10.0, 2.0 / 10.0, 3.0 / 10.0, 4.0 / 10.0,
+                                        5.0 / 10.0, 6.0 / 10.0, 7.0 / 10.0, 8.0 / 10.0, 9.0 / 10.0};
+
+// One value token "[-]d{1,9}[.d]" that starts at L[j] and must end at a blank or at the end of the line (L[n..] is
+// never read).  Returns false for anything else.
+__device__ __forceinline__ bool parse_value(const unsigned char *L, int j, int n, const double *tenth, float *out)
+{
+    auto at = [&](int k) -> unsigned { return k < n ? (unsigned)L[k] : 10u; };
+    const bool neg = at(j) == '-';
+    j += neg;
+    unsigned d = at(j) - '0';
+    if (d > 9) return false;
+    uint32_t ip = d;
+    int nd = 1;
+    j++;
+    while (nd <= 9 && (d = at(j) - '0') <= 9) { ip = ip * 10u + d; j++; nd++; }
+    if (nd > 9) return false;                               // ten digits or more: the host's general path
+    double v = (double)ip;
+    if (at(j) == '.') {
+        const unsigned f = at(j + 1) - '0';
+        if (f > 9) return false;
+        v += tenth[f];
+        j += 2;
+    }
+    const unsigned e = at(j);
+    if (e != ' ' && e != 10u) return false;
+    *out = (float)(neg ? -v : v);
+    return true;
+}
+
+__global__ __launch_bounds__(PARSE_WAVES * WAVE) void tp_parse_rows(const uint4 *gran, int shift, const int64_t *line_end,
+                                                                     int64_t *info, float *x, int64_t *meta, uint8_t *status)
+{
+    __shared__ uint4 text_lds[PARSE_WAVES][LINE_LDS / 16];
+    __shared__ float4 row_lds[PARSE_WAVES][NV / 4];
+    __shared__ double tenth_lds[10];
+    if (threadIdx.x < 10) tenth_lds[threadIdx.x] = tp_tenth[threadIdx.x];
+    __syncthreads();
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+    const int64_t lines = info[1];
+    const int64_t nwaves = (int64_t)gridDim.x * PARSE_WAVES;
+    unsigned long long n_row = 0, n_host = 0;
+    float *row = (float *)row_lds[w];
+    for (int64_t i = (int64_t)blockIdx.x * PARSE_WAVES + w; i < lines; i += nwaves) {
+        const int64_t start = i ? line_end[i - 1] + 1 : 0;
+        const int64_t n64 = line_end[i] - start;             // bytes of the line without its newline
+        uint8_t st = CV_TEXT_ROW;
+        int64_t sp[3] = {0, 0, 0};
+        if (n64 == 0) st = CV_TEXT_SKIP;
+        else if (n64 > CV_TEXT_LINE_CAP) st = CV_TEXT_HOST;
+        else {
+            const int n = (int)n64;
+            const int64_t a = shift + start;                  // offset of the line's first byte from granule 0
+            const int head = (int)(a & 15);
+            const int ngran = (head + n + 15) >> 4;
+            for (int g = lane; g < ngran; g += WAVE) text_lds[w][g] = gran[(a >> 4) + g];
+            wave_sync();
+            const unsigned char *L = (const unsigned char *)text_lds[w] + head;
+            // pass over the line, 64 bytes at a time: blanks, forbidden bytes, the first three blanks
+            int nblank = 0;
+            bool bad = L[0] == ' ' || L[n - 1] == ' ';        // (wave-uniform reads)
+            int carry_blank = 0;                              // the byte in front of this step was a blank
+            for (int b = 0; b < n && !bad; b += WAVE) {
+                const int j = b + lane;
+                const unsigned c = j < n ? (unsigned)L[j] : 'x';
+                const uint64_t blank = __ballot(c == ' ');
+                const uint64_t other = __ballot(c == '\t' || c == '\r' || c == '\v' || c == '\f');
+                if (other || (blank & (blank << 1)) || (carry_blank && (blank & 1))) { bad = true; break; }
+                carry_blank = (int)(blank >> 63);
+                // the first three blanks close the three header tokens
+                uint64_t m = blank;
+                while (m && nblank < 3) { sp[nblank++] = b + __ffsll((long long)m) - 1; m &= m - 1; }
+                if (nblank >= 3) nblank += __popcll(m);
+            }
+            if (bad || nblank != 3 + NV - 1) st = CV_TEXT_HOST;        // 3 header tokens + 528 values: 530 blanks
+            else {
+                // values: every byte behind a blank, from the third blank on, starts a token
+                const int v0 = (int)sp[2];
+                int before = 0;                                // value tokens in front of this step
+                int ok = 1;
+                for (int b = v0 & ~(WAVE - 1); b < n; b += WAVE) {
+                    const int j = b + lane;
+                    const bool starts = j > v0 && j < n && L[j - 1] == ' ';
+                    const uint64_t sm = __ballot(starts);
+                    if (starts) {
+                        const int t = before + __popcll(sm & lanes_below());
+                        float v;
+                        if (parse_value(L, j, n, tenth_lds, &v)) row[t] = v;      // t < 528: the line has 530 blanks
+                        else ok = 0;
+                    }
+                    before += __popcll(sm);
+                }
+                if (__ballot(!ok)) st = CV_TEXT_HOST;
+                else {
+                    const int sl = (int)(sp[2] - sp[1] - 1);
+                    unsigned c = sl > CV_INPUT_H / 2 ? (unsigned)L[sp[1] + 1 + CV_INPUT_H / 2] : 0u;
+                    if (c >= 'a' && c <= 'z') c -= 32;
+                    if (c != 'A' && c != 'C' && c != 'G' && c != 'T') st = CV_TEXT_SKIP;
+                }
+            }
+            if (st == CV_TEXT_ROW) {
+                wave_sync();
+                float4 *dst = (float4 *)(x + i * NV);
+                for (int e = lane; e < NV / 4; e += WAVE) {
+                    float4 q = row_lds[w][e];
+                    q.y -= q.x; q.z -= q.x; q.w -= q.x;
+                    dst[e] = q;
+                }
+                if (lane < 6) {
+                    const int k = lane >> 1;
+                    const int64_t tb = k == 0 ? 0 : sp[k - 1] + 1;
+                    meta[i * 6 + lane] = (lane & 1) ? sp[k] - tb : start + tb;
+                }
+            }
+            wave_sync();                   // the LDS line and row are reused by the next line
+        }
+        if (lane == 0) status[i] = st;
+        n_row += st == CV_TEXT_ROW;
+        n_host += st == CV_TEXT_HOST;
+    }
+    if (lane == 0) {
+        if (n_row) atomicAdd((unsigned long long *)&info[2], n_row);
+        if (n_host) atomicAdd((unsigned long long *)&info[3], n_host);
+    }
+}
+
+__global__ __launch_bounds__(256) void tp_gather_rows(const float4 *x, const int64_t *idx, int64_t nrows, float4 *out)
+{
+    const int64_t total = nrows * (NV / 4);
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = e / (NV / 4), c = e - r * (NV / 4);
+        out[e] = x[idx[r] * (NV / 4) + c];
+    }
+}
+
+struct ws_layout {
+    int64_t ntiles_max;          // tiles of a slab of `len` bytes at the worst offset inside its first granule
+    size_t tile_cnt, tile_first, line_end, scan_tmp, scan_bytes, total;
+};
+
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+int layout(int64_t len, int64_t max_lines, ws_layout *L)
+{
+    L->ntiles_max = (len + 15 + TILE - 1) / TILE;
+    size_t o = 0;
+    L->tile_cnt = o; o = up256(o + (size_t)(L->ntiles_max + 1) * 4);
+    L->tile_first = o; o = up256(o + (size_t)(L->ntiles_max + 1) * 4);
+    L->line_end = o; o = up256(o + (size_t)(max_lines > 0 ? max_lines : 1) * 8);
+    size_t need = 0;
+    TP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                            (int)(L->ntiles_max + 1), (hipStream_t)0));
+    L->scan_tmp = o; L->scan_bytes = need; o = up256(o + need);
+    L->total = o;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int cv_parse_tensor_text_dev_workspace(int64_t len, int64_t max_lines, int64_t *bytes)
+{
+    if (!bytes) { cv_set_error("cv_parse_tensor_text_dev_workspace: null argument"); return 1; }
+    if (len < 0 || max_lines < 0 || len > CV_TEXT_SLAB_MAX) {
+        cv_set_error("cv_parse_tensor_text_dev_workspace: len %lld / max_lines %lld out of range (0 .. %lld bytes)",
+                     (long long)len, (long long)max_lines, (long long)CV_TEXT_SLAB_MAX);
+        return 1;
+    }
+    ws_layout L;
+    if (layout(len, max_lines, &L)) return 1;
+    *bytes = (int64_t)L.total;
+    return 0;
+}
+
+extern "C" int cv_parse_tensor_text_dev(const char *text_dev, int64_t len, int64_t max_lines, float *x_dev,
+                                        int64_t *meta_dev, uint8_t *status_dev, int64_t *info_dev, void *workspace_dev,
+                                        int64_t workspace_bytes, void *stream)
+{
+    if (!text_dev || !x_dev || !meta_dev || !status_dev || !info_dev || !workspace_dev) {
+        cv_set_error("cv_parse_tensor_text_dev: null argument");
+        return 1;
+    }
+    if (len < 0 || max_lines < 0 || len > CV_TEXT_SLAB_MAX) {
+        cv_set_error("cv_parse_tensor_text_dev: len %lld / max_lines %lld out of range (0 .. %lld bytes)", (long long)len,
+                     (long long)max_lines, (long long)CV_TEXT_SLAB_MAX);
+        return 1;
+    }
+    if (((uintptr_t)x_dev & 15) || ((uintptr_t)meta_dev & 7) || ((uintptr_t)info_dev & 7) || ((uintptr_t)workspace_dev & 255)) {
+        cv_set_error("cv_parse_tensor_text_dev: x_dev must be 16-byte, meta_dev / info_dev 8-byte, the workspace 256-byte aligned");
+        return 1;
+    }
+    ws_layout L;
+    if (layout(len, max_lines, &L)) return 1;
+    if (workspace_bytes < (int64_t)L.total) {
+        cv_set_error("cv_parse_tensor_text_dev: workspace holds %lld bytes, need %lld", (long long)workspace_bytes, (long long)L.total);
+        return 1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace_dev;
+    uint32_t *tile_cnt = (uint32_t *)(ws + L.tile_cnt), *tile_first = (uint32_t *)(ws + L.tile_first);
+    int64_t *line_end = (int64_t *)(ws + L.line_end);
+    const int shift = (int)((uintptr_t)text_dev & 15);
+    const uint4 *gran = (const uint4 *)(text_dev - shift);
+    // (the tile count of the worst offset: what the workspace and the scan were sized for; a tile behind the slab counts 0)
+    const int64_t ntiles = len > 0 && max_lines > 0 ? L.ntiles_max : 0;
+    if (ntiles > 0) {
+        const int grid = (int)(ntiles < INDEX_GRID ? ntiles : INDEX_GRID);
+        hipLaunchKernelGGL(tp_count_newlines, dim3(grid), dim3(TILE_THREADS), 0, st, gran, shift, len, ntiles, tile_cnt);
+        size_t need = L.scan_bytes;
+        TP_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.scan_tmp, need, (const uint32_t *)tile_cnt, tile_first, (int)(ntiles + 1), st));
+        hipLaunchKernelGGL(tp_line_ends, dim3(grid), dim3(TILE_THREADS), 0, st, gran, shift, len, ntiles,
+                           (const uint32_t *)tile_first, max_lines, line_end);
+    }
+    hipLaunchKernelGGL(tp_begin, dim3(1), dim3(64), 0, st, (const uint32_t *)tile_first, ntiles, max_lines,
+                       (const int64_t *)line_end, info_dev);
+    if (ntiles > 0) {
+        const int64_t blocks = (max_lines + PARSE_WAVES - 1) / PARSE_WAVES;
+        hipLaunchKernelGGL(tp_parse_rows, dim3((int)(blocks < PARSE_GRID ? blocks : PARSE_GRID)), dim3(PARSE_WAVES * WAVE), 0, st,
+                           gran, shift, (const int64_t *)line_end, info_dev, x_dev, meta_dev, status_dev);
+    }
+    TP_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int cv_text_gather_rows(const float *x_dev, const int64_t *index_dev, int64_t nrows, float *out_dev, void *stream)
+{
+    if (nrows < 0) { cv_set_error("cv_text_gather_rows: negative row count"); return 1; }
+    if (nrows == 0) return 0;
+    if (!x_dev || !index_dev || !out_dev) { cv_set_error("cv_text_gather_rows: null argument"); return 1; }
+    if (((uintptr_t)x_dev & 15) || ((uintptr_t)out_dev & 15) || ((uintptr_t)index_dev & 7)) {
+        cv_set_error("cv_text_gather_rows: the tensors must be 16-byte, the index list 8-byte aligned");
+        return 1;
+    }
+    const int64_t blocks = (nrows * (NV / 4) + 255) / 256;
+    hipLaunchKernelGGL(tp_gather_rows, dim3((int)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       (const float4 *)x_dev, index_dev, nrows, (float4 *)out_dev);
+    TP_HIP(hipGetLastError());
+    return 0;
+}

@@ -632,6 +632,342 @@ def _join_pos(bufs):
     return PosBatch(pieces=bufs)
 
 
+# ---- the text reader on the device (csrc/cv_textparse.hip) -------------------------------------------------------------
+TEXT_SKIP, TEXT_ROW, TEXT_HOST = 0, 1, 2            # CV_TEXT_* of include/clairvoyante_amd.h
+text_parse_counts = {"device": 0, "host": 0}        # GetTensorDevice / GetTensor runs callVar.Test started (tests read it)
+
+
+def _last_newline(a):
+    """index of the last '\n' of the uint8 array `a`, -1 if it has none (looks at growing windows from the back)"""
+    n, w = len(a), 4096
+    while True:
+        lo = max(0, n - w)
+        hit = np.flatnonzero(a[lo:n] == 10)
+        if len(hit):
+            return lo + int(hit[-1])
+        if lo == 0:
+            return -1
+        w *= 8
+
+
+def _first_newline(a, start):
+    n, w = len(a), 4096
+    while start < n:
+        hit = np.flatnonzero(a[start:start + w] == 10)
+        if len(hit):
+            return start + int(hit[0])
+        start += w
+        w *= 8
+    return -1
+
+
+def _slab_bytes(first_line, num):
+    """bytes of text that hold about `num` rows; CV_TEXT_SLAB_BYTES overrides it (tests cut the input finely with it)"""
+    forced = os.environ.get("CV_TEXT_SLAB_BYTES")
+    if forced:
+        return max(1, int(forced))
+    return min(max(num, 1) * max(first_line, 64), _PinnedPool.MAX_BYTES)     # (what a page-locked staging buffer holds)
+
+
+def _text_slabs(tensor_fn, num):
+    """The input cut into slabs of whole lines, as uint8 arrays that end in '\n': views of the memory-mapped plain file,
+    or pieces of the inflated stream (`_GzipFile` / the reference's `gzip -fdc` pipe) with the partial last line of one
+    read carried into the next, as GetTensor carries `pending`.  A last line without newline gets one."""
+    data = _map_plain_text(tensor_fn)
+    if data is not None:
+        n, off = len(data), 0
+        nl = _first_newline(data, 0)
+        size = _slab_bytes((nl if nl >= 0 else n) + 1, num)
+        while off < n:
+            end = min(off + size, n)
+            if end < n:
+                k = _last_newline(data[off:end])
+                if k < 0:                                # one line longer than a slab: up to its end
+                    k = _first_newline(data, end)
+                    k = k - off if k >= 0 else -1
+                end = off + k + 1 if k >= 0 else n
+            if data[end - 1] != 10:                      # (only the end of the file)
+                yield np.frombuffer(bytes(data[off:end]) + b"\n", dtype=np.uint8)
+            else:
+                yield data[off:end]
+            off = end
+        return
+    proc, fo = _open_tensor_stream(tensor_fn)
+    done = False
+    try:
+        parts, have, size = [], 0, None          # pieces read since the last slab (joined ONCE per slab) and their bytes
+        while True:
+            chunk = fo.read((1 << 16) if size is None else max(size - have, 1 << 12))
+            if chunk:
+                parts.append(chunk); have += len(chunk)
+                if size is None:
+                    nl = chunk.find(b"\n")
+                    if nl < 0:
+                        continue
+                    size = _slab_bytes(have - len(chunk) + nl + 1, num)
+                if have < size or (b"\n" not in chunk and not any(b"\n" in c for c in parts)):
+                    continue
+            piece = parts[0] if len(parts) == 1 else b"".join(parts)
+            if not chunk:
+                if piece:
+                    yield np.frombuffer(piece if piece.endswith(b"\n") else piece + b"\n", dtype=np.uint8)
+                break
+            k = piece.rfind(b"\n")
+            yield np.frombuffer(piece, dtype=np.uint8)[:k + 1]
+            parts = [piece[k + 1:]] if k + 1 < len(piece) else []
+            have = len(piece) - k - 1
+        done = True
+    finally:
+        _close_quietly_unless(done, proc, fo, tensor_fn)
+
+
+def _read_ahead(items, depth):
+    """the generator `items` run in a thread of its own, at most `depth` items ahead of the consumer; an exception of
+    the generator is raised where the consumer would have got the item"""
+    import queue
+    import threading
+    q, stop = queue.Queue(maxsize=depth), threading.Event()
+
+    def put(item):
+        while not stop.is_set():
+            try:
+                q.put(item, timeout=0.1)
+                return True
+            except queue.Full:
+                pass
+        return False
+
+    def run():
+        try:
+            for item in items:
+                if not put((item, None)):
+                    break
+            else:
+                put((None, StopIteration()))
+        except BaseException as e:
+            put((None, e))
+        finally:
+            items.close()
+
+    t = threading.Thread(target=run, daemon=True)
+    t.start()
+    try:
+        while True:
+            item, err = q.get()
+            if isinstance(err, StopIteration):
+                return
+            if err is not None:
+                raise err
+            yield item
+    finally:
+        stop.set()
+        t.join()
+
+
+class _TextSlabDevice(object):
+    """The device side of GetTensorDevice: uploads a slab (the runtime's staged copy from pageable memory, on a copy
+    stream), runs cv_parse_tensor_text_dev over it on a parse stream, brings info / meta / status back in one copy.
+    (A test without a GPU replaces this class with a stand-in that marks every line HOST.)"""
+    STAGE_THREADS = 8
+
+    def __init__(self, device, cap):
+        import torch
+        from .model import _require_gpu
+        _require_gpu()                                       # (no CPU fallback here either: the caller chose this reader)
+        self.torch, self.device, self.cap = torch, torch.device(device), cap
+        self.lib = _lib.load()
+        with torch.cuda.device(self.device):
+            self.copy_stream = torch.cuda.Stream(device=self.device)
+            self.stream = torch.cuda.Stream(device=self.device)
+        from concurrent.futures import ThreadPoolExecutor
+        self.pool = ThreadPoolExecutor(self.STAGE_THREADS)
+
+    def close(self):
+        self.pool.shutdown(wait=True)
+
+    def upload(self, slab):
+        """-> handle of the slab's text in HBM.  The bytes go through a page-locked buffer, copied there by several
+        threads (one thread moves ~10 GB/s out of the page cache, and the runtime's own staging of a pageable source is
+        one thread too); the copy to the device is then asynchronous on the copy stream."""
+        torch = self.torch
+        n = len(slab)
+        import warnings
+        stage = slab
+        if _PinnedPool.MIN_BYTES <= n <= _PinnedPool.MAX_BYTES:      # (outside it the pool hands out pageable memory: a
+            stage = _pinned.empty((n,), np.uint8)                    # copy into that would only add to the runtime's own)
+            cuts = [n * t // self.STAGE_THREADS for t in range(self.STAGE_THREADS + 1)] if n >= (1 << 22) else [0, n]
+            list(self.pool.map(lambda t: np.copyto(stage[cuts[t]:cuts[t + 1]], slab[cuts[t]:cuts[t + 1]]), range(len(cuts) - 1)))
+        with torch.cuda.device(self.device), torch.cuda.stream(self.copy_stream):
+            text = torch.empty(n + 32, dtype=torch.uint8, device=self.device)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")                      # (a read-only source: the map, a bytes object)
+                text[:n].copy_(torch.from_numpy(stage), non_blocking=True)
+            ev = torch.cuda.Event(); ev.record(self.copy_stream)
+        return text, n, ev, stage
+
+    def parse(self, up, start):
+        """enqueues the parse of the uploaded slab from byte `start` on; -> job"""
+        torch = self.torch
+        text, n, ev, _stage = up
+        cap, length = self.cap, n - start
+        need = ctypes.c_int64()
+        _lib.check(self.lib.cv_parse_tensor_text_dev_workspace(length, cap, ctypes.byref(need)))
+        with torch.cuda.device(self.device):
+            x = torch.empty((cap, _NV), dtype=torch.float32, device=self.device)
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))    # (a recycled block: its last reader)
+            with torch.cuda.stream(self.stream):
+                self.stream.wait_event(ev)
+                ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+                out = torch.empty(32 + cap * 48 + cap, dtype=torch.uint8, device=self.device)   # info | meta | status
+                p = out.data_ptr()
+                _lib.check(self.lib.cv_parse_tensor_text_dev(
+                    ctypes.c_void_p(text.data_ptr() + start), length, cap, ctypes.c_void_p(x.data_ptr()),
+                    ctypes.c_void_p(p + 32), ctypes.c_void_p(p + 32 + cap * 48), ctypes.c_void_p(p),
+                    ctypes.c_void_p(ws.data_ptr()), need.value, ctypes.c_void_p(self.stream.cuda_stream)))
+                host = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)
+                host.copy_(out, non_blocking=True)
+        return {"x": x, "host": host, "keep": (text, ws, out)}
+
+    def collect(self, job):
+        """-> (info [4] int64, status [lines] uint8, meta [lines,6] int64) once the job's kernels have run"""
+        self.stream.synchronize()
+        h, cap = job["host"].numpy(), self.cap
+        info = h[:32].view(np.int64)
+        lines = int(info[1])
+        job["keep"] = None
+        return info, h[32 + cap * 48:32 + cap * 48 + lines], h[32:32 + cap * 48].view(np.int64).reshape(cap, 6)[:lines]
+
+    def patch(self, job, slots, rows):
+        """rows [k,528] parsed on the host into the slots of their lines"""
+        torch = self.torch
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            idx = torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int64)).to(self.device)
+            job["x"].index_copy_(0, idx, torch.from_numpy(rows).to(self.device))
+
+    def rows(self, job, lines, index):
+        """-> X [c,33,4,4] on the device: the first `lines` slots, or the slots `index` names gathered in that order"""
+        torch = self.torch
+        shape = (2 * param.flankingBaseNum + 1, 4, param.matrixNum)
+        x = job["x"]
+        with torch.cuda.device(self.device):
+            if index is None:
+                self.stream.synchronize()
+                return x[:lines].reshape((lines,) + shape)
+            out = torch.empty((len(index), _NV), dtype=torch.float32, device=self.device)
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(self.stream):
+                idx = torch.from_numpy(np.ascontiguousarray(index, dtype=np.int64)).to(self.device)
+                _lib.check(self.lib.cv_text_gather_rows(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(idx.data_ptr()),
+                                                        len(index), ctypes.c_void_p(out.data_ptr()),
+                                                        ctypes.c_void_p(self.stream.cuda_stream)))
+            self.stream.synchronize()
+            return out.reshape((len(index),) + shape)
+
+    def empty(self):
+        return self.torch.empty((0, 2 * param.flankingBaseNum + 1, 4, param.matrixNum), dtype=self.torch.float32,
+                                device=self.device)
+
+
+def _merge_host_lines(lib, text, info, status, meta):
+    """The lines of a slab the device left to the host (status HOST; normally none), parsed one by one with
+    cv_parse_tensor_text.  `text`: the bytes the job parsed.  -> (status, meta) with those lines ROW or SKIP, the slots
+    and rows [k,528] to patch, the number of malformed lines."""
+    todo = np.flatnonzero(status == TEXT_HOST)
+    if len(todo) == 0:
+        return status, meta, todo, None, 0
+    status, meta = status.copy(), meta.copy()
+    ends = np.flatnonzero(text[:int(info[0])] == 10)
+    rows = np.empty((len(todo), _NV), dtype=np.float32)
+    row = np.empty(_NV, dtype=np.float32)
+    m1 = np.empty(6, dtype=np.int64)
+    consumed = ctypes.c_int64(); nrows = ctypes.c_int64(); nbad = ctypes.c_int64()
+    held = text if text.flags.c_contiguous else np.ascontiguousarray(text)
+    base, k, bad = held.ctypes.data, 0, 0
+    slots = np.empty(len(todo), dtype=np.int64)
+    for i in todo:
+        start = int(ends[i - 1]) + 1 if i else 0
+        _lib.check(lib.cv_parse_tensor_text(ctypes.c_void_p(base + start), int(ends[i]) + 1 - start, 1,
+                                            row.ctypes.data_as(ctypes.c_void_p), m1.ctypes.data_as(ctypes.c_void_p),
+                                            ctypes.byref(consumed), ctypes.byref(nrows), ctypes.byref(nbad)))
+        bad += nbad.value
+        if nrows.value:
+            status[i] = TEXT_ROW
+            meta[i] = m1
+            meta[i, 0::2] += start
+            rows[k] = row; slots[k] = i; k += 1
+        else:
+            status[i] = TEXT_SKIP
+    return status, meta, slots[:k], rows[:k], bad
+
+
+def _closing(items, dev):
+    try:
+        for item in items:
+            yield item
+    finally:
+        items.close()
+        if hasattr(dev, "close"):
+            dev.close()
+
+
+def GetTensorDevice(tensor_fn, num, device, log=True):
+    """GetTensor with the rows parsed on the GPU: generator of (endFlag, c, X_dev, pos), X_dev a [c,33,4,4] fp32 torch
+    tensor on `device` (the bits GetTensor gives), pos a PosBatch over the host copy of the text.  The input is cut
+    into slabs of whole lines (about `num` rows each, from the first line's length), slab k + 1 is copied to the device
+    under the kernels of slab k, and every slab gives one batch -- so a batch holds ABOUT `num` rows, not exactly
+    `num`; candidates are independent, the VCF does not depend on the cut.  Lines that are not in the producer's format
+    come back marked and are parsed by cv_parse_tensor_text (malformed ones are reported as GetTensor reports them); a
+    slab with more lines than a batch has slots is finished by parsing its remainder again.  The last batch, and only
+    it, carries endFlag 1 (an input without rows gives one empty batch)."""
+    lib = _lib.load()
+    cap = num + num // 8 + 64
+    dev = _TextSlabDevice(device, cap)
+    total = 0
+    held = None
+
+    def batches():
+        slabs = _read_ahead(_text_slabs(tensor_fn, num), 2)   # (the inflate of slab k + 1 runs beside the staging of slab k)
+        slab = next(slabs, None)
+        up = dev.upload(slab) if slab is not None else None
+        while slab is not None:
+            start = 0
+            job = dev.parse(up, start)
+            nxt = next(slabs, None)                            # (its copy runs under the kernels of `slab`)
+            nxt_up = dev.upload(nxt) if nxt is not None else None
+            while True:
+                info, status, meta = dev.collect(job)
+                text = slab[start:]
+                lines = int(info[1])
+                status, meta, slots, rows, bad = _merge_host_lines(lib, text, info, status, meta)
+                if bad:
+                    print("UnpackATensorRecord Failure (%d malformed rows skipped)" % bad, file=sys.stderr)
+                if len(slots):
+                    dev.patch(job, slots, rows)
+                keep = np.flatnonzero(status == TEXT_ROW)
+                if len(keep):
+                    x = dev.rows(job, lines, None if len(keep) == lines else keep)
+                    yield len(keep), x, PosBatch(text[:int(info[0])], meta[keep])
+                start += int(info[0])
+                if lines == 0 or start >= len(slab):
+                    break
+                job = dev.parse(up, start)
+            slab, up = nxt, nxt_up
+
+    for c, x, pos in _closing(batches(), dev):
+        if held is not None:
+            total += held[0]
+            if log:
+                print("Processed %d tensors" % total, file=sys.stderr)
+            yield (0,) + held
+        held = (c, x, pos)
+    if held is None:
+        held = (0, dev.empty(), PosBatch(b"", np.zeros((0, 6), dtype=np.int64)))
+    total += held[0]
+    if log:
+        print("Processed %d tensors" % total, file=sys.stderr)
+    yield (1,) + held
+
+
 # ---- blosc container (python-blosc pack_array / unpack_array equivalents) ---------------
 def blosc_decompress(chunk):
     lib = _lib.load()

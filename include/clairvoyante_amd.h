@@ -267,6 +267,35 @@ int cv_parse_tensor_text(const char *buf, int64_t len, int64_t max_rows, float *
 /* Host threads cv_parse_tensor_text may use (process-wide, default 1); the rows do not depend on it. */
 int cv_set_host_threads(int n);
 
+/* The same reader on the device, for text that is already in HBM: a slab text_dev[0,len) of '\n'-terminated lines at
+ * any alignment (the kernels read the 16-byte granules that contain the slab and mask what lies outside it).  Line i
+ * of the slab (i < max_lines) gets slot i of every output:
+ *   x_dev[max_lines][528] fp32   the row of a line with status ROW (matrices 1..3 minus matrix 0, the bits of
+ *                                cv_parse_tensor_text); other slots are not written;
+ *   meta_dev[max_lines][6] int64 as cv_parse_tensor_text's, relative to text_dev (ROW slots only);
+ *   status_dev[max_lines] uint8  CV_TEXT_ROW; CV_TEXT_SKIP (empty line, sequence of <= 16 bases, centre base not in
+ *                                ACGT: dropped silently); CV_TEXT_HOST: the line is not in the producer's format
+ *                                (CreateTensor.py:56) -- the device neither accepts nor rejects it, the caller parses
+ *                                it with cv_parse_tensor_text;
+ *   info_dev[4] int64            bytes consumed (whole lines, at most max_lines of them), lines, ROW lines, HOST lines.
+ * The producer's format: "<tok> <tok> <tok>" + 528 x " [-]d{1,9}[.d]", single blanks, no tab / CR / VT / FF anywhere,
+ * nothing behind the last value, at most CV_TEXT_LINE_CAP bytes in front of the newline.
+ * Everything is enqueued on `stream`; the call neither synchronises nor allocates: `workspace_dev` (256-byte aligned)
+ * holds at least cv_parse_tensor_text_dev_workspace(len, max_lines) bytes and belongs to the call until its kernels
+ * have run.  x_dev is 16-byte, meta_dev and info_dev are 8-byte aligned.                                             */
+#define CV_TEXT_SKIP 0
+#define CV_TEXT_ROW 1
+#define CV_TEXT_HOST 2
+#define CV_TEXT_LINE_CAP 8192
+#define CV_TEXT_SLAB_MAX ((int64_t)1 << 31)      /* largest `len` */
+int cv_parse_tensor_text_dev_workspace(int64_t len, int64_t max_lines, int64_t *bytes);
+int cv_parse_tensor_text_dev(const char *text_dev, int64_t len, int64_t max_lines, float *x_dev, int64_t *meta_dev,
+                             uint8_t *status_dev, int64_t *info_dev, void *workspace_dev, int64_t workspace_bytes,
+                             void *stream);
+/* Compaction behind cv_parse_tensor_text_dev (after the caller has patched the HOST slots): out_dev[r][528] =
+ * x_dev[index_dev[r]][528] for r < nrows; index_dev int64 on the device.  Enqueued on `stream`.                       */
+int cv_text_gather_rows(const float *x_dev, const int64_t *index_dev, int64_t nrows, float *out_dev, void *stream);
+
 /* c-blosc 1.x chunk codec for the 500-item blocks of the `.bin` training file
  * (utils_v2.py:159-186 blosc.pack_array(cname='lz4hc'), :189-207 blosc.unpack_array;
  * tensor2Bin.py:24-28).  Decoder: LZ4/LZ4HC streams, byte shuffle, split blocks, memcpy'd

@@ -1,5 +1,12 @@
 """Development probe: callVar.py end to end on text tensors (BASELINE.json configs[0] path at a larger size):
-rows/s for a plain and a gzip-compressed tensor file, with the share of each stage."""
+rows/s for a plain and a gzip-compressed tensor file, with the share of each stage.
+    python tools/gpu_callvar_text_probe.py [rows] [parse=device|host]
+parse=... forces one text reader (CV_TEXT_PARSE) for the whole run.  With a ladder,
+    python tools/gpu_callvar_text_probe.py ladder=1000,16384,65536,200000,1000000 [runs=5] [gzmax=1000000]
+one process alternates parse=host and parse=device at every size, plain and .gz: a warm-up run of each, then `runs`
+timed runs of each in turn (wall time of callVar.Test behind a loaded model, ending in a device synchronise), rows/s
+as median and range, and which side wins by more than the host side's own range.  kernels=ROWS times the parse
+kernels of one slab beside the forward pass of the same rows."""
 import cProfile
 import gzip
 import os
@@ -16,7 +23,128 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+def _write_rows(path, n, x, ngz):
+    from clairvoyante_amd.pileup import format_rows
+    with open(path, "wb") as fh:
+        for s in range(0, n, ngz):
+            k = min(ngz, n - s)
+            rows = format_rows("chr1", np.arange(100 + s, 100 + s + k), b"N" * 83 + b"ACGT" * ((n + 200) // 4 + 8), 0, x[:k])
+            fh.write(b"\n".join(rows) + b"\n")
+
+
+def ladder(sizes, runs, gzmax):
+    import torch
+    import common
+    from oracle import cv_oracle as O
+    from clairvoyante_amd import callVar, clairvoyante_v3, synth, utils_v2
+    tmp = tempfile.mkdtemp(prefix="cv_cvtext_")
+    ngz = min(max(sizes), 200000)
+    x = synth.make_candidates(ngz, seed=9, device="cuda").cpu().numpy()
+    x[..., 1:] += x[..., 0:1]
+    x = np.maximum(x, 0)
+    m = clairvoyante_v3.Clairvoyante(); m.init(); m.setParameters(common.bench_params(O, "full", seed=11))
+    print("rows form bytes | host rows/s median (min..max) | device rows/s median (min..max) | verdict")
+    for n in sizes:
+        txt = os.path.join(tmp, "t%d.txt" % n)
+        _write_rows(txt, n, x, ngz)
+        forms = [("plain", txt)]
+        if n <= gzmax:
+            subprocess.check_call("gzip -1 -c %s > %s.gz" % (txt, txt), shell=True)
+            forms.append(("gz", txt + ".gz"))
+        for form, fn in forms:
+            a = types.SimpleNamespace(tensor_fn=fn, chkpnt_fn=None, call_fn=os.path.join(tmp, "out.vcf"), qual=None, sampleName="S",
+                                      ref_fn=None, threads=None, showRef=False, v3=True, v2=False, slim=False)
+            rate = {"host": [], "device": []}
+            vcf = {}
+            for r in range(runs + 1):                       # run 0 of each side warms up
+                for side in ("host", "device"):
+                    os.environ["CV_TEXT_PARSE"] = side
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    callVar.Test(a, m, utils_v2)
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                    if r:
+                        rate[side].append(n / dt)
+                    else:
+                        vcf[side] = open(a.call_fn, "rb").read()
+            assert vcf["host"] == vcf["device"], "the two readers disagree"
+            h, d = np.array(rate["host"]), np.array(rate["device"])
+            wins = np.median(d) > np.median(h) + (h.max() - h.min())
+            print("%8d %-5s %11d | %.3g (%.3g..%.3g) | %.3g (%.3g..%.3g) | %s" % (
+                n, form, os.path.getsize(fn), np.median(h), h.min(), h.max(), np.median(d), d.min(), d.max(),
+                "device wins" if wins else "device does not win"), flush=True)
+            if form == "gz":
+                os.unlink(fn)
+        os.unlink(txt)
+    os.environ.pop("CV_TEXT_PARSE", None)
+    m.close()
+    import shutil
+    shutil.rmtree(tmp, ignore_errors=True)
+
+
+def kernels(n):
+    """HIP-event time of the parse kernels (and the gather) for one slab of n rows beside the forward pass of the rows"""
+    import ctypes
+    import torch
+    import common
+    from oracle import cv_oracle as O
+    from clairvoyante_amd import _lib, clairvoyante_v3, synth
+    lib = _lib.load()
+    tmp = tempfile.mkdtemp(prefix="cv_cvtext_")
+    x = synth.make_candidates(n, seed=9, device="cuda").cpu().numpy()
+    x[..., 1:] += x[..., 0:1]
+    x = np.maximum(x, 0)
+    txt = os.path.join(tmp, "k.txt")
+    _write_rows(txt, n, x, n)
+    text = open(txt, "rb").read()
+    os.unlink(txt); os.rmdir(tmp)
+    m = clairvoyante_v3.Clairvoyante(); m.init(); m.setParameters(common.bench_params(O, "full", seed=11))
+    need = ctypes.c_int64()
+    _lib.check(lib.cv_parse_tensor_text_dev_workspace(len(text), n, ctypes.byref(need)))
+    buf = torch.frombuffer(bytearray(text), dtype=torch.uint8).cuda()
+    buf = torch.cat([buf, torch.zeros(64, dtype=torch.uint8, device="cuda")])
+    xd = torch.empty((n, 528), device="cuda"); meta = torch.empty((n, 6), dtype=torch.int64, device="cuda")
+    status = torch.empty(n, dtype=torch.uint8, device="cuda"); info = torch.empty(4, dtype=torch.int64, device="cuda")
+    ws = torch.empty(need.value, dtype=torch.uint8, device="cuda")
+    idx = torch.arange(0, n, 2, dtype=torch.int64, device="cuda"); out = torch.empty((len(idx), 528), device="cuda")
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def parse():
+        _lib.check(lib.cv_parse_tensor_text_dev(ctypes.c_void_p(buf.data_ptr()), len(text), n, ctypes.c_void_p(xd.data_ptr()),
+                                                ctypes.c_void_p(meta.data_ptr()), ctypes.c_void_p(status.data_ptr()),
+                                                ctypes.c_void_p(info.data_ptr()), ctypes.c_void_p(ws.data_ptr()), need.value, st))
+
+    def gather():
+        _lib.check(lib.cv_text_gather_rows(ctypes.c_void_p(xd.data_ptr()), ctypes.c_void_p(idx.data_ptr()), len(idx),
+                                           ctypes.c_void_p(out.data_ptr()), st))
+
+    def forward():
+        m.predict_device(xd.reshape(n, 33, 4, 4))
+
+    for name, fn in (("index + parse", parse), ("gather of every second row", gather), ("forward pass", forward)):
+        ms = []
+        for r in range(8):
+            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record(); torch.cuda.synchronize()
+            if r >= 3:
+                ms.append(e0.elapsed_time(e1))
+        print("%d rows, %.1f MB of text: %-28s %.3f ms median (%.3f..%.3f)" % (n, len(text) / 1e6, name, np.median(ms), min(ms), max(ms)))
+    assert tuple(info.cpu().numpy()) == (len(text), n, n, 0)
+    m.close()
+
+
 def main():
+    opts = dict(a.split("=", 1) for a in sys.argv[1:] if "=" in a)
+    sys.argv = [a for a in sys.argv if "=" not in a]
+    if "parse" in opts:
+        os.environ["CV_TEXT_PARSE"] = opts["parse"]
+    if "kernels" in opts:
+        kernels(int(opts["kernels"]))
+    if "ladder" in opts:
+        ladder([int(v) for v in opts["ladder"].split(",")], int(opts.get("runs", 5)), int(opts.get("gzmax", 1000000)))
+    if "kernels" in opts or "ladder" in opts:
+        return
     import common
     from oracle import cv_oracle as O
     from clairvoyante_amd import callVar, clairvoyante_v3, synth
