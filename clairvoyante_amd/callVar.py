@@ -17,8 +17,6 @@ import os
 import sys
 import time
 from math import log
-from queue import Queue
-from threading import Thread
 
 import numpy as np
 
@@ -313,12 +311,48 @@ class ResultFetcher(object):
             return call, qual, rows_h.numpy(), xrow
 
 
+def called_batches(args, m, items):
+    """The call loop: `items` are (key, num, X, pos) batches -- X a host array ([num,33,4,4] fp32, copied to the
+    device here) or rows that are in HBM already (a torch tensor) -- and (key, None, None, None) end markers.  Yields
+    (key, VCF text of the batch as bytes) ONE BATCH BEHIND what it has enqueued: per batch the H2D copy (or the device
+    rows), predict_device, cv_call_postproc and an event go to the GPU, then the decisions of the batch before come to
+    the host on the fetcher's side stream and are formatted while the GPU works.  End markers pass through in order,
+    as (key, None), behind the text of the batches in front of them.  Closes `items` when it ends, however it ends."""
+    import torch
+    try:
+        with torch.cuda.device(m.device):
+            fetcher = ResultFetcher(m)
+            pending = None                   # (key, num, X, pos, call_dev, qual_dev, event) of the batch the GPU works on
+
+            def finish(key, num, X, pos, call, qual, ev):
+                if torch.is_tensor(X):       # rows on the device: only those that give a record come to the host
+                    hcall, hqual, rows, xrow = fetcher.fetch(ev, call, qual, X, bool(args.showRef))
+                    return key, format_records(args, num, rows, pos, hcall, hqual, xrow)
+                hcall, hqual = fetcher.fetch(ev, call, qual)
+                return key, format_records(args, num, X, pos, hcall, hqual)
+
+            for key, num, X, pos in items:
+                nxt = None
+                if num:
+                    xd = X if torch.is_tensor(X) else torch.from_numpy(X).to(m.device, non_blocking=True)
+                    call, qual = predict_and_reduce(m, xd)
+                    nxt = (key, num, X, pos, call, qual, fetcher.mark())
+                if pending is not None:      # format batch k while the GPU works on batch k + 1
+                    yield finish(*pending)
+                pending = nxt
+                if num is None:              # end of `key` (its last batch was formatted just above)
+                    yield key, None
+            if pending is not None:
+                yield finish(*pending)
+    finally:
+        items.close()
+
+
 def CallFromDevice(args, m, call_fh, X_dev, pos, batch=65536):
     """VCF records for tensors that are already in HBM (callVarBam's fused path): X_dev [n,33,4,4] with matrices 1..3
     minus matrix 0; pos: utils_v2.PosBatch (or a function i -> "chrom:coord:seq") for the n rows.  Batch k's decisions
     and the rows that produce a record (non-REF calls, or all with --showRef) come to the host on a side stream and
-    are formatted by the host threads while the GPU runs batch k+1."""
-    import torch
+    are formatted by the host threads while the GPU runs batch k+1 (called_batches)."""
     from .utils_v2 import PosBatch
     n = X_dev.shape[0]
     if callable(pos):
@@ -328,24 +362,9 @@ def CallFromDevice(args, m, call_fh, X_dev, pos, batch=65536):
         pos = PosBatch.from_strings(list(pos))
         pieces = pos.pieces()
     _start, _rows, buf, meta = pieces[0]
-    with torch.cuda.device(m.device):
-        fetcher = ResultFetcher(m)
-        pending = None
-
-        def finish(p):
-            s, xd, call_d, qual_d, ev = p
-            call, qual, rows, xrow = fetcher.fetch(ev, call_d, qual_d, xd, bool(args.showRef))
-            OutputFromDevice(args, call_fh, call.shape[0], rows, PosBatch(buf, meta[s:s + call.shape[0]]), call, qual, xrow)
-
-        for s in range(0, n, batch):
-            xd = X_dev[s:s + batch].contiguous()
-            call_d, qual_d = predict_and_reduce(m, xd)
-            nxt = (s, xd, call_d, qual_d, fetcher.mark())
-            if pending is not None:
-                finish(pending)
-            pending = nxt
-        if pending is not None:
-            finish(pending)
+    slices = ((0, min(batch, n - s), X_dev[s:s + batch].contiguous(), PosBatch(buf, meta[s:s + batch])) for s in range(0, n, batch))
+    for _key, text in called_batches(args, m, slices):
+        call_fh.write(text.decode("ascii"))
 
 
 def Run(args):
@@ -432,8 +451,6 @@ def TestSharded(args, m, utils, rank, ws):
     frag_fn = "%s.rank%d" % (args.call_fn, rank)
     frag = open(frag_fn, "wb")
     index = []
-    fetcher = ResultFetcher(m)
-    q_in = Queue(maxsize=4)
 
     # "--tensor_fn a.gz,b.gz,...": one file per chunk, file k -> rank k % ws (each rank inflates only its own files);
     # a single file: its LINES are split block-cyclically (every rank inflates the whole stream -- the job is then
@@ -445,18 +462,14 @@ def TestSharded(args, m, utils, rank, ws):
                         "Give --tensor_fn a comma-separated list (one file per chunk of the genome; file k goes to rank k mod N) "
                         "or uncompressed text to scale." % ws)
 
-    def reader():
-        try:
-            if len(files) > 1:       # this rank's files, compressed ones several at a time, batches as they complete
-                for item in utils.GetTensorFiles(files, max(param.predictBatchSize, 16384), rank, ws, ordered=False):
-                    q_in.put(item)
-            else:                    # one batch per owned block of lines
-                for block, num, X, pos in utils.GetTensorBlocks(files[0], SHARD_BLOCK_LINES, rank, ws):
-                    q_in.put((block, num, X, pos))
-                    q_in.put((block, None, None, None))
-        except BaseException as e:
-            q_in.put(e)
-        q_in.put(None)
+    def batches():
+        if len(files) > 1:           # this rank's files, compressed ones several at a time, batches as they complete
+            for item in utils.GetTensorFiles(files, max(param.predictBatchSize, 16384), rank, ws, ordered=False):
+                yield item
+        else:                        # one batch per owned block of lines
+            for block, num, X, pos in utils.GetTensorBlocks(files[0], SHARD_BLOCK_LINES, rank, ws):
+                yield block, num, X, pos
+                yield block, None, None, None
 
     # the fragment holds this rank's blocks / files in ascending order (merge_fragments walks k = 0, 1, 2, ...): text that
     # is ready before its turn waits in memory (_OrderedWriter); one index entry per block that was seen
@@ -471,32 +484,12 @@ def TestSharded(args, m, utils, rank, ws):
 
     out = _OrderedWriter(write, first=rank, step=ws)
 
-    rt = Thread(target=reader, daemon=True)
-    rt.start()
-    pending = None
     failure = None
     try:
-        with torch.cuda.device(m.device):
-            while True:
-                item = q_in.get()
-                if isinstance(item, BaseException):
-                    raise item
-                nxt = None
-                if item is not None and item[1] is not None and item[1] > 0:
-                    block, num, X, pos = item
-                    xd = torch.from_numpy(X).to(m.device, non_blocking=True)
-                    call, qual = predict_and_reduce(m, xd)
-                    nxt = (block, num, X, pos, call, qual, fetcher.mark())
-                if pending is not None:
-                    pblock, pnum, pX, ppos, pcall, pqual, pev = pending
-                    hcall, hqual = fetcher.fetch(pev, pcall, pqual)
-                    out.add(pblock, format_records(args, pnum, pX, ppos, hcall, hqual))
-                pending = nxt
-                if item is not None and item[1] is None:      # block / file complete (its last batch was formatted above)
-                    seen.add(item[0])
-                    out.end(item[0])
-                if item is None:
-                    break
+        for k, text in called_batches(args, m, utils._read_ahead(batches(), 4)):
+            if text is None:             # block / file complete
+                seen.add(k)
+            out.put(k, text)
         # every block this rank owns gets an index entry, also one without records (merge_fragments counts them)
         have = dict(index)
         index = [(k, have.get(k, 0)) for k in sorted(seen)]
@@ -543,6 +536,13 @@ class _OrderedWriter(object):
         self.write, self.next, self.step = write, first, step
         self.held, self.done = {}, set()
 
+    def put(self, k, text):
+        """what called_batches yields: the text of a batch of file k, or None behind its last batch"""
+        if text is None:
+            self.end(k)
+        else:
+            self.add(k, text)
+
     def add(self, k, text):
         if not text:
             return
@@ -588,8 +588,6 @@ def Test(args, m, utils):
     """callVar.py:180-216 re-cut for the GPU: reader thread(s) (inflate, parse) || GPU (predict + per-candidate
     reductions) || writer (format); the records of a file stay in the order of its rows, files in list order, so the VCF
     is the reference's record for record."""
-    import torch
-    from . import _lib
     call_fh = open(args.call_fn, "w")
     PrintVCFHeader(args, call_fh)
     logging.info("Calling variants ...")
@@ -600,54 +598,23 @@ def Test(args, m, utils):
     on_device = len(files) == 1 and parses_on_device(files[0])
     mapped = on_device or utils._map_plain_text(files[0]) is not None      # (either way the rows arrive at millions per second)
     batch = getattr(args, "batch_size", None) or (65536 if mapped else max(param.predictBatchSize, 16384))
-    q_in = Queue(maxsize=2 if mapped else 4)
 
-    def reader():
-        try:
-            if len(files) > 1:                   # a list of files: compressed ones are inflated several at a time and their
-                for item in utils.GetTensorFiles(files, batch, 0, 1, ordered=False):     # batches taken as they complete
-                    q_in.put(item)
-            else:
-                side = "device" if on_device else "host"
-                utils.text_parse_counts[side] += 1
-                logging.info("Text tensors are parsed on the %s" % side)
-                batches = utils.GetTensorDevice(files[0], batch, m.device) if on_device else utils.GetTensor(files[0], batch)
-                for _end, c, X, pos in batches:
-                    q_in.put((0, c, X, pos))
-                q_in.put((0, None, None, None))
-        except BaseException as e:   # surfaced on the consumer side (the reference loses it)
-            q_in.put(e)
-        q_in.put(None)
+    def batches():
+        if len(files) > 1:                       # a list of files: compressed ones are inflated several at a time and their
+            for item in utils.GetTensorFiles(files, batch, 0, 1, ordered=False):         # batches taken as they complete
+                yield item
+        else:
+            side = "device" if on_device else "host"
+            utils.text_parse_counts[side] += 1
+            logging.info("Text tensors are parsed on the %s" % side)
+            for _end, c, X, pos in (utils.GetTensorDevice(files[0], batch, m.device) if on_device else utils.GetTensor(files[0], batch)):
+                yield 0, c, X, pos
+            yield 0, None, None, None
 
-    rt = Thread(target=reader, daemon=True)
-    rt.start()
+    # the reader(s) run in a thread of their own; an exception there surfaces here (the reference loses it)
     out = _OrderedWriter(lambda _k, text: call_fh.write(text.decode("ascii")))
-    pending = None                   # (file, num, X, pos, call_dev, qual_dev, event)
-    with torch.cuda.device(m.device):
-        fetcher = ResultFetcher(m)
-        while True:
-            item = q_in.get()
-            if isinstance(item, BaseException):
-                raise item
-            nxt = None
-            if item is not None and item[1] is not None and item[1] > 0:
-                k, num, X, pos = item
-                xd = X if torch.is_tensor(X) else torch.from_numpy(X).to(m.device, non_blocking=True)
-                call, qual = predict_and_reduce(m, xd)
-                nxt = (k, num, X, pos, call, qual, fetcher.mark())
-            if pending is not None:      # format batch j while the GPU works on batch j+1
-                pk, pnum, pX, ppos, pcall, pqual, pev = pending
-                if torch.is_tensor(pX):  # rows parsed on the device: only those that give a record come to the host
-                    hcall, hqual, rows, xrow = fetcher.fetch(pev, pcall, pqual, pX, bool(args.showRef))
-                    out.add(pk, format_records(args, pnum, rows, ppos, hcall, hqual, xrow))
-                else:
-                    hcall, hqual = fetcher.fetch(pev, pcall, pqual)
-                    out.add(pk, format_records(args, pnum, pX, ppos, hcall, hqual))
-            pending = nxt
-            if item is not None and item[1] is None:      # end of file k (its last batch was formatted just above)
-                out.end(item[0])
-            if item is None:
-                break
+    for k, text in called_batches(args, m, utils._read_ahead(batches(), 2 if mapped else 4)):
+        out.put(k, text)
     call_fh.close()
     logging.info("Total time elapsed: %.2f s" % (time.time() - predictStart))
 

@@ -20,7 +20,8 @@ from . import _lib
 from . import param
 
 base2num = dict(zip("ACGT", (0, 1, 2, 3)))
-_NV = (2 * param.flankingBaseNum + 1) * 4 * param.matrixNum
+_SHAPE = (2 * param.flankingBaseNum + 1, 4, param.matrixNum)      # of one candidate's tensor
+_NV = _SHAPE[0] * _SHAPE[1] * _SHAPE[2]
 
 
 def SetupEnv():
@@ -227,9 +228,22 @@ def _open_tensor_stream(tensor_fn):
     if tensor_fn != "PIPE":
         if os.environ.get("CV_GZIP") != "external" and os.path.isfile(tensor_fn):
             return None, _GzipOrPipe(tensor_fn)
-        f = subprocess.Popen(shlex.split("gzip -fdc %s" % (tensor_fn)), stdout=subprocess.PIPE, bufsize=8388608)
+        f = _gzip_pipe(tensor_fn)
         return f, f.stdout
     return None, sys.stdin.buffer
+
+
+def _gzip_pipe(fn):
+    return subprocess.Popen(shlex.split("gzip -fdc %s" % (fn)), stdout=subprocess.PIPE, bufsize=8388608)
+
+
+def _end_gzip_pipe(proc, fn):
+    """closes the pipe of a `gzip -fdc` child process and waits for it.  gzip: 1 = error (missing / unreadable / corrupt
+    file), 2 = warning.  The reference reads on with whatever arrived (utils_v2.py:25 never looks at the exit status):
+    a truncated call set"""
+    proc.stdout.close()
+    if proc.wait() == 1:
+        raise _lib.CvError("gzip -fdc %s failed (exit status 1): the tensor stream is incomplete" % fn)
 
 
 class _GzipOrPipe(object):
@@ -250,7 +264,7 @@ class _GzipOrPipe(object):
         if self.g is not None:
             self.g.close()
             self.g = None
-        self.proc = subprocess.Popen(shlex.split("gzip -fdc %s" % (self.fn)), stdout=subprocess.PIPE, bufsize=8388608)
+        self.proc = _gzip_pipe(self.fn)
         skip = self.out
         while skip > 0:
             c = self.proc.stdout.read(min(skip, 1 << 24))
@@ -275,67 +289,50 @@ class _GzipOrPipe(object):
             self.g.close()
             self.g = None
         if self.proc is not None:
-            self.proc.stdout.close()
-            rc = self.proc.wait()
-            self.proc = None
-            if rc == 1:
-                raise _lib.CvError("gzip -fdc %s failed (exit status 1): the tensor stream is incomplete" % self.fn)
-
-
-def _close_tensor_stream(proc, fo, tensor_fn):
-    if proc is not None:
-        fo.close()
-        if proc.wait() == 1:          # gzip: 1 = error (missing / unreadable / corrupt file), 2 = warning.  The reference
-            # reads on with whatever arrived (utils_v2.py:25 never looks at the exit status): a truncated call set
-            raise _lib.CvError("gzip -fdc %s failed (exit status 1): the tensor stream is incomplete" % tensor_fn)
-    elif fo is not sys.stdin.buffer:
-        fo.close()
+            proc, self.proc = self.proc, None
+            _end_gzip_pipe(proc, self.fn)
 
 
 def _close_quietly_unless(done, proc, fo, tensor_fn):
-    """the `finally` of the stream generators: a generator that ran to its end closes its stream the loud way (a failed
+    """the `finally` of _text_spans: a generator that ran to its end closes its stream the loud way (a failed
     `gzip -fdc` raises); one that is dropped early -- the consumer stopped, an error is already on its way up -- still
     closes it (the child process is waited for, the window buffer and the map are released) but adds no second error"""
-    if done:
-        _close_tensor_stream(proc, fo, tensor_fn)
-        return
     try:
-        _close_tensor_stream(proc, fo, tensor_fn)
+        if proc is not None:
+            _end_gzip_pipe(proc, tensor_fn)
+        elif fo is not sys.stdin.buffer:
+            fo.close()
     except Exception:
-        pass
+        if done:
+            raise
 
 
-def owned_line_blocks(fo, rank, ws, block_lines):
-    """Split a text stream into blocks of `block_lines` lines and yield (block index, bytes) for the blocks
-    rank `rank` of `ws` owns (block k belongs to rank k % ws): the sharding of callVar under torchrun.  Every rank
-    reads (decompresses) the whole stream but only parses its own blocks; a last line without newline gets one."""
+def owned_line_blocks(spans, rank, ws, block_lines):
+    """Cut spans of whole lines (_text_spans) into blocks of `block_lines` lines and yield (block index, uint8 array) for
+    the blocks rank `rank` of `ws` owns (block k belongs to rank k % ws): the sharding of callVar under torchrun.  Every
+    rank reads (decompresses) the whole input but only parses its own blocks."""
     block, have = 0, 0                      # current block index, lines of it seen so far
     parts = []                              # pieces of the current block if it is ours
-    while True:
-        chunk = fo.read(1 << 24)
-        if not chunk:
-            break
-        nl = np.flatnonzero(np.frombuffer(chunk, dtype=np.uint8) == 10)
-        start, used = 0, 0                  # byte offset / newlines of the chunk consumed
+    for span in spans:
+        nl = np.flatnonzero(span == 10)
+        start, used = 0, 0                  # byte offset / newlines of the span consumed
         while used < len(nl):
             need = block_lines - have
-            if len(nl) - used >= need:      # the block ends inside this chunk
+            if len(nl) - used >= need:      # the block ends inside this span
                 end = int(nl[used + need - 1]) + 1
                 if block % ws == rank:
-                    parts.append(chunk[start:end])
-                    yield block, b"".join(parts)
+                    parts.append(span[start:end])
+                    yield block, parts[0] if len(parts) == 1 else np.concatenate(parts)
                 parts = []
                 block += 1; have = 0
                 start = end; used += need
             else:
                 have += len(nl) - used
                 used = len(nl)
-        if start < len(chunk) and block % ws == rank:
-            parts.append(chunk[start:])
-    if parts or have:
-        tail = b"".join(parts)
-        if block % ws == rank and tail:
-            yield block, tail if tail.endswith(b"\n") else tail + b"\n"
+        if start < len(span) and block % ws == rank:
+            parts.append(span[start:])
+    if parts:
+        yield block, parts[0] if len(parts) == 1 else np.concatenate(parts)
 
 
 def GetTensorBlocks(tensor_fn, block_lines, rank, ws):
@@ -343,33 +340,14 @@ def GetTensorBlocks(tensor_fn, block_lines, rank, ws):
     `block_lines` input lines this rank owns -- one batch per block, rows as GetTensor makes them."""
     if tensor_fn == "PIPE":
         raise ValueError("--tensor_fn PIPE cannot be sharded over ranks: give the tensor file")
-    lib = _lib.load()
-    proc, fo = _open_tensor_stream(tensor_fn)
-    consumed = ctypes.c_int64(); nrows = ctypes.c_int64(); nbad = ctypes.c_int64()
-    done = False
+    batch = _RowBatch(block_lines)
+    spans = _text_spans(tensor_fn, 1 << 24)
     try:
-        for block, data in owned_line_blocks(fo, rank, ws, block_lines):
-            rows = _pinned.empty((block_lines, _NV), np.float32)
-            meta = np.empty((block_lines, 6), dtype=np.int64)
-            c, off, bufs = 0, 0, []
-            while off < len(data):
-                view = data[off:] if off else data
-                _lib.check(lib.cv_parse_tensor_text(view, len(view), block_lines - c,
-                                                    rows[c:].ctypes.data_as(ctypes.c_void_p),
-                                                    meta[c:].ctypes.data_as(ctypes.c_void_p),
-                                                    ctypes.byref(consumed), ctypes.byref(nrows), ctypes.byref(nbad)))
-                if nbad.value:
-                    print("UnpackATensorRecord Failure (%d malformed rows skipped)" % nbad.value, file=sys.stderr)
-                if nrows.value:
-                    bufs.append((view, meta[c:c + nrows.value].copy()))
-                c += nrows.value
-                off += consumed.value
-                if consumed.value == 0:
-                    break
-            yield block, c, rows[:c].reshape((c, 2 * param.flankingBaseNum + 1, 4, param.matrixNum)), _join_pos(bufs)
-        done = True
+        for block, text in owned_line_blocks(spans, rank, ws, block_lines):
+            full = next(batch.fill(text), None)              # (a block whose every line is a row fills the batch)
+            yield (block,) + (full or batch.take())
     finally:
-        _close_quietly_unless(done, proc, fo, tensor_fn)
+        spans.close()
 
 
 def _default_readers(nfiles):
@@ -394,7 +372,7 @@ def GetTensorFiles(files, num, rank, ws, readers=None, depth=2, ordered=True):
                      all readers stay busy, `readers` x the rate of one file.
     An error in a reader is raised in the consumer."""
     import threading
-    from queue import Queue, Full
+    from queue import Queue
     owned = [(k, fn) for k, fn in enumerate(files) if k % ws == rank]
     if readers is None:
         compressed = any(is_compressed(fn) for _k, fn in owned)       # (magic bytes only: nothing is mapped here)
@@ -410,25 +388,16 @@ def GetTensorFiles(files, num, rank, ws, readers=None, depth=2, ordered=True):
     slots = threading.Semaphore(readers)
     stop = threading.Event()
 
-    def put(q, item):
-        while not stop.is_set():
-            try:
-                q.put(item, timeout=0.2)
-                return True
-            except Full:                                   # the consumer is busy elsewhere: look at `stop` and wait on
-                continue
-        return False
-
     def read(i):
         q = queues[i]
         gen = GetTensor(owned[i][1], num, log=False)
         try:
             for _end, c, X, pos in gen:
-                if not put(q, (i, c, X, pos)):
+                if not _put_unless(stop, q, (i, c, X, pos)):
                     return
-            put(q, (i, None, None, None))
+            _put_unless(stop, q, (i, None, None, None))
         except BaseException as e:                         # surfaced in the consumer
-            put(q, (i, e, None, None))
+            _put_unless(stop, q, (i, e, None, None))
         finally:
             gen.close()                                    # a reader told to stop still closes its stream (child process, map)
             slots.release()
@@ -507,129 +476,95 @@ def _map_plain_text(tensor_fn):
     return np.frombuffer(mm, dtype=np.uint8)
 
 
-def _get_tensor_mapped(data, num, log):
-    """GetTensor over a memory-mapped plain-text file: the parser threads read the lines where the page cache holds them
-    (no pipe, no copies; cv_parse_tensor_text sizes its own window), the position fields of a batch stay views of the map."""
+def _text_parser():
+    """-> parse(address, length, max_rows, rows, meta) -> (bytes consumed, rows written, malformed lines): the call of
+    cv_parse_tensor_text (csrc/cv_hostio.cpp), its out-parameters allocated once"""
     lib = _lib.load()
-    n = int(data.shape[0])
-    base = data.ctypes.data
-    shape = (2 * param.flankingBaseNum + 1, 4, param.matrixNum)
     consumed = ctypes.c_int64(); nrows = ctypes.c_int64(); nbad = ctypes.c_int64()
-    total, off = 0, 0
-    tail = None                      # a last line without newline: parsed from a copy that has one
-    if data[n - 1] != 10:
-        last_nl = n - 1
-        while last_nl >= 0 and data[last_nl] != 10:
-            last_nl -= 1
-        tail = bytes(data[last_nl + 1:]) + b"\n"
-        n = last_nl + 1
-    rows = _pinned.empty((num, _NV), np.float32)
-    meta = np.empty((num, 6), dtype=np.int64)
-    c, bufs = 0, []
 
-    def parse(ptr, length, view):
-        nonlocal c
-        _lib.check(lib.cv_parse_tensor_text(ctypes.c_void_p(ptr), length, num - c,
-                                            rows[c:].ctypes.data_as(ctypes.c_void_p), meta[c:].ctypes.data_as(ctypes.c_void_p),
+    def parse(address, length, max_rows, rows, meta):
+        _lib.check(lib.cv_parse_tensor_text(ctypes.c_void_p(address), length, max_rows,
+                                            rows.ctypes.data_as(ctypes.c_void_p), meta.ctypes.data_as(ctypes.c_void_p),
                                             ctypes.byref(consumed), ctypes.byref(nrows), ctypes.byref(nbad)))
-        if nbad.value:
-            print("UnpackATensorRecord Failure (%d malformed rows skipped)" % nbad.value, file=sys.stderr)
-        if nrows.value:
-            bufs.append((view(consumed.value), meta[c:c + nrows.value].copy()))
-        c += nrows.value
-        return consumed.value
+        return consumed.value, nrows.value, nbad.value
+    return parse
 
-    while off < n or tail is not None:
-        if off < n:
-            o = off
-            used = parse(base + off, n - off, lambda k: data[o:o + k])
+
+def _report_malformed(bad):
+    if bad:
+        print("UnpackATensorRecord Failure (%d malformed rows skipped)" % bad, file=sys.stderr)
+
+
+class _RowBatch(object):
+    """The batch of up to `cap` rows that is being filled from spans of whole lines (_text_spans).  Every batch gets
+    fresh `rows` / `meta` arrays, allocated when its first line arrives: the consumer still holds the batch before
+    (callVar formats batch k while batch k + 1 is filled), and no buffer is pinned behind the last one.  The position
+    fields of a batch stay views of the spans they were found in."""
+
+    def __init__(self, cap):
+        self.cap, self.parse, self.rows = cap, _text_parser(), None
+
+    def _start(self):
+        self.rows = _pinned.empty((self.cap, _NV), np.float32)      # page-locked when a GPU is present: the consumer copies it to HBM
+        self.meta = np.empty((self.cap, 6), dtype=np.int64)
+        self.c, self.bufs = 0, []           # rows so far; their (bytes, meta rows) pieces
+
+    def fill(self, span):
+        """parses `span`; generator of the (c, X, pos) batches it completes -- rows behind the last full batch wait for
+        the next span or for take()"""
+        off = 0
+        while off < len(span):
+            if self.rows is None:
+                self._start()
+            c, text = self.c, span[off:] if off else span
+            used, n, bad = self.parse(text.ctypes.data, len(text), self.cap - c, self.rows[c:], self.meta[c:])
+            _report_malformed(bad)
+            if n:
+                self.bufs.append((text[:used], self.meta[c:c + n].copy()))
+            self.c += n
             off += used
-            if used == 0:
-                off = n
-        else:
-            keep = np.frombuffer(tail, dtype=np.uint8)
-            parse(keep.ctypes.data, len(tail), lambda k: keep[:k])
-            tail = None
-        if c == num:
-            total += c
-            if log:
-                print("Processed %d tensors" % total, file=sys.stderr)
-            yield 0, c, rows.reshape((num,) + shape), _join_pos(bufs)
-            rows = _pinned.empty((num, _NV), np.float32)
-            meta = np.empty((num, 6), dtype=np.int64)
-            c, bufs = 0, []
-    total += c
-    if log:
-        print("Processed %d tensors" % total, file=sys.stderr)
-    yield 1, c, rows[:c].reshape((c,) + shape), _join_pos(bufs)
+            if self.c == self.cap:
+                yield self.take()
+            elif used == 0:                 # (whole lines: only a line longer than the parser takes, which is no row)
+                break
+
+    def take(self):
+        """-> (c, X, pos) of the rows so far (possibly none): X a view of the `cap`-row buffer"""
+        if self.rows is None:
+            self._start()
+        c, rows = self.c, self.rows
+        self.rows = None
+        return c, rows[:c].reshape((c,) + _SHAPE), PosBatch(pieces=self.bufs)
+
+
+def _flagged(log):
+    """-> done(endFlag, (c, X, pos)) -> (endFlag, c, X, pos), which counts the rows and reports them as utils_v2.py:57 does"""
+    total = 0
+
+    def done(flag, batch):
+        nonlocal total
+        total += batch[0]
+        if log:
+            print("Processed %d tensors" % total, file=sys.stderr)
+        return (flag,) + batch
+    return done
 
 
 def GetTensor(tensor_fn, num, log=True):
     """Generator over batches of `num` candidates: yields (endFlag, c, X, pos) exactly like
     utils_v2.py:23-59 -- X [c,33,4,4] fp32 with matrices 1..3 minus matrix 0, rows whose
-    centre base is not ACGT dropped, a final (possibly empty) batch with endFlag 1."""
-    mapped = _map_plain_text(tensor_fn)
-    if mapped is not None:
-        for item in _get_tensor_mapped(mapped, num, log):
-            yield item
-        return
-    lib = _lib.load()
-    proc, fo = _open_tensor_stream(tensor_fn)
-    total = 0
-    pending = b""
-    rows = _pinned.empty((num, _NV), np.float32)      # page-locked when a GPU is present: the consumer copies it to HBM
-    meta = np.empty((num, 6), dtype=np.int64)
-    c = 0
-    bufs = []          # (bytes, meta rows) pieces of the batch being filled
-    consumed = ctypes.c_int64(); nrows = ctypes.c_int64(); nbad = ctypes.c_int64()
-    eof = False
-    done = False
+    centre base is not ACGT dropped, a final (possibly empty) batch with endFlag 1.  Over a memory-mapped plain-text
+    file the parser threads read the lines where the page cache holds them (no pipe, no copies; cv_parse_tensor_text
+    sees the whole rest of the file and sizes its own window); everything else arrives in 16 MiB reads of the stream."""
+    batch, done = _RowBatch(num), _flagged(log)
+    spans = _text_spans(tensor_fn)
     try:
-        while True:
-            chunk = fo.read(1 << 24) if not eof else b""
-            if not chunk:
-                eof = True
-                if pending and not pending.endswith(b"\n"):
-                    pending += b"\n"
-            data = pending + chunk if pending else chunk
-            arr = np.frombuffer(data, dtype=np.uint8)          # addresses into the bytes object: no slice copies
-            off = 0
-            while off < len(data):
-                _lib.check(lib.cv_parse_tensor_text(ctypes.c_void_p(arr.ctypes.data + off), len(data) - off, num - c,
-                                                    rows[c:].ctypes.data_as(ctypes.c_void_p),
-                                                    meta[c:].ctypes.data_as(ctypes.c_void_p),
-                                                    ctypes.byref(consumed), ctypes.byref(nrows), ctypes.byref(nbad)))
-                if nbad.value:
-                    print("UnpackATensorRecord Failure (%d malformed rows skipped)" % nbad.value, file=sys.stderr)
-                if nrows.value:
-                    bufs.append((arr[off:off + consumed.value], meta[c:c + nrows.value].copy()))
-                c += nrows.value
-                off += consumed.value
-                if c == num:
-                    total += c
-                    if log:
-                        print("Processed %d tensors" % total, file=sys.stderr)
-                    yield 0, c, rows.reshape((num, 2 * param.flankingBaseNum + 1, 4, param.matrixNum)), _join_pos(bufs)
-                    rows = _pinned.empty((num, _NV), np.float32)      # page-locked when a GPU is present: the consumer copies it to HBM
-                    meta = np.empty((num, 6), dtype=np.int64)
-                    c = 0
-                    bufs = []
-                elif consumed.value == 0:
-                    break
-            pending = data[off:]
-            if eof:
-                break
-        done = True
+        for span in spans:
+            for full in batch.fill(span):
+                yield done(0, full)
     finally:
-        _close_quietly_unless(done, proc, fo, tensor_fn)
-    total += c
-    if log:
-        print("Processed %d tensors" % total, file=sys.stderr)
-    yield 1, c, rows[:c].reshape((c, 2 * param.flankingBaseNum + 1, 4, param.matrixNum)), _join_pos(bufs)
-
-
-def _join_pos(bufs):
-    return PosBatch(pieces=bufs)
+        spans.close()                       # closed early: the stream's child process is waited for here and now
+    yield done(1, batch.take())
 
 
 # ---- the text reader on the device (csrc/cv_textparse.hip) -------------------------------------------------------------
@@ -669,33 +604,41 @@ def _slab_bytes(first_line, num):
     return min(max(num, 1) * max(first_line, 64), _PinnedPool.MAX_BYTES)     # (what a page-locked staging buffer holds)
 
 
-def _text_slabs(tensor_fn, num):
-    """The input cut into slabs of whole lines, as uint8 arrays that end in '\n': views of the memory-mapped plain file,
-    or pieces of the inflated stream (`_GzipFile` / the reference's `gzip -fdc` pipe) with the partial last line of one
-    read carried into the next, as GetTensor carries `pending`.  A last line without newline gets one."""
+def _text_spans(tensor_fn, want_bytes=None):
+    """The input as spans of whole lines: uint8 arrays that end in '\n'.  The one place that turns a tensor file into
+    lines, and the only one that opens and closes its stream.
+      a plain regular file (_map_plain_text): views of the memory map, no copy of the text;
+      everything else (.gz, PIPE, FIFOs, CV_TEXT=stream): reads of the inflated stream (`_GzipFile` / the reference's
+        `gzip -fdc` pipe), the text behind the last newline of a read carried into the next span, the pieces of a span
+        joined ONCE.
+    A last line without newline gets one: on the map that line alone is copied and follows as a span of its own.
+    want_bytes: None = as the source gives them (the whole map -- cv_parse_tensor_text sizes its own window --, 16 MiB
+    of the stream); a number of bytes; or a function of the first line's length (GetTensorDevice: `num` rows' worth).
+    A span is cut at the last newline inside want_bytes, a line longer than that is a span of its own."""
+    def size_for(first_line):
+        return want_bytes(first_line) if callable(want_bytes) else want_bytes
+
     data = _map_plain_text(tensor_fn)
     if data is not None:
-        n, off = len(data), 0
-        nl = _first_newline(data, 0)
-        size = _slab_bytes((nl if nl >= 0 else n) + 1, num)
+        n, off = _last_newline(data) + 1, 0          # the whole lines end here
+        size = size_for(_first_newline(data, 0) + 1) if want_bytes is not None and n else n
         while off < n:
             end = min(off + size, n)
             if end < n:
                 k = _last_newline(data[off:end])
-                if k < 0:                                # one line longer than a slab: up to its end
-                    k = _first_newline(data, end)
-                    k = k - off if k >= 0 else -1
-                end = off + k + 1 if k >= 0 else n
-            if data[end - 1] != 10:                      # (only the end of the file)
-                yield np.frombuffer(bytes(data[off:end]) + b"\n", dtype=np.uint8)
-            else:
-                yield data[off:end]
+                if k < 0:                                # one line longer than a span: up to its end
+                    k = _first_newline(data, end) - off
+                end = off + k + 1
+            yield data[off:end]
             off = end
+        if n < len(data):
+            yield np.frombuffer(bytes(data[n:]) + b"\n", dtype=np.uint8)
         return
     proc, fo = _open_tensor_stream(tensor_fn)
     done = False
     try:
-        parts, have, size = [], 0, None          # pieces read since the last slab (joined ONCE per slab) and their bytes
+        parts, have = [], 0                      # pieces read since the last span and their bytes
+        size = None if callable(want_bytes) else (want_bytes or 1 << 24)
         while True:
             chunk = fo.read((1 << 16) if size is None else max(size - have, 1 << 12))
             if chunk:
@@ -704,7 +647,7 @@ def _text_slabs(tensor_fn, num):
                     nl = chunk.find(b"\n")
                     if nl < 0:
                         continue
-                    size = _slab_bytes(have - len(chunk) + nl + 1, num)
+                    size = size_for(have - len(chunk) + nl + 1)
                 if have < size or (b"\n" not in chunk and not any(b"\n" in c for c in parts)):
                     continue
             piece = parts[0] if len(parts) == 1 else b"".join(parts)
@@ -721,31 +664,37 @@ def _text_slabs(tensor_fn, num):
         _close_quietly_unless(done, proc, fo, tensor_fn)
 
 
+def _put_unless(stop, q, item):
+    """q.put(item) that gives up once `stop` is set (-> False): a producer whose consumer is busy elsewhere looks at
+    `stop` and waits on; one whose consumer has left does not block on a full queue for ever"""
+    import queue
+    while not stop.is_set():
+        try:
+            q.put(item, timeout=0.1)
+            return True
+        except queue.Full:
+            pass
+    return False
+
+
 def _read_ahead(items, depth):
     """the generator `items` run in a thread of its own, at most `depth` items ahead of the consumer; an exception of
-    the generator is raised where the consumer would have got the item"""
+    the generator is raised where the consumer would have got the item.  When the consumer leaves, the thread is told
+    to stop and waited for, but not for ever: a reader that sits in a read of standard input which never returns is
+    left behind (a daemon thread), so that an error exit stays an exit."""
     import queue
     import threading
     q, stop = queue.Queue(maxsize=depth), threading.Event()
 
-    def put(item):
-        while not stop.is_set():
-            try:
-                q.put(item, timeout=0.1)
-                return True
-            except queue.Full:
-                pass
-        return False
-
     def run():
         try:
             for item in items:
-                if not put((item, None)):
+                if not _put_unless(stop, q, (item, None)):
                     break
             else:
-                put((None, StopIteration()))
+                _put_unless(stop, q, (None, StopIteration()))
         except BaseException as e:
-            put((None, e))
+            _put_unless(stop, q, (None, e))
         finally:
             items.close()
 
@@ -761,7 +710,7 @@ def _read_ahead(items, depth):
             yield item
     finally:
         stop.set()
-        t.join()
+        t.join(5)
 
 
 class _TextSlabDevice(object):
@@ -847,12 +796,11 @@ class _TextSlabDevice(object):
     def rows(self, job, lines, index):
         """-> X [c,33,4,4] on the device: the first `lines` slots, or the slots `index` names gathered in that order"""
         torch = self.torch
-        shape = (2 * param.flankingBaseNum + 1, 4, param.matrixNum)
         x = job["x"]
         with torch.cuda.device(self.device):
             if index is None:
                 self.stream.synchronize()
-                return x[:lines].reshape((lines,) + shape)
+                return x[:lines].reshape((lines,) + _SHAPE)
             out = torch.empty((len(index), _NV), dtype=torch.float32, device=self.device)
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(self.stream):
@@ -861,14 +809,13 @@ class _TextSlabDevice(object):
                                                         len(index), ctypes.c_void_p(out.data_ptr()),
                                                         ctypes.c_void_p(self.stream.cuda_stream)))
             self.stream.synchronize()
-            return out.reshape((len(index),) + shape)
+            return out.reshape((len(index),) + _SHAPE)
 
     def empty(self):
-        return self.torch.empty((0, 2 * param.flankingBaseNum + 1, 4, param.matrixNum), dtype=self.torch.float32,
-                                device=self.device)
+        return self.torch.empty((0,) + _SHAPE, dtype=self.torch.float32, device=self.device)
 
 
-def _merge_host_lines(lib, text, info, status, meta):
+def _merge_host_lines(parse, text, info, status, meta):
     """The lines of a slab the device left to the host (status HOST; normally none), parsed one by one with
     cv_parse_tensor_text.  `text`: the bytes the job parsed.  -> (status, meta) with those lines ROW or SKIP, the slots
     and rows [k,528] to patch, the number of malformed lines."""
@@ -880,17 +827,14 @@ def _merge_host_lines(lib, text, info, status, meta):
     rows = np.empty((len(todo), _NV), dtype=np.float32)
     row = np.empty(_NV, dtype=np.float32)
     m1 = np.empty(6, dtype=np.int64)
-    consumed = ctypes.c_int64(); nrows = ctypes.c_int64(); nbad = ctypes.c_int64()
     held = text if text.flags.c_contiguous else np.ascontiguousarray(text)
     base, k, bad = held.ctypes.data, 0, 0
     slots = np.empty(len(todo), dtype=np.int64)
     for i in todo:
         start = int(ends[i - 1]) + 1 if i else 0
-        _lib.check(lib.cv_parse_tensor_text(ctypes.c_void_p(base + start), int(ends[i]) + 1 - start, 1,
-                                            row.ctypes.data_as(ctypes.c_void_p), m1.ctypes.data_as(ctypes.c_void_p),
-                                            ctypes.byref(consumed), ctypes.byref(nrows), ctypes.byref(nbad)))
-        bad += nbad.value
-        if nrows.value:
+        _used, n, b = parse(base + start, int(ends[i]) + 1 - start, 1, row, m1)
+        bad += b
+        if n:
             status[i] = TEXT_ROW
             meta[i] = m1
             meta[i, 0::2] += start
@@ -919,14 +863,14 @@ def GetTensorDevice(tensor_fn, num, device, log=True):
     come back marked and are parsed by cv_parse_tensor_text (malformed ones are reported as GetTensor reports them); a
     slab with more lines than a batch has slots is finished by parsing its remainder again.  The last batch, and only
     it, carries endFlag 1 (an input without rows gives one empty batch)."""
-    lib = _lib.load()
+    parse = _text_parser()
     cap = num + num // 8 + 64
     dev = _TextSlabDevice(device, cap)
-    total = 0
-    held = None
+    done, held = _flagged(log), None
 
     def batches():
-        slabs = _read_ahead(_text_slabs(tensor_fn, num), 2)   # (the inflate of slab k + 1 runs beside the staging of slab k)
+        slabs = _read_ahead(_text_spans(tensor_fn, lambda first_line: _slab_bytes(first_line, num)), 2)   # (the inflate
+        # of slab k + 1 runs beside the staging of slab k)
         slab = next(slabs, None)
         up = dev.upload(slab) if slab is not None else None
         while slab is not None:
@@ -938,9 +882,8 @@ def GetTensorDevice(tensor_fn, num, device, log=True):
                 info, status, meta = dev.collect(job)
                 text = slab[start:]
                 lines = int(info[1])
-                status, meta, slots, rows, bad = _merge_host_lines(lib, text, info, status, meta)
-                if bad:
-                    print("UnpackATensorRecord Failure (%d malformed rows skipped)" % bad, file=sys.stderr)
+                status, meta, slots, rows, bad = _merge_host_lines(parse, text, info, status, meta)
+                _report_malformed(bad)
                 if len(slots):
                     dev.patch(job, slots, rows)
                 keep = np.flatnonzero(status == TEXT_ROW)
@@ -955,17 +898,11 @@ def GetTensorDevice(tensor_fn, num, device, log=True):
 
     for c, x, pos in _closing(batches(), dev):
         if held is not None:
-            total += held[0]
-            if log:
-                print("Processed %d tensors" % total, file=sys.stderr)
-            yield (0,) + held
+            yield done(0, held)
         held = (c, x, pos)
     if held is None:
         held = (0, dev.empty(), PosBatch(b"", np.zeros((0, 6), dtype=np.int64)))
-    total += held[0]
-    if log:
-        print("Processed %d tensors" % total, file=sys.stderr)
-    yield (1,) + held
+    yield done(1, held)
 
 
 # ---- blosc container (python-blosc pack_array / unpack_array equivalents) ---------------

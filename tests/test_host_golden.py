@@ -209,6 +209,72 @@ def test_list_of_compressed_files_read_ahead_gives_the_sequential_batches(tmp_pa
     assert set(seen) <= {0, 1, 2} and {0, 1} <= set(seen)
 
 
+def _route_texts():
+    import textparse_cases as T
+    return {"volume": lambda: T.volume_text(3000, 3), "off_format": lambda: T.off_format_text()[0],
+            "blank_then_rows": lambda: T.blank_then_rows_text(2000, 300)}
+
+
+@pytest.mark.parametrize("name", ["volume", "off_format", "blank_then_rows"])
+@pytest.mark.parametrize("cut_last_newline", [False, True])
+def test_every_route_from_text_to_batches_gives_the_same_rows(name, cut_last_newline, tmp_path, monkeypatch, capfd):
+    """One text read through GetTensor over the memory map, GetTensor with CV_TEXT=stream, GetTensor over the .gz,
+    GetTensorBlocks and GetTensorFiles, as written and with its final newline cut off: the rows (bit for bit) and the
+    (contig, position, sequence) fields are the same sequence on every route and equal what cv_parse_tensor_text makes
+    of the whole text in ONE call; the three GetTensor routes cut the same batches with the same end flags; the
+    malformed lines reported on stderr sum to the one call's count on every route."""
+    import gzip
+    import re
+    import textparse_cases as T
+    from clairvoyante_amd import utils_v2
+    text = _route_texts()[name]()
+    if cut_last_newline:
+        assert text.endswith(b"\n")
+        text = text[:-1]
+    fn = str(tmp_path / "t.txt")
+    open(fn, "wb").write(text)
+    gz = fn + ".gz"
+    with gzip.open(gz, "wb", compresslevel=1) as fh:
+        fh.write(text)
+    whole = text if text.endswith(b"\n") else text + b"\n"
+    consumed, bad, X, meta = T.host_parse(whole)
+    assert consumed == len(whole)
+    want_x, nrows = X.view(np.uint32), len(X)
+    want_pos = [tuple(bytes(whole[m[2 * k]:m[2 * k] + m[2 * k + 1]]) for k in range(3)) for m in meta]
+    assert nrows >= 80 and (bad > 10) == (name == "off_format")
+
+    def reported():
+        return sum(int(k) for k in re.findall(r"UnpackATensorRecord Failure \((\d+) malformed rows skipped\)", capfd.readouterr().err))
+
+    def check(batches, what):
+        x, pos, flags, sizes = T.collect(batches)
+        got_bad = reported()
+        assert np.array_equal(x, want_x), what
+        assert pos == want_pos, what
+        assert got_bad == bad, what + (got_bad, bad)
+        return flags, sizes
+
+    small = name != "volume"                       # (3 000 rows of 10 MB: no row-by-row cuts)
+    reported()
+    for num in ((1,) if small else ()) + (7, nrows, nrows + 1):
+        cuts = []
+        for route in ("map", "stream", "gz"):
+            if route == "stream":
+                monkeypatch.setenv("CV_TEXT", "stream")
+            try:
+                cuts.append(check(utils_v2.GetTensor(gz if route == "gz" else fn, num, log=False), (route, num)))
+            finally:
+                monkeypatch.delenv("CV_TEXT", raising=False)
+        assert cuts[0] == cuts[1] == cuts[2], num
+        flags, sizes = cuts[0]
+        assert flags[-1] == 1 and not any(flags[:-1]) and all(s == num for s in sizes[:-1]), num
+        check([(0, c, x, p) for _k, c, x, p in utils_v2.GetTensorFiles([fn], num, 0, 1)], ("files", num))
+    for block_lines in ((1,) if small else ()) + (64,):
+        for src in (fn, gz):
+            check([(0, c, x, p) for _b, c, x, p in utils_v2.GetTensorBlocks(src, block_lines, 0, 1)],
+                  ("blocks", block_lines, src == gz))
+
+
 def test_training_array_matches_reference():
     from clairvoyante_amd import utils_v2
     d = np.load(os.path.join(G, "trainarray.npz"))
