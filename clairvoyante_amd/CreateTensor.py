@@ -9,7 +9,8 @@ Like the reference it shells out to `samtools faidx` for the reference window (c
 ctgEnd+1Mb, :99-104) and to `samtools view -F 2308` for the alignments (:128-130), reads candidates
 from --can_fn (through `gzip -fdc`) or standard input, and writes one row per candidate that some
 read reached: "<ctg> <pos> <33 reference bases> <528 counts %0.1f>" (:52), to `gzip -c > tensor_fn`
-or standard output.  Differences: candidates are read completely before the alignments are streamed
+or standard output; with --bgzf (not in the reference) the file is written as BGZF members instead, the form callVar
+inflates on the GPU.  Differences: candidates are read completely before the alignments are streamed
 (the reference interleaves the two, :160-162) and rows come out in ascending position order (the
 reference: dict order, :232-246).  `pileup_region()` returns the tensors in HBM instead of text --
 callVarBam feeds them to the network without the text round trip.
@@ -122,7 +123,12 @@ class TensorStdout(object):
 
 def OutputAlnTensor(args):
     res = pileup_region(args, subtract=False)
-    if args.tensor_fn != "PIPE":
+    bgzf = None
+    if args.tensor_fn != "PIPE" and getattr(args, "bgzf", False):      # the same text as BGZF members (utils_v2.BgzfWriter)
+        from .utils_v2 import BgzfWriter
+        bgzf = BgzfWriter(args.tensor_fn)
+        fpo, fp = None, TensorStdout(bgzf)
+    elif args.tensor_fn != "PIPE":
         fpo = open(args.tensor_fn, "wb")
         fp = subprocess.Popen(shlex.split("gzip -c"), stdin=subprocess.PIPE, stdout=fpo, stderr=sys.stderr,
                               bufsize=8388608)
@@ -136,7 +142,9 @@ def OutputAlnTensor(args):
         for row in format_rows(args.ctgName, centers[s:s + step], res["ref_seq"], res["shift"], host):
             fp.stdin.write(row)
             fp.stdin.write(b"\n")
-    if fpo is not None:
+    if bgzf is not None:
+        bgzf.close()
+    elif fpo is not None:
         fp.stdin.close()
         fp.wait()
         fpo.close()
@@ -170,6 +178,9 @@ def build_parser():
     parser.add_argument("--considerleftedge", type=param.str2bool, nargs="?", const=True, default=True,
                         help="Count the left-most base-pairs of a read for coverage even if the starting position of "
                              "a read is after the starting position of a tensor, default: %(default)s")
+    parser.add_argument("--bgzf", type=param.str2bool, nargs="?", const=True, default=False,
+                        help="Write --tensor_fn as BGZF (independent gzip members, as bgzip writes them; any gzip reads "
+                             "it, callVar inflates it on the GPU) instead of through `gzip -c`, default: %(default)s")
     return parser
 
 

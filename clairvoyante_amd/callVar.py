@@ -565,12 +565,17 @@ class _OrderedWriter(object):
 # the fixed cost of the device path (streams, buffers, a round trip per slab) outweighs the host parser's time; a
 # compressed file arrives at one core's inflate rate and the device path wins at no size.
 TEXT_DEVICE_MIN_BYTES = (150000000, None)
+# The same for a .gz that is BGZF through and through (utils_v2.is_bgzf), whose members the device inflates itself:
+# bytes on disk, None = never.  Measured (profiles/r07/bgzf_device.txt): the device wins from the 16 384-row rung
+# (3.8 MB on disk) upwards, 1.2 M rows/s against the host reader's 0.2-0.25 M there and 4.1 M against 0.37 M at 1 M rows;
+# at 1 000 rows (0.23 MB) the fixed cost of the device path loses.
+BGZF_DEVICE_MIN_BYTES = 3800000
 
 
 def parses_on_device(tensor_fn):
     """Which text reader a one-file run uses is decided from the input, not by the user: the device parser
-    (utils_v2.GetTensorDevice) for a regular file of at least TEXT_DEVICE_MIN_BYTES, the host parser below that and for
-    PIPE.  CV_TEXT_PARSE=host|device forces one side for a regular file -- it exists so that tests and
+    (utils_v2.GetTensorDevice) for a regular file of at least TEXT_DEVICE_MIN_BYTES (BGZF_DEVICE_MIN_BYTES for a BGZF
+    file, which that reader also inflates on the device), the host parser below that and for PIPE.  CV_TEXT_PARSE=host|device forces one side for a regular file -- it exists so that tests and
     tools/gpu_callvar_text_probe.py can run both readers over the same input, like CV_TEXT=stream."""
     from . import utils_v2
     if tensor_fn == "PIPE" or not os.path.isfile(tensor_fn):
@@ -580,7 +585,10 @@ def parses_on_device(tensor_fn):
         return forced == "device"
     if forced:
         raise ValueError("CV_TEXT_PARSE must be 'host' or 'device', got %r" % forced)
-    floor = TEXT_DEVICE_MIN_BYTES[1 if utils_v2.is_compressed(tensor_fn) else 0]
+    if utils_v2.is_compressed(tensor_fn):
+        floor = BGZF_DEVICE_MIN_BYTES if utils_v2.is_bgzf(tensor_fn) else TEXT_DEVICE_MIN_BYTES[1]
+    else:
+        floor = TEXT_DEVICE_MIN_BYTES[0]
     return floor is not None and os.path.getsize(tensor_fn) >= max(floor, 1)
 
 

@@ -257,6 +257,51 @@ __global__ __launch_bounds__(256) void tp_gather_rows(const float4 *x, const int
     }
 }
 
+// cv_text_gather_tokens: the three header tokens of the lines idx[0 .. nrows) back to back.  One workgroup walks the
+// lines in steps of its size and scans their token lengths (the offsets of a line depend on every line in front of it);
+// a grid then copies the ~60 bytes of each line.
+constexpr int TOKEN_THREADS = 1024;
+
+__global__ __launch_bounds__(TOKEN_THREADS) void tp_token_offsets(const int64_t *meta, const int64_t *idx, int64_t nrows, int64_t *meta_out)
+{
+    typedef hipcub::BlockScan<int64_t, TOKEN_THREADS> scan_t;
+    __shared__ typename scan_t::TempStorage tmp;
+    __shared__ int64_t carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (int64_t r0 = 0; r0 < nrows; r0 += TOKEN_THREADS) {
+        const int64_t r = r0 + threadIdx.x;
+        int64_t l0 = 0, l1 = 0, l2 = 0;
+        if (r < nrows) {
+            const int64_t *m = meta + idx[r] * 6;
+            l0 = m[1] > 0 ? m[1] : 0; l1 = m[3] > 0 ? m[3] : 0; l2 = m[5] > 0 ? m[5] : 0;
+        }
+        int64_t before, total;
+        scan_t(tmp).ExclusiveSum(l0 + l1 + l2, before, total);
+        const int64_t base = carry + before;
+        if (r < nrows) {
+            int64_t *o = meta_out + r * 6;
+            o[0] = base; o[1] = l0; o[2] = base + l0; o[3] = l1; o[4] = base + l0 + l1; o[5] = l2;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) carry += total;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void tp_token_copy(const uint8_t *text, const int64_t *meta, const int64_t *idx, int64_t nrows,
+                                                     const int64_t *meta_out, uint8_t *bytes, int64_t cap)
+{
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t *m = meta + idx[r] * 6, *o = meta_out + r * 6;
+        for (int t = 0; t < 3; t++) {
+            const int64_t from = m[2 * t], to = o[2 * t], n = o[2 * t + 1];
+            if (to + n > cap) return;                        // (the caller sized the buffer from these very lengths)
+            for (int64_t k = 0; k < n; k++) bytes[to + k] = text[from + k];
+        }
+    }
+}
+
 struct ws_layout {
     int64_t ntiles_max;          // tiles of a slab of `len` bytes at the worst offset inside its first granule
     size_t tile_cnt, tile_first, line_end, scan_tmp, scan_bytes, total;
@@ -357,6 +402,24 @@ extern "C" int cv_text_gather_rows(const float *x_dev, const int64_t *index_dev,
     const int64_t blocks = (nrows * (NV / 4) + 255) / 256;
     hipLaunchKernelGGL(tp_gather_rows, dim3((int)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
                        (const float4 *)x_dev, index_dev, nrows, (float4 *)out_dev);
+    TP_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int cv_text_gather_tokens(const char *text_dev, const int64_t *meta_dev, const int64_t *index_dev, int64_t nrows,
+                                     uint8_t *bytes_dev, int64_t bytes_cap, int64_t *meta_out_dev, void *stream)
+{
+    if (nrows < 0 || bytes_cap < 0) { cv_set_error("cv_text_gather_tokens: negative row count or capacity"); return 1; }
+    if (nrows == 0) return 0;
+    if (!text_dev || !meta_dev || !index_dev || !bytes_dev || !meta_out_dev) { cv_set_error("cv_text_gather_tokens: null argument"); return 1; }
+    if (((uintptr_t)meta_dev & 7) || ((uintptr_t)index_dev & 7) || ((uintptr_t)meta_out_dev & 7)) {
+        cv_set_error("cv_text_gather_tokens: meta and the index list must be 8-byte aligned");
+        return 1;
+    }
+    hipLaunchKernelGGL(tp_token_offsets, dim3(1), dim3(TOKEN_THREADS), 0, (hipStream_t)stream, meta_dev, index_dev, nrows, meta_out_dev);
+    const int64_t blocks = (nrows + 255) / 256;
+    hipLaunchKernelGGL(tp_token_copy, dim3((int)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint8_t *)text_dev, meta_dev, index_dev, nrows, (const int64_t *)meta_out_dev, bytes_dev, bytes_cap);
     TP_HIP(hipGetLastError());
     return 0;
 }

@@ -567,6 +567,160 @@ def GetTensor(tensor_fn, num, log=True):
     yield done(1, batch.take())
 
 
+# ---- BGZF: gzip as independent members of at most 64 KiB (bgzip / htslib), which the GPU inflates side by side -----------
+class BgzfWriter(object):
+    """write() / close() over a new BGZF file: every BLOCK input bytes become one gzip member -- raw DEFLATE from zlib
+    between a header whose "BC" extra subfield states the member's size and the CRC-32 / ISIZE trailer --, the 28-byte
+    empty member that marks the end follows the last.  Any gzip reads the file as ordinary multi-member gzip."""
+    BLOCK = 65280
+    EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+    def __init__(self, fn, level=6, block=None, strategy=0):
+        self.fh = open(fn, "wb") if isinstance(fn, str) else fn
+        self.owned = isinstance(fn, str)
+        self.level, self.block, self.strategy = level, min(block or self.BLOCK, self.BLOCK), strategy
+        self.parts, self.have = [], 0
+
+    @staticmethod
+    def member(data, level=6, strategy=0):
+        """-> one BGZF member that holds `data` (at most 65 280 bytes)"""
+        import struct
+        import zlib
+        for lv in (level, 0):                                # (bytes that do not compress: stored, which always fits)
+            c = zlib.compressobj(lv, zlib.DEFLATED, -15, 9, strategy)
+            body = c.compress(data) + c.flush()
+            if len(body) + 26 <= 65536:
+                break
+        return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(body) + 25) + body +
+                struct.pack("<II", zlib.crc32(data), len(data)))
+
+    def write(self, data):
+        self.parts.append(bytes(data)); self.have += len(data)
+        if self.have >= self.block:
+            buf = b"".join(self.parts)
+            cut = len(buf) - len(buf) % self.block
+            for at in range(0, cut, self.block):
+                self.fh.write(self.member(buf[at:at + self.block], self.level, self.strategy))
+            self.parts, self.have = ([buf[cut:]], len(buf) - cut) if cut < len(buf) else ([], 0)
+        return len(data)
+
+    def flush(self):
+        pass
+
+    def close(self):
+        if self.fh is None:
+            return
+        if self.have:
+            self.fh.write(self.member(b"".join(self.parts), self.level, self.strategy))
+        self.fh.write(self.EOF)
+        if self.owned:
+            self.fh.close()
+        else:
+            self.fh.flush()
+        self.fh = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def bgzf_scan(data):
+    """cv_bgzf_scan over the uint8 array of a whole file -> (table [members,4] int64: offset of the DEFLATE data, its
+    length, running output offset, ISIZE << 32 | CRC-32; inflated bytes), or None when the file is not BGZF through
+    and through (it is then read as ordinary gzip, all of it)"""
+    lib = _lib.load()
+    members, total = ctypes.c_int64(), ctypes.c_int64()
+    src = ctypes.c_void_p(data.ctypes.data)
+    if lib.cv_bgzf_scan(src, len(data), 0, None, ctypes.byref(members), ctypes.byref(total)) != 0:
+        return None
+    table = np.empty((members.value, 4), dtype=np.int64)
+    if lib.cv_bgzf_scan(src, len(data), members.value, table.ctypes.data_as(ctypes.c_void_p), ctypes.byref(members),
+                        ctypes.byref(total)) != 0:
+        return None
+    return table, total.value
+
+
+def _map_bgzf(tensor_fn):
+    """-> (uint8 array over the memory-mapped file, table, inflated bytes) for a regular file that is BGZF; else None"""
+    import mmap
+    if tensor_fn == "PIPE" or not os.path.isfile(tensor_fn) or os.environ.get("CV_GZIP") == "external":
+        return None
+    try:
+        with open(tensor_fn, "rb") as fh:
+            if fh.read(4) != b"\x1f\x8b\x08\x04":
+                return None
+            mm = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
+    except (OSError, ValueError):
+        return None
+    data = np.frombuffer(mm, dtype=np.uint8)
+    got = bgzf_scan(data)
+    return None if got is None else (data,) + got
+
+
+def is_bgzf(tensor_fn):
+    return _map_bgzf(tensor_fn) is not None
+
+
+class _BgzfSlab(object):
+    """consecutive members of a BGZF file: `comp` = the file's bytes from the first member's DEFLATE data to the end of
+    the last one's, `table` = their rows with both offsets relative to the first's, `n` = inflated bytes, `last` = no
+    slab follows"""
+
+    def __init__(self, data, table, fn):
+        lo, hi = int(table[0, 0]), int(table[-1, 0] + table[-1, 1])
+        self.comp = data[lo:hi]
+        self.table = table.copy()
+        self.table[:, 0] -= lo
+        self.table[:, 2] -= table[0, 2]
+        self.n = int(self.table[-1, 2] + (self.table[-1, 3] >> 32))
+        self.last, self.fn = False, fn
+
+    def inflate_member(self, i):
+        """member i inflated on the host and checked (cv_inflate_raw, cv_crc32_ieee) -> uint8 array; CvError in the words
+        of _GzipFile._fail when the host cannot vouch for it either"""
+        lib = _lib.load()
+        off, clen, at, packed = (int(v) for v in self.table[i])
+        isize, crc = packed >> 32, packed & 0xffffffff
+        out = np.empty(max(isize, 1), dtype=np.uint8)
+        # (the 8 bytes behind the DEFLATE data are the member's trailer: cv_inflate_raw may look at them)
+        src = np.ascontiguousarray(np.concatenate((self.comp[off:off + clen], np.zeros(8, dtype=np.uint8))))
+        got = lib.cv_inflate_raw(ctypes.c_void_p(src.ctypes.data), clen, ctypes.c_void_p(out.ctypes.data), isize)
+        if got != isize or lib.cv_crc32_ieee(0, ctypes.c_void_p(out.ctypes.data), isize) != crc:
+            raise _lib.CvError("gzip stream broke off after %d bytes: %s: CRC-32 / length of a member do not match its trailer"
+                               % (at, self.fn))
+        return out[:isize]
+
+
+def _bgzf_slabs(tensor_fn, data, table, num):
+    """the members of a BGZF file grouped into slabs of about `num` rows of INFLATED text (_slab_bytes of the first
+    line, which the host inflates one member for)"""
+    import zlib
+    first_line = 0
+    for off, clen, _at, packed in table[:64]:
+        if packed >> 32:
+            try:
+                first_line = zlib.decompressobj(-15).decompress(bytes(data[off:off + clen])).find(b"\n") + 1
+            except zlib.error:
+                pass
+            break
+    want = _slab_bytes(first_line, num)
+    ends = table[:, 2] + (table[:, 3] >> 32)              # inflated bytes up to and including each member
+    lo, slab = 0, None
+    while lo < len(table):
+        hi = max(int(np.searchsorted(ends, (ends[lo - 1] if lo else 0) + want, side="left")) + 1, lo + 1)
+        if slab is not None:
+            yield slab
+        slab = _BgzfSlab(data, table[lo:hi], tensor_fn)
+        lo = hi
+    slab.last = True
+    yield slab
+
+
+bgzf_member_counts = {"device": 0, "host": 0}       # members GetTensorDevice inflated on the device / handed to the host
+
+
 # ---- the text reader on the device (csrc/cv_textparse.hip) -------------------------------------------------------------
 TEXT_SKIP, TEXT_ROW, TEXT_HOST = 0, 1, 2            # CV_TEXT_* of include/clairvoyante_amd.h
 text_parse_counts = {"device": 0, "host": 0}        # GetTensorDevice / GetTensor runs callVar.Test started (tests read it)
@@ -740,19 +894,99 @@ class _TextSlabDevice(object):
         one thread too); the copy to the device is then asynchronous on the copy stream."""
         torch = self.torch
         n = len(slab)
+        with torch.cuda.device(self.device), torch.cuda.stream(self.copy_stream):
+            text = torch.empty(n + 32, dtype=torch.uint8, device=self.device)
+            stage = self._to_device(text[:n], slab)
+            ev = torch.cuda.Event(); ev.record(self.copy_stream)
+        return text, n, ev, stage
+
+    def _to_device(self, dst, src):
+        """enqueues the copy of the uint8 array `src` into the device tensor `dst` on the current stream; -> what must
+        stay alive until it has run"""
         import warnings
-        stage = slab
+        n = len(src)
+        stage = src
         if _PinnedPool.MIN_BYTES <= n <= _PinnedPool.MAX_BYTES:      # (outside it the pool hands out pageable memory: a
             stage = _pinned.empty((n,), np.uint8)                    # copy into that would only add to the runtime's own)
             cuts = [n * t // self.STAGE_THREADS for t in range(self.STAGE_THREADS + 1)] if n >= (1 << 22) else [0, n]
-            list(self.pool.map(lambda t: np.copyto(stage[cuts[t]:cuts[t + 1]], slab[cuts[t]:cuts[t + 1]]), range(len(cuts) - 1)))
+            list(self.pool.map(lambda t: np.copyto(stage[cuts[t]:cuts[t + 1]], src[cuts[t]:cuts[t + 1]]), range(len(cuts) - 1)))
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")                          # (a read-only source: the map, a bytes object)
+            dst.copy_(self.torch.from_numpy(stage), non_blocking=True)
+        return stage
+
+    # -- a BGZF slab: the compressed bytes are uploaded and inflated on the copy stream, under the kernels of the slab
+    # before; the text buffer has `head` free bytes in front of the inflated text for the unfinished line of that slab
+    def upload_bgzf(self, slab, head):
+        """-> (handle as upload() gives it, end of the text in the buffer)"""
+        torch = self.torch
+        m, end = len(slab.table), head + slab.n + (1 if slab.last else 0)
         with torch.cuda.device(self.device), torch.cuda.stream(self.copy_stream):
-            text = torch.empty(n + 32, dtype=torch.uint8, device=self.device)
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore")                      # (a read-only source: the map, a bytes object)
-                text[:n].copy_(torch.from_numpy(stage), non_blocking=True)
+            text = torch.empty(end + 32, dtype=torch.uint8, device=self.device)
+            comp = torch.empty(len(slab.comp) + 8, dtype=torch.uint8, device=self.device)
+            table = torch.empty((m, 4), dtype=torch.int64, device=self.device)
+            status = torch.zeros(m, dtype=torch.uint8, device=self.device)
+            stage = [self._to_device(comp[:len(slab.comp)], slab.comp), self._to_device(table.view(torch.uint8).reshape(-1), slab.table.view(np.uint8).reshape(-1))]
+            _lib.check(self.lib.cv_inflate_bgzf_dev(ctypes.c_void_p(comp.data_ptr()), ctypes.c_void_p(table.data_ptr()), m,
+                                                    ctypes.c_void_p(text.data_ptr() + head), slab.n, ctypes.c_void_p(status.data_ptr()),
+                                                    ctypes.c_void_p(self.copy_stream.cuda_stream)))
+            if slab.last:
+                text[end - 1:end].fill_(10)                          # (a last line without newline gets one; after one, a blank line)
+            host = torch.empty(m, dtype=torch.uint8, pin_memory=True)
+            host.copy_(status, non_blocking=True)
             ev = torch.cuda.Event(); ev.record(self.copy_stream)
-        return text, n, ev, stage
+        return (text, end, ev, (stage, comp, table, status, host)), end
+
+    def settle(self, up, slab, head):
+        """waits for the slab's inflate; members the device left to the host are inflated there and copied into place"""
+        torch = self.torch
+        text, _end, ev, (_stage, _comp, _table, _status, host) = up
+        ev.synchronize()
+        todo = np.flatnonzero(host.numpy() != 1)                     # CV_BGZF_OK
+        bgzf_member_counts["device"] += len(slab.table) - len(todo)
+        bgzf_member_counts["host"] += len(todo)
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            for i in todo:
+                out = slab.inflate_member(int(i))
+                at = head + int(slab.table[i, 2])
+                text[at:at + len(out)].copy_(torch.from_numpy(out))
+
+    def carry(self, frm, lo, hi, up, at):
+        """the text frm[lo, hi) in front of the inflated text of `up`, at byte `at`"""
+        with self.torch.cuda.device(self.device), self.torch.cuda.stream(self.stream):
+            up[0][at:at + hi - lo].copy_(frm[0][lo:hi])
+
+    def grow(self, up, end, extra):
+        """-> the handle of the same text with `extra` more free bytes in front (a line longer than the headroom)"""
+        torch = self.torch
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            self.stream.wait_event(up[2])
+            text = torch.empty(extra + end + 32, dtype=torch.uint8, device=self.device)
+            text[extra:extra + end].copy_(up[0][:end])
+        return (text, extra + end, up[2], up[3])
+
+    def host_text(self, up, lo, hi):
+        """-> the text up[lo, hi) on the host (slabs with lines the device left to the host: rare)"""
+        self.stream.synchronize()
+        return up[0][lo:hi].cpu().numpy()
+
+    def tokens(self, job, keep, meta):
+        """-> (bytes, meta) piece of a PosBatch for the lines `keep` of a job whose text exists on the device only (and
+        whose every line the device parsed): cv_text_gather_tokens and ONE copy to the host, ~60 bytes per row instead
+        of the ~2.3 KB of its text.  `meta`: the job's, on the host (the token lengths size the buffer)."""
+        torch = self.torch
+        k, total = len(keep), int(meta[keep][:, 1::2].sum())
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            idx = torch.from_numpy(np.ascontiguousarray(keep, dtype=np.int64)).to(self.device)
+            out = torch.empty(k * 48 + total + 8, dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.cv_text_gather_tokens(
+                ctypes.c_void_p(job["text_ptr"]), ctypes.c_void_p(job["meta_ptr"]), ctypes.c_void_p(idx.data_ptr()), k,
+                ctypes.c_void_p(out.data_ptr() + k * 48), total, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(self.stream.cuda_stream)))
+            host = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(out, non_blocking=True)
+        self.stream.synchronize()
+        h = host.numpy()
+        return h[k * 48:k * 48 + total], h[:k * 48].view(np.int64).reshape(k, 6)
 
     def parse(self, up, start):
         """enqueues the parse of the uploaded slab from byte `start` on; -> job"""
@@ -775,7 +1009,7 @@ class _TextSlabDevice(object):
                     ctypes.c_void_p(ws.data_ptr()), need.value, ctypes.c_void_p(self.stream.cuda_stream)))
                 host = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)
                 host.copy_(out, non_blocking=True)
-        return {"x": x, "host": host, "keep": (text, ws, out)}
+        return {"x": x, "host": host, "keep": (text, ws), "out": out, "text_ptr": text.data_ptr() + start, "meta_ptr": p + 32}
 
     def collect(self, job):
         """-> (info [4] int64, status [lines] uint8, meta [lines,6] int64) once the job's kernels have run"""
@@ -854,6 +1088,9 @@ def _closing(items, dev):
             dev.close()
 
 
+BGZF_HEADROOM = 1 << 16        # free bytes in front of a BGZF slab's inflated text: room for the line the slab before left unfinished
+
+
 def GetTensorDevice(tensor_fn, num, device, log=True):
     """GetTensor with the rows parsed on the GPU: generator of (endFlag, c, X_dev, pos), X_dev a [c,33,4,4] fp32 torch
     tensor on `device` (the bits GetTensor gives), pos a PosBatch over the host copy of the text.  The input is cut
@@ -862,39 +1099,65 @@ def GetTensorDevice(tensor_fn, num, device, log=True):
     `num`; candidates are independent, the VCF does not depend on the cut.  Lines that are not in the producer's format
     come back marked and are parsed by cv_parse_tensor_text (malformed ones are reported as GetTensor reports them); a
     slab with more lines than a batch has slots is finished by parsing its remainder again.  The last batch, and only
-    it, carries endFlag 1 (an input without rows gives one empty batch)."""
+    it, carries endFlag 1 (an input without rows gives one empty batch).
+    A BGZF file is a second source of slabs: its COMPRESSED members are uploaded and inflated on the device
+    (cv_inflate_bgzf_dev), so the text never exists on the host -- a slab is then whole members, not whole lines: the
+    text behind its last newline is copied in front of the next slab's, the positions come back through
+    cv_text_gather_tokens, and only a slab with lines the device left to the host is copied back as text."""
     parse = _text_parser()
     cap = num + num // 8 + 64
     dev = _TextSlabDevice(device, cap)
     done, held = _flagged(log), None
+    bgzf = _map_bgzf(tensor_fn) if os.environ.get("CV_TEXT") != "stream" else None
+    if bgzf is None:
+        source = _text_spans(tensor_fn, lambda first_line: _slab_bytes(first_line, num))
+        upload = lambda slab: (dev.upload(slab), len(slab))
+    else:
+        source = _bgzf_slabs(tensor_fn, bgzf[0], bgzf[1], num)
+        upload = lambda slab: dev.upload_bgzf(slab, BGZF_HEADROOM)
 
     def batches():
-        slabs = _read_ahead(_text_spans(tensor_fn, lambda first_line: _slab_bytes(first_line, num)), 2)   # (the inflate
-        # of slab k + 1 runs beside the staging of slab k)
+        slabs = _read_ahead(source, 2)                         # (the inflate of slab k + 1 runs beside the staging of slab k)
         slab = next(slabs, None)
-        up = dev.upload(slab) if slab is not None else None
+        up, end = upload(slab) if slab is not None else (None, 0)
+        tail = None                                            # BGZF: (handle, first byte, end) of the line the slab before left unfinished
         while slab is not None:
             start = 0
+            if bgzf is not None:
+                dev.settle(up, slab, BGZF_HEADROOM)
+                start = BGZF_HEADROOM
+                if tail is not None:
+                    if tail[2] - tail[1] > start:              # one over-long line: more room in front
+                        up, end = dev.grow(up, end, tail[2] - tail[1] - start), end + tail[2] - tail[1] - start
+                        start = tail[2] - tail[1]
+                    start -= tail[2] - tail[1]
+                    dev.carry(tail[0], tail[1], tail[2], up, start)
             job = dev.parse(up, start)
             nxt = next(slabs, None)                            # (its copy runs under the kernels of `slab`)
-            nxt_up = dev.upload(nxt) if nxt is not None else None
+            nxt_up, nxt_end = upload(nxt) if nxt is not None else (None, 0)
             while True:
                 info, status, meta = dev.collect(job)
-                text = slab[start:]
                 lines = int(info[1])
-                status, meta, slots, rows, bad = _merge_host_lines(parse, text, info, status, meta)
-                _report_malformed(bad)
-                if len(slots):
-                    dev.patch(job, slots, rows)
+                if bgzf is None:
+                    text = slab[start:]
+                else:
+                    text = dev.host_text(up, start, start + int(info[0])) if int(info[3]) else None
+                if text is not None:
+                    status, meta, slots, rows, bad = _merge_host_lines(parse, text, info, status, meta)
+                    _report_malformed(bad)
+                    if len(slots):
+                        dev.patch(job, slots, rows)
                 keep = np.flatnonzero(status == TEXT_ROW)
                 if len(keep):
                     x = dev.rows(job, lines, None if len(keep) == lines else keep)
-                    yield len(keep), x, PosBatch(text[:int(info[0])], meta[keep])
+                    pos = PosBatch(text[:int(info[0])], meta[keep]) if text is not None else PosBatch(*dev.tokens(job, keep, meta))
+                    yield len(keep), x, pos
                 start += int(info[0])
-                if lines == 0 or start >= len(slab):
+                if lines == 0 or start >= end:
                     break
                 job = dev.parse(up, start)
-            slab, up = nxt, nxt_up
+            tail = (up, start, end) if bgzf is not None and start < end else None
+            slab, up, end = nxt, nxt_up, nxt_end
 
     for c, x, pos in _closing(batches(), dev):
         if held is not None:

@@ -295,6 +295,33 @@ int cv_parse_tensor_text_dev(const char *text_dev, int64_t len, int64_t max_line
 /* Compaction behind cv_parse_tensor_text_dev (after the caller has patched the HOST slots): out_dev[r][528] =
  * x_dev[index_dev[r]][528] for r < nrows; index_dev int64 on the device.  Enqueued on `stream`.                       */
 int cv_text_gather_rows(const float *x_dev, const int64_t *index_dev, int64_t nrows, float *out_dev, void *stream);
+/* What the host still needs of a slab whose text exists only on the device: the three header tokens (contig,
+ * position, sequence) of the lines index_dev[0 .. nrows), back to back in bytes_dev[0, bytes_cap), and
+ * meta_out_dev[nrows][6] = their offsets / lengths inside bytes_dev -- a (bytes, meta) piece of a position batch after one
+ * copy to the host.  meta_dev is cv_parse_tensor_text_dev's (relative to text_dev).  The caller sizes bytes_dev from the
+ * token lengths it already holds; a line that would not fit is left out.  Enqueued on `stream`.                       */
+int cv_text_gather_tokens(const char *text_dev, const int64_t *meta_dev, const int64_t *index_dev, int64_t nrows,
+                          uint8_t *bytes_dev, int64_t bytes_cap, int64_t *meta_out_dev, void *stream);
+
+/* BGZF (bgzip / htslib: independent gzip members of <= 64 KiB, the compressed size in the "BC" extra subfield).
+ * cv_bgzf_scan walks the member headers of a whole file in memory, once: 0 = BGZF (*members, *inflated_bytes set; the
+ * first max_members rows of table[m][4] filled: offset of the DEFLATE data in src, its length, the running output
+ * offset, ISIZE << 32 | CRC-32), 1 = not BGZF -- a member without the BC subfield or with other header flags, ISIZE
+ * above 65536, a BSIZE that runs past the file, a truncated last member, no member at all; the caller then reads the
+ * WHOLE file as ordinary gzip --, -1 = bad arguments.  Zero padding behind the last member, empty members and a file
+ * without the EOF marker are accepted.
+ * cv_inflate_bgzf_dev inflates `members` rows of such a table on the device: comp_dev points at the first row's DEFLATE
+ * data, member i goes to text_dev[out_i - out_0, + ISIZE_i) inside text_dev[0, text_cap) (offsets are taken relative to
+ * the first row's).  status_dev[i] = CV_BGZF_OK: a valid stream that produced exactly ISIZE bytes, ended there and has
+ * the trailer's CRC-32; CV_BGZF_HOST: anything else -- the device neither accepts nor rejects the member, the caller
+ * inflates it with cv_inflate_raw and checks cv_crc32_ieee (its output range may hold anything until then).
+ * Enqueued on `stream`; neither allocates nor synchronises.                                                         */
+#define CV_BGZF_OK 1
+#define CV_BGZF_HOST 2
+int cv_bgzf_scan(const uint8_t *src, int64_t n, int64_t max_members, int64_t *table, int64_t *members,
+                 int64_t *inflated_bytes);
+int cv_inflate_bgzf_dev(const uint8_t *comp_dev, const int64_t *table_dev, int64_t members, uint8_t *text_dev,
+                        int64_t text_cap, uint8_t *status_dev, void *stream);
 
 /* c-blosc 1.x chunk codec for the 500-item blocks of the `.bin` training file
  * (utils_v2.py:159-186 blosc.pack_array(cname='lz4hc'), :189-207 blosc.unpack_array;

@@ -3,10 +3,11 @@ rows/s for a plain and a gzip-compressed tensor file, with the share of each sta
     python tools/gpu_callvar_text_probe.py [rows] [parse=device|host]
 parse=... forces one text reader (CV_TEXT_PARSE) for the whole run.  With a ladder,
     python tools/gpu_callvar_text_probe.py ladder=1000,16384,65536,200000,1000000 [runs=5] [gzmax=1000000]
-one process alternates parse=host and parse=device at every size, plain and .gz: a warm-up run of each, then `runs`
+one process alternates parse=host and parse=device at every size, plain, .gz and BGZF (the same text re-blocked by
+clairvoyante_amd.bgzf; the device side then inflates it too): a warm-up run of each, then `runs`
 timed runs of each in turn (wall time of callVar.Test behind a loaded model, ending in a device synchronise), rows/s
 as median and range, and which side wins by more than the host side's own range.  kernels=ROWS times the parse
-kernels of one slab beside the forward pass of the same rows."""
+kernels of one slab, and the inflate of the same slab as BGZF members, beside the forward pass of the same rows."""
 import cProfile
 import gzip
 import os
@@ -36,7 +37,7 @@ def ladder(sizes, runs, gzmax):
     import torch
     import common
     from oracle import cv_oracle as O
-    from clairvoyante_amd import callVar, clairvoyante_v3, synth, utils_v2
+    from clairvoyante_amd import bgzf, callVar, clairvoyante_v3, synth, utils_v2
     tmp = tempfile.mkdtemp(prefix="cv_cvtext_")
     ngz = min(max(sizes), 200000)
     x = synth.make_candidates(ngz, seed=9, device="cuda").cpu().numpy()
@@ -51,6 +52,8 @@ def ladder(sizes, runs, gzmax):
         if n <= gzmax:
             subprocess.check_call("gzip -1 -c %s > %s.gz" % (txt, txt), shell=True)
             forms.append(("gz", txt + ".gz"))
+            bgzf.reblock(txt, txt + ".bgzf.gz", level=1)
+            forms.append(("bgzf", txt + ".bgzf.gz"))
         for form, fn in forms:
             a = types.SimpleNamespace(tensor_fn=fn, chkpnt_fn=None, call_fn=os.path.join(tmp, "out.vcf"), qual=None, sampleName="S",
                                       ref_fn=None, threads=None, showRef=False, v3=True, v2=False, slim=False)
@@ -74,7 +77,7 @@ def ladder(sizes, runs, gzmax):
             print("%8d %-5s %11d | %.3g (%.3g..%.3g) | %.3g (%.3g..%.3g) | %s" % (
                 n, form, os.path.getsize(fn), np.median(h), h.min(), h.max(), np.median(d), d.min(), d.max(),
                 "device wins" if wins else "device does not win"), flush=True)
-            if form == "gz":
+            if form != "plain":
                 os.unlink(fn)
         os.unlink(txt)
     os.environ.pop("CV_TEXT_PARSE", None)
@@ -122,14 +125,34 @@ def kernels(n):
     def forward():
         m.predict_device(xd.reshape(n, 33, 4, 4))
 
-    for name, fn in (("index + parse", parse), ("gather of every second row", gather), ("forward pass", forward)):
+    # the same slab as BGZF members (65 280 input bytes each, zlib level 1 and 6), inflated into a second buffer
+    from clairvoyante_amd import utils_v2
+    inflates = []
+    for level in (1, 6):
+        blob = b"".join(utils_v2.BgzfWriter.member(text[at:at + 65280], level) for at in range(0, len(text), 65280))
+        table, total = utils_v2.bgzf_scan(np.frombuffer(blob, dtype=np.uint8))
+        assert total == len(text)
+        table[:, 0] -= table[0, 0]
+        comp = torch.frombuffer(bytearray(blob[18:]), dtype=torch.uint8).cuda()
+        tab = torch.from_numpy(table).cuda()
+        mstat = torch.zeros(len(table), dtype=torch.uint8, device="cuda")
+        dst = torch.zeros(len(text) + 64, dtype=torch.uint8, device="cuda")
+
+        def inflate(comp=comp, tab=tab, mstat=mstat, dst=dst):
+            _lib.check(lib.cv_inflate_bgzf_dev(ctypes.c_void_p(comp.data_ptr()), ctypes.c_void_p(tab.data_ptr()), len(tab),
+                                               ctypes.c_void_p(dst.data_ptr()), len(text), ctypes.c_void_p(mstat.data_ptr()), st))
+        inflate(); torch.cuda.synchronize()
+        assert int((mstat != 1).sum()) == 0 and torch.equal(dst[:len(text)], buf[:len(text)])
+        inflates.append(("inflate + CRC, %d members, level %d, %.1f MB" % (len(table), level, len(blob) / 1e6), inflate))
+
+    for name, fn in [("index + parse", parse), ("gather of every second row", gather), ("forward pass", forward)] + inflates:
         ms = []
         for r in range(8):
             e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
             e0.record(); fn(); e1.record(); torch.cuda.synchronize()
             if r >= 3:
                 ms.append(e0.elapsed_time(e1))
-        print("%d rows, %.1f MB of text: %-28s %.3f ms median (%.3f..%.3f)" % (n, len(text) / 1e6, name, np.median(ms), min(ms), max(ms)))
+        print("%d rows, %.1f MB of text: %-48s %.3f ms median (%.3f..%.3f)" % (n, len(text) / 1e6, name, np.median(ms), min(ms), max(ms)))
     assert tuple(info.cpu().numpy()) == (len(text), n, n, 0)
     m.close()
 
