@@ -169,6 +169,8 @@ class _BatchStream(object):
 
         def stage(X, Y):
             import torch
+            if torch.is_tensor(X) and torch.is_tensor(Y) and X.is_cuda and Y.is_cuda:
+                return X, Y, None                  # slices of a set that lies in HBM: nothing to copy
             with torch.cuda.device(device):
                 side = torch.cuda.Stream(device=device)
                 with torch.cuda.stream(side):
@@ -269,8 +271,11 @@ class _Job(Thread):
             raise self.err
 
 
-def load_dataset(args, utils):
-    """(total, XC, YC, posC) from --bin_fn or from --tensor_fn/--var_fn/--bed_fn (train.py:39-49)"""
+def load_dataset(args, utils, m=None):
+    """(total, XC, YC, posC) from --bin_fn or from --tensor_fn/--var_fn/--bed_fn (train.py:39-49).
+    With one rank, a real model `m` (it takes batches that lie in HBM) and a tensor file whose training set is built on
+    the device (utils.trains_on_device), the set stays there: XC / YC are stand-ins for the block lists which
+    DecompressArray hands out slices of (posC is None: training does not read it)."""
     if args.bin_fn is not None:
         if hasattr(utils, "LoadBin"):
             try:
@@ -278,6 +283,14 @@ def load_dataset(args, utils):
             except TypeError:                                    # a foreign utils module with the plain signature
                 return utils.LoadBin(args.bin_fn)
         return _load_bin(args.bin_fn)
+    if m is not None and getattr(m, "accepts_device_batches", False) and hasattr(utils, "GetTrainingSetDevice") \
+            and utils.trains_on_device(args.tensor_fn):
+        from . import parallel
+        if parallel.world()[1] == 1:
+            ts = utils.GetTrainingSetDevice(args.tensor_fn, args.var_fn, args.bed_fn, device=getattr(m, "device", None))
+            if ts.route == "device":
+                return ts.resident() + (None,)
+            return ts.blocks()
     return utils.GetTrainingArray(args.tensor_fn, args.var_fn, args.bed_fn)
 
 
@@ -340,7 +353,7 @@ def TrainAll(args, m, utils):
     from . import parallel
     rank, ws = parallel.world()
     logging.info("Loading the training dataset ...")
-    total, XC, YC, _posC = load_dataset(args, utils)
+    total, XC, YC, _posC = load_dataset(args, utils, m)
     logging.info("The size of training dataset: {}".format(total))
 
     writer = m.summaryFileWriter(args.olog_dir) if (args.olog_dir is not None and rank == 0) else None
@@ -406,6 +419,8 @@ def PredictAndReport(m, utils, total, XC, YC):
     bases, zs, ts, ls = [np.concatenate(o) for o in outs]
     logging.info("Prediciton time elapsed: %.2f s" % (time.time() - t_pred))
     YArray, _, _ = utils.DecompressArray(YC, 0, total, total)
+    if hasattr(YArray, "cpu"):                      # (a set that lies in HBM: the report is host arithmetic)
+        YArray = YArray.cpu().numpy()
     EvaluateReport(bases, zs, ts, ls, YArray)
 
 

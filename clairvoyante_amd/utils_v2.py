@@ -2,6 +2,9 @@
 /root/reference/clairvoyante/utils_v2.py (SetupEnv :14, GetTensor :23-59,
 GetTrainingArray :62-186, DecompressArray :189-207), with the per-row tokenising and
 the blosc codec done in native code (csrc/cv_hostio.cpp) instead of CPython / python-blosc.
+With a GPU, large text tensor files are parsed on the device (GetTensorDevice, csrc/cv_textparse.hip) and the labelled
+training set of GetTrainingArray is built there (GetTrainingSetDevice, csrc/cv_trainset.hip); the host loops stay as
+the definition of both results.
 """
 import ctypes
 import gc
@@ -724,6 +727,7 @@ bgzf_member_counts = {"device": 0, "host": 0}       # members GetTensorDevice in
 # ---- the text reader on the device (csrc/cv_textparse.hip) -------------------------------------------------------------
 TEXT_SKIP, TEXT_ROW, TEXT_HOST = 0, 1, 2            # CV_TEXT_* of include/clairvoyante_amd.h
 text_parse_counts = {"device": 0, "host": 0}        # GetTensorDevice / GetTensor runs callVar.Test started (tests read it)
+text_line_counts = {"host": 0}                      # lines GetTensorDevice's parser left to the host (status HOST)
 
 
 def _last_newline(a):
@@ -1091,7 +1095,7 @@ def _closing(items, dev):
 BGZF_HEADROOM = 1 << 16        # free bytes in front of a BGZF slab's inflated text: room for the line the slab before left unfinished
 
 
-def GetTensorDevice(tensor_fn, num, device, log=True):
+def GetTensorDevice(tensor_fn, num, device, log=True, keep_device=False):
     """GetTensor with the rows parsed on the GPU: generator of (endFlag, c, X_dev, pos), X_dev a [c,33,4,4] fp32 torch
     tensor on `device` (the bits GetTensor gives), pos a PosBatch over the host copy of the text.  The input is cut
     into slabs of whole lines (about `num` rows each, from the first line's length), slab k + 1 is copied to the device
@@ -1103,7 +1107,9 @@ def GetTensorDevice(tensor_fn, num, device, log=True):
     A BGZF file is a second source of slabs: its COMPRESSED members are uploaded and inflated on the device
     (cv_inflate_bgzf_dev), so the text never exists on the host -- a slab is then whole members, not whole lines: the
     text behind its last newline is copied in front of the next slab's, the positions come back through
-    cv_text_gather_tokens, and only a slab with lines the device left to the host is copied back as text."""
+    cv_text_gather_tokens, and only a slab with lines the device left to the host is copied back as text.
+    keep_device: every batch's `pos` also says where its tokens lie in HBM (pos.device, for GetTrainingSetDevice), which
+    keeps the slab's text there for as long as the batch is held."""
     parse = _text_parser()
     cap = num + num // 8 + 64
     dev = _TextSlabDevice(device, cap)
@@ -1138,6 +1144,7 @@ def GetTensorDevice(tensor_fn, num, device, log=True):
             while True:
                 info, status, meta = dev.collect(job)
                 lines = int(info[1])
+                text_line_counts["host"] += int(info[3])
                 if bgzf is None:
                     text = slab[start:]
                 else:
@@ -1151,6 +1158,13 @@ def GetTensorDevice(tensor_fn, num, device, log=True):
                 if len(keep):
                     x = dev.rows(job, lines, None if len(keep) == lines else keep)
                     pos = PosBatch(text[:int(info[0])], meta[keep]) if text is not None else PosBatch(*dev.tokens(job, keep, meta))
+                    # where the parser left the batch's tokens in HBM (GetTrainingSetDevice reads them there): the slab's
+                    # text, its meta, the kept lines; `merged`: some lines were parsed on the host, whose meta only the
+                    # host copy (pos) holds
+                    if keep_device:
+                        pos.device = {"text": up[0], "out": job.get("out"), "text_ptr": job.get("text_ptr"), "meta_ptr": job.get("meta_ptr"),
+                                      "keep": None if len(keep) == lines else keep, "merged": text is not None and bool(len(slots)),
+                                      "stream": getattr(dev, "stream", None)}
                     yield len(keep), x, pos
                 start += int(info[0])
                 if lines == 0 or start >= end:
@@ -1368,13 +1382,18 @@ class _Intervals(object):
         self.iv.append((b, e))
         self._sorted = None
 
-    def hit(self, p):
+    def table(self):
+        """-> (sorted begins, running maximum of the ends): what hit() bisects, and what cv_trainset_join is given"""
         if self._sorted is None:
             iv = sorted(self.iv)
             self._b = np.array([x[0] for x in iv], dtype=np.int64)
             # running maximum of the ends lets one bisect answer "any interval covers p"
             self._emax = np.maximum.accumulate(np.array([x[1] for x in iv], dtype=np.int64)) if iv else np.array([], dtype=np.int64)
             self._sorted = True
+        return self._b, self._emax
+
+    def hit(self, p):
+        self.table()
         k = int(np.searchsorted(self._b, p, side="right"))
         return k > 0 and self._emax[k - 1] > p
 
@@ -1387,10 +1406,9 @@ def _gz_lines(fn):
     f.wait()
 
 
-def GetTrainingArray(tensor_fn, var_fn, bed_fn, shuffle=True):
-    """utils_v2.py:62-186 -> (total, XArrayCompressed, YArrayCompressed, posArrayCompressed):
-    blocks of param.bloscBlockSize items; X fp32 [k,33,4,4] (matrix-0-subtracted), Y float64
-    [k,16], pos string array; a trailing (possibly empty) block is always appended."""
+def _read_bed_truth(var_fn, bed_fn):
+    """The BED and truth files as utils_v2.py:62-119 reads them -> (tree: contig -> _Intervals, Y: "ctg:pos" -> label of
+    the truth rows the BED keeps; the last row of a key wins).  A truth contig the BED file lacks raises KeyError, as there."""
     tree = {}
     if bed_fn is not None:
         for row in _gz_lines(bed_fn):
@@ -1412,6 +1430,12 @@ def GetTrainingArray(tensor_fn, var_fn, bed_fn, shuffle=True):
             if bed_fn is not None and not tree[ctg].hit(pos):
                 continue
             Y[ctg + ":" + str(pos)] = _label(row)
+    return tree, Y
+
+
+def _training_array_host(tensor_fn, var_fn, bed_fn, shuffle=True):
+    """GetTrainingArray's loop on the host: one dict entry per row -- the definition of what the device route gives"""
+    tree, Y = _read_bed_truth(var_fn, bed_fn)
     X = {}
     total = 0
     for end, c, xb, posb in GetTensor(tensor_fn, 4096, log=False):
@@ -1447,6 +1471,422 @@ def GetTrainingArray(tensor_fn, var_fn, bed_fn, shuffle=True):
     YC.append(pack_array(np.array([Y[k] for k in keys])))
     PC.append(pack_array(np.array(keys)))
     return len(allPos), XC, YC, PC
+
+
+# ---- the labelled training set on the device (csrc/cv_trainset.hip) ------------------------------------------------------
+# Smallest tensor file (bytes on disk) whose training set is built on the device: (plain text, ordinary .gz) and BGZF;
+# None = never.  Measured (profiles/r08/trainset_device.txt, tools/gpu_trainset_probe.py): the device route to blocks beats
+# the host loop in all five runs from the smallest rung of the ladder, 16 384 rows (37.5 MB of plain text, 3.77 MB of
+# BGZF), upwards -- 5.7e5 / 4.5e5 rows/s against 1.2e5 / 0.9e5 there, 9.2e5 / 7.7e5 against 1.0e5 / 0.8e5 at 1 M rows.
+# An ordinary .gz arrives at one core's inflate rate, was not measured and never takes the device route.
+TRAINSET_DEVICE_MIN_BYTES = (37000000, None)
+TRAINSET_BGZF_DEVICE_MIN_BYTES = 3700000
+TRAINSET_MAX_CONTIGS = 65535                        # CV_TRAINSET_MAX_CONTIGS: the sort key holds the contig's rank in 16 bits
+TRAINSET_MAX_DIGITS = 12                            # CV_TRAINSET_MAX_DIGITS
+TRAINSET_RUN_START, TRAINSET_BAD_COORD, TRAINSET_BAD_SEQ = 1, 2, 4
+TRAINSET_FREE_BYTES = None                          # tests: what the device reports as free memory (None = ask it)
+_ROW_BYTES = _NV * 4
+
+
+def _gpu_present():
+    try:
+        import torch
+        return bool(torch.cuda.is_available())
+    except Exception:
+        return False
+
+
+def trains_on_device(tensor_fn):
+    """Which builder GetTrainingArray uses is decided from the input, as callVar.parses_on_device decides its reader:
+    the device route for a regular file at or above this consumer's floors when a GPU is present, the host loop below
+    them, for PIPE and without a GPU.  CV_TEXT_PARSE=host|device forces one side for a regular file."""
+    if tensor_fn == "PIPE" or not os.path.isfile(tensor_fn):
+        return False
+    forced = os.environ.get("CV_TEXT_PARSE")
+    if forced in ("host", "device"):
+        return forced == "device" and _gpu_present()
+    if forced:
+        raise ValueError("CV_TEXT_PARSE must be 'host' or 'device', got %r" % forced)
+    if is_compressed(tensor_fn):
+        floor = TRAINSET_BGZF_DEVICE_MIN_BYTES if is_bgzf(tensor_fn) else TRAINSET_DEVICE_MIN_BYTES[1]
+    else:
+        floor = TRAINSET_DEVICE_MIN_BYTES[0]
+    return floor is not None and os.path.getsize(tensor_fn) >= max(floor, 1) and _gpu_present()
+
+
+def trainset_sort_key(rank, pos, digits):
+    """the 64-bit key of cv_trainset_finish: orders (contig, coordinate) as sorted() orders the strings
+    contig + ":" + coordinate -- `rank` = position of the contig among all contigs ordered by the bytes of name + ":",
+    the coordinate (canonical decimal of `digits` <= 12 digits) padded with zeros to 12 digits compares like its string,
+    and of two coordinates where one is a prefix of the other the shorter comes first"""
+    return (int(rank) << 48) | ((int(pos) * 10 ** (TRAINSET_MAX_DIGITS - int(digits))) << 4) | int(digits)
+
+
+def contig_ranks(names):
+    """names: byte strings in id order -> rank[id] among them ordered by name + b":" """
+    order = sorted(range(len(names)), key=lambda i: names[i] + b":")
+    rank = np.empty(len(names), dtype=np.int32)
+    rank[order] = np.arange(len(names), dtype=np.int32)
+    return rank
+
+
+def canonical_coordinate(tok):
+    """a coordinate token (bytes) the device route takes: digits only, no leading zero unless it is b"0", <= 12 digits"""
+    return 1 <= len(tok) <= TRAINSET_MAX_DIGITS and tok.isdigit() and tok.isascii() and not (len(tok) > 1 and tok[:1] == b"0")
+
+
+def contig_token_ok(tok):
+    """a contig token (bytes) the device route takes: no ':', no NUL, no byte >= 0x80"""
+    return b":" not in tok and b"\0" not in tok and tok.isascii()
+
+
+def shuffled_indices(total):
+    """random.shuffle of range(total): the permutation random.shuffle applies to ANY list of that length under the same
+    generator state (it draws from the length alone), so item p[r] of the sorted keys is item r of the shuffled ones"""
+    p = list(range(total))
+    random.shuffle(p)
+    return p
+
+
+def _trainset_tables(tree, Y, has_bed):
+    """contig ids for the BED and truth contigs and their tables in id order -> (names [bytes], dict of numpy tables)"""
+    ids = {}
+    for name in tree:
+        ids.setdefault(name, len(ids))
+    truth = {}                                      # contig -> [(pos, label)]
+    for key, v in Y.items():
+        name, pos = key.rsplit(":", 1)
+        ids.setdefault(name, len(ids))
+        truth.setdefault(name, []).append((int(pos), v))
+    names = [None] * len(ids)
+    for name, i in ids.items():
+        names[i] = name
+    bed_off, bed_begin, bed_emax = [0], [], []
+    truth_off, truth_pos, labels = [0], [], []
+    for name in names:
+        if name in tree:
+            b, e = tree[name].table()
+            bed_begin.append(b); bed_emax.append(e)
+        bed_off.append(bed_off[-1] + (len(tree[name].iv) if name in tree else 0))
+        rows = sorted(truth.get(name, []), key=lambda r: r[0])
+        truth_pos += [r[0] for r in rows]
+        labels += [r[1] for r in rows]
+        truth_off.append(len(truth_pos))
+    cat = lambda parts: np.concatenate(parts).astype(np.int64) if parts else np.zeros(0, dtype=np.int64)
+    return [n.encode("utf-8") for n in names], {
+        "bed_off": np.array(bed_off, dtype=np.int64), "bed_begin": cat(bed_begin), "bed_emax": cat(bed_emax),
+        "truth_off": np.array(truth_off, dtype=np.int64), "truth_pos": np.array(truth_pos, dtype=np.int64),
+        "labels": np.array(labels, dtype=np.float32).reshape(-1, 16)}
+
+
+def _estimated_rows(tensor_fn):
+    """rows of a tensor file from its size and its first line's length (the inflated size for BGZF, whose table states it)"""
+    bgzf = _map_bgzf(tensor_fn)
+    size = bgzf[2] if bgzf is not None else os.path.getsize(tensor_fn)
+    spans = _text_spans(tensor_fn, 1 << 16)
+    try:
+        first = next(spans, None)
+    finally:
+        spans.close()
+    if first is None or len(first) == 0:
+        return 0
+    nl = _first_newline(first, 0)
+    return size // max(nl + 1 if nl >= 0 else len(first), 1) + 1
+
+
+def trainset_host_reason(tensor_fn, device=None):
+    """why GetTrainingSetDevice hands this input to the host builder before reading it, or None: no GPU, not a regular
+    file, or twice its estimated rows (the set and the rows in arrival order exist side by side) above half of the free
+    device memory"""
+    if not _gpu_present():
+        return "no GPU"
+    if tensor_fn == "PIPE" or not os.path.isfile(tensor_fn):
+        return "not a regular file"
+    free = TRAINSET_FREE_BYTES
+    if free is None:
+        import torch
+        with torch.cuda.device(device):
+            free = torch.cuda.mem_get_info()[0]
+    if _estimated_rows(tensor_fn) * _ROW_BYTES * 2 > free // 2:
+        return "the set would not fit into half of the free device memory"
+    return None
+
+
+class _TrainsetFallback(Exception):
+    """the device route met an input only the host builder defines the result for"""
+
+
+class ResidentBlocks(object):
+    """Stand-in for a compressed-block list whose items already lie in HBM: DecompressArray hands out slices (views, no
+    decompression, no copy) of the device tensor `t`"""
+
+    def __init__(self, t):
+        self.t = t
+
+    def __len__(self):
+        return (int(self.t.shape[0]) + param.bloscBlockSize) // param.bloscBlockSize
+
+
+class TrainingSet(object):
+    """The labelled training set of GetTrainingSetDevice: `total` items in final (sorted, then shuffled) order;
+    X [total,33,4,4] / Y [total,16] fp32 -- device tensors when route == "device", numpy arrays when the host builder
+    made the set (route == "host": `reason` says why); keys() their "ctg:pos" strings; blocks() the return value of
+    GetTrainingArray.  host_lines: lines the device parser left to the host parser."""
+
+    def __init__(self, total, X, Y, route, reason=None, names=None, key_ctg=None, key_pos=None, blocks=None, host_lines=0):
+        self.total, self.route, self.reason, self.host_lines = total, route, reason, host_lines
+        self._X, self._Y = X, Y
+        self._names, self._key_ctg, self._key_pos, self._keys, self._blocks = names, key_ctg, key_pos, None, blocks
+        self.times, self.batches = {}, 0           # seconds per part of the device route; batches GetTensorDevice gave
+
+    @property
+    def X(self):
+        if self._X is None:
+            self._X = DecompressArray(self._blocks[1], 0, self.total, self.total)[0] if self.total else np.zeros((0,) + _SHAPE, np.float32)
+        return self._X
+
+    @property
+    def Y(self):
+        if self._Y is None:
+            y = DecompressArray(self._blocks[2], 0, self.total, self.total)[0] if self.total else np.zeros((0, 16))
+            self._Y = np.asarray(y, dtype=np.float32)
+        return self._Y
+
+    def keys(self):
+        if self._keys is None:
+            if self._blocks is not None:
+                self._keys = [str(k) for a in unpack_arrays(self._blocks[3]) for k in a]
+            else:
+                ctg, pos = self._key_ctg.cpu().numpy(), self._key_pos.cpu().numpy()
+                names = [n.decode("utf-8", "replace") + ":" for n in self._names]      # (a name that reaches a key is ASCII)
+                self._keys = [names[c] + str(p) for c, p in zip(ctg.tolist(), pos.tolist())]
+        return self._keys
+
+    def resident(self):
+        """-> (total, XC, YC) whose block lists are ResidentBlocks over X / Y (train.load_dataset)"""
+        return self.total, ResidentBlocks(self._X), ResidentBlocks(self._Y)
+
+    PACK_THREADS = 16
+    STAGE_ITEMS = 32 * 500                         # items per copy to the host: 34 MB of page-locked staging
+
+    def blocks(self):
+        """-> (total, XC, YC, PC) exactly as the host loop packs them: blocks of param.bloscBlockSize items and a
+        trailing, possibly empty one; X fp32, Y float64, the keys a numpy string array.  The blocks are packed by up to 16
+        host threads (the codec runs outside the interpreter lock) while the next piece of X crosses to the host."""
+        if self._blocks is not None:
+            return self._blocks
+        import time
+        import torch
+        from concurrent.futures import ThreadPoolExecutor
+        t0 = time.time()
+        keys = self.keys()
+        self.times["keys"] = time.time() - t0
+        t0 = time.time()
+        bs, total = param.bloscBlockSize, self.total
+        nfull = total // bs
+        Y = self._Y.cpu().numpy().astype(np.float64)
+        empty = np.array([])
+
+        def block(a, s):
+            return pack_array(np.ascontiguousarray(a[s:s + bs])) if s < len(a) else pack_array(empty)
+
+        step = max(self.STAGE_ITEMS // bs, 1) * bs
+        XC = []
+        with ThreadPoolExecutor(min(self.PACK_THREADS, _lib.usable_cores())) as pool:
+            jobs = []
+            for lo in range(0, max(total, 1), step):
+                hi = min(lo + step, total)
+                host = _pinned.empty((hi - lo,) + _SHAPE, np.float32)
+                if hi > lo:
+                    torch.from_numpy(host).copy_(self._X[lo:hi])
+                # (every block of the piece but a partial last one; the trailing block comes behind the loop)
+                jobs += [pool.submit(block, host, s) for s in range(0, (hi - lo) // bs * bs, bs)]
+                if hi == total:
+                    jobs.append(pool.submit(block, host, (hi - lo) // bs * bs))
+            YC = list(pool.map(lambda b: block(Y, b * bs), range(nfull + 1)))
+            PC = list(pool.map(lambda b: pack_array(np.array(keys[b * bs:(b + 1) * bs])), range(nfull + 1)))
+            XC = [j.result() for j in jobs]
+        self.times["pack"] = time.time() - t0
+        self._blocks = (total, XC, YC, PC)
+        return self._blocks
+
+
+class _TrainsetBuilder(object):
+    """the device side of GetTrainingSetDevice: the rows in arrival order and their per-row columns in HBM, grown by
+    doubling; the tokens and join passes per batch, the finish pass and the gather at the end"""
+
+    def __init__(self, device, names, tables, has_bed, rows_hint):
+        import torch
+        self.torch, self.device, self.lib = torch, torch.device(device), _lib.load()
+        self.names, self.ids = list(names), {n: i for i, n in enumerate(names)}
+        self.ntab, self.has_bed = len(names), has_bed
+        with torch.cuda.device(self.device):
+            self.tab = {k: torch.from_numpy(v).to(self.device) for k, v in tables.items()}
+        self.n, self.cap = 0, 0
+        self.cols = None
+        self._grow(max(int(rows_hint), 1024))
+
+    _COLS = (("pos", "int64"), ("ctg", "int32"), ("truth", "int32"), ("digits", "uint8"), ("centre", "uint8"), ("keep", "uint8"))
+
+    def _grow(self, cap):
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            x = torch.empty((cap, _NV), dtype=torch.float32, device=self.device)
+            cols = {k: torch.empty(cap, dtype=getattr(torch, t), device=self.device) for k, t in self._COLS}
+            if self.n:
+                x[:self.n].copy_(self.x[:self.n])
+                for k in cols:
+                    cols[k][:self.n].copy_(self.cols[k][:self.n])
+        self.x, self.cols, self.cap = x, cols, cap
+
+    def _p(self, t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+    def add(self, c, x, pos):
+        """one batch of GetTensorDevice: its rows behind the ones before, the tokens pass, the run-start tokens compared
+        on the host, the join pass"""
+        torch, lib, d = self.torch, self.lib, pos.device
+        if self.n + c > self.cap:
+            self._grow(max(2 * self.cap, self.n + c))
+        lo, hi = self.n, self.n + c
+        with torch.cuda.device(self.device):
+            cs = torch.cuda.current_stream(self.device)
+            if d["stream"] is not None:
+                cs.wait_stream(d["stream"])
+            st = ctypes.c_void_p(cs.cuda_stream)
+            self.x[lo:hi].copy_(x.reshape(c, _NV))
+            pieces = pos.pieces()
+            if d["merged"]:      # the meta of host-parsed lines: only the host copy holds it
+                meta = torch.from_numpy(np.ascontiguousarray(np.concatenate([m for _s, _r, _b, m in pieces]))).to(self.device)
+                meta_ptr, idx = meta.data_ptr(), None
+            else:
+                meta_ptr = d["meta_ptr"]
+                idx = None if d["keep"] is None else torch.from_numpy(np.ascontiguousarray(d["keep"], dtype=np.int64)).to(self.device)
+            need = ctypes.c_int64()
+            _lib.check(lib.cv_trainset_tokens_workspace(c, ctypes.byref(need)))
+            ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            flags = torch.empty(c, dtype=torch.uint8, device=self.device)
+            run = torch.empty(c, dtype=torch.int32, device=self.device)
+            col = {k: v[lo:hi] for k, v in self.cols.items()}
+            _lib.check(lib.cv_trainset_tokens(ctypes.c_void_p(d["text_ptr"]), ctypes.c_void_p(meta_ptr), self._p(idx), c,
+                                              self._p(col["pos"]), self._p(col["digits"]), self._p(col["centre"]), self._p(flags),
+                                              self._p(run), self._p(ws), need.value, st))
+            fl = flags.cpu().numpy()                         # (synchronises: the slab's text may go after this)
+            if (fl & (TRAINSET_BAD_COORD | TRAINSET_BAD_SEQ)).any():
+                raise _TrainsetFallback("a coordinate that is not canonical decimal, or a sequence token with ':' / a byte >= 0x80")
+            starts = np.flatnonzero(fl & TRAINSET_RUN_START)
+            run_ctg = np.empty(len(starts), dtype=np.int32)
+            first = np.cumsum([0] + [r for _s, r, _b, _m in pieces])
+            for k, j in enumerate(starts.tolist()):          # a handful per file: the only contig tokens the host reads
+                pc = int(np.searchsorted(first, j, side="right")) - 1
+                buf, m = pieces[pc][2], pieces[pc][3][j - int(first[pc])]
+                name = bytes(buf[m[0]:m[0] + m[1]])
+                if name not in self.ids:
+                    if not contig_token_ok(name):
+                        raise _TrainsetFallback("a contig token with ':', NUL or a byte >= 0x80")
+                    if len(self.names) >= TRAINSET_MAX_CONTIGS:
+                        raise _TrainsetFallback("more than %d contigs" % TRAINSET_MAX_CONTIGS)
+                    self.ids[name] = len(self.names)
+                    self.names.append(name)
+                run_ctg[k] = self.ids[name]
+            run_ctg_dev = torch.from_numpy(run_ctg).to(self.device)
+            t = self.tab
+            _lib.check(lib.cv_trainset_join(c, self._p(run), self._p(run_ctg_dev), len(starts), self._p(col["pos"]), self.ntab,
+                                            1 if self.has_bed else 0, self._p(t["bed_off"]), self._p(t["bed_begin"]), self._p(t["bed_emax"]),
+                                            self._p(t["truth_off"]) if t["truth_pos"].numel() else None, self._p(t["truth_pos"]),
+                                            self._p(col["ctg"]), self._p(col["keep"]), self._p(col["truth"]), st))
+        self.n = hi
+
+    def finish(self, shuffle):
+        """-> (total, X, Y, ctg and pos of the items in final order, seconds the shuffle took)"""
+        import time
+        torch, lib, n = self.torch, self.lib, self.n
+        with torch.cuda.device(self.device):
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            rank = torch.from_numpy(contig_ranks(self.names) if self.names else np.zeros(1, np.int32)).to(self.device)
+            need = ctypes.c_int64()
+            _lib.check(lib.cv_trainset_finish_workspace(n, ctypes.byref(need)))
+            ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            src = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+            ys = torch.empty((max(n, 1), 16), dtype=torch.float32, device=self.device)
+            total_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
+            c = self.cols
+            _lib.check(lib.cv_trainset_finish(n, self._p(c["ctg"][:n]), self._p(c["pos"][:n]), self._p(c["digits"][:n]),
+                                              self._p(c["centre"][:n]), self._p(c["keep"][:n]), self._p(c["truth"][:n]),
+                                              self._p(rank), max(len(self.names), 1), self._p(self.tab["labels"]),
+                                              int(self.tab["labels"].shape[0]), self._p(src), self._p(ys), self._p(total_dev),
+                                              self._p(ws), need.value, st))
+            total = int(total_dev.item())
+            t0 = time.time()
+            perm = torch.from_numpy(np.array(shuffled_indices(total), dtype=np.int64)).to(self.device) if shuffle else None
+            t_shuffle = time.time() - t0
+            X = torch.empty((total,) + _SHAPE, dtype=torch.float32, device=self.device)
+            Y = torch.empty((total, 16), dtype=torch.float32, device=self.device)
+            _lib.check(lib.cv_trainset_gather(self._p(self.x), self._p(ys), self._p(src), self._p(perm), total,
+                                              self._p(X), self._p(Y), st))
+            final = src[:total] if perm is None else src[:total][perm]
+            key_ctg, key_pos = c["ctg"][:n][final], c["pos"][:n][final]
+            torch.cuda.current_stream(self.device).synchronize()
+        self.x = self.cols = None
+        return total, X, Y, key_ctg, key_pos, t_shuffle
+
+
+def GetTrainingSetDevice(tensor_fn, var_fn, bed_fn, shuffle=True, device=None, num=65536):
+    """The labelled training set of GetTrainingArray built on the GPU and kept there -> TrainingSet.  The BED and truth
+    files are read as the host loop reads them; the tensor file comes through GetTensorDevice in batches of about
+    `num` rows (plain, .gz streamed, BGZF inflated on the device); per batch the tokens and join passes of
+    csrc/cv_trainset.hip give coordinate, centre base, contig id, BED verdict and truth index of every row; at the end one
+    stable sort by the key that reproduces sorted() over the "ctg:pos" strings gives one item per key -- X of its last
+    arrival, the default label from its first --, shuffled by the permutation random.shuffle applies to the sorted keys.
+    The host loop remains the definition: the WHOLE call goes to it (same result, same exception; route == "host") without
+    a GPU, when the set would not fit, and when a token is met whose treatment only that loop defines (a coordinate
+    that is not canonical decimal, a contig with ':' / NUL / bytes >= 0x80, more than 65 535 contigs)."""
+    import time
+    reason = trainset_host_reason(tensor_fn, device)
+    if reason is None:
+        import torch
+        device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        t0 = time.time()
+        tree, Y = _read_bed_truth(var_fn, bed_fn)
+        names, tables = _trainset_tables(tree, Y, bed_fn is not None)
+        t_tables = time.time() - t0
+        host0 = text_line_counts["host"]
+        b = _TrainsetBuilder(device, names, tables, bed_fn is not None, _estimated_rows(tensor_fn))
+        t_join, nbatches = 0.0, 0
+        t0 = time.time()
+        batches = GetTensorDevice(tensor_fn, num, device, log=False, keep_device=True)
+        try:
+            for _end, c, x, pos in batches:
+                if c:
+                    t1 = time.time()
+                    b.add(c, x, pos)
+                    t_join += time.time() - t1
+                    nbatches += 1
+            t_read = time.time() - t0 - t_join
+            t0 = time.time()
+            total, X, Yd, key_ctg, key_pos, t_shuffle = b.finish(shuffle)
+            ts = TrainingSet(total, X, Yd, "device", names=b.names, key_ctg=key_ctg, key_pos=key_pos,
+                             host_lines=text_line_counts["host"] - host0)
+            ts.batches = nbatches
+            ts.times.update({"tables": t_tables, "read+parse": t_read, "tokens+join": t_join,
+                             "finish+gather": time.time() - t0 - t_shuffle, "shuffle": t_shuffle})
+            return ts
+        except _TrainsetFallback as e:
+            reason, b = str(e), None                 # (the rows gathered so far leave HBM: the host builder starts over)
+        finally:
+            batches.close()
+    blocks = _training_array_host(tensor_fn, var_fn, bed_fn, shuffle)
+    return TrainingSet(blocks[0], None, None, "host", reason=reason, blocks=blocks)
+
+
+def GetTrainingArray(tensor_fn, var_fn, bed_fn, shuffle=True):
+    """utils_v2.py:62-186 -> (total, XArrayCompressed, YArrayCompressed, posArrayCompressed):
+    blocks of param.bloscBlockSize items; X fp32 [k,33,4,4] (matrix-0-subtracted), Y float64
+    [k,16], pos string array; a trailing (possibly empty) block is always appended.
+    Built on the device (GetTrainingSetDevice) when trains_on_device(tensor_fn) says so, by the host loop otherwise."""
+    if trains_on_device(tensor_fn):
+        return GetTrainingSetDevice(tensor_fn, var_fn, bed_fn, shuffle).blocks()
+    return _training_array_host(tensor_fn, var_fn, bed_fn, shuffle)
 
 
 _block_layout = {}          # id(block list) -> (dtype, item shape) learnt from its first block
@@ -1542,6 +1982,8 @@ def DecompressArray(array, start, num, maximum):
     if start + num >= maximum:
         num = maximum - start
         endFlag = 1
+    if isinstance(array, ResidentBlocks):           # the set lies in HBM: a view of it, nothing to decompress or copy
+        return array.t[start:start + num], num, endFlag
     bs = param.bloscBlockSize
     leftEnd = start % bs
     first = int(start / bs)

@@ -323,6 +323,57 @@ int cv_bgzf_scan(const uint8_t *src, int64_t n, int64_t max_members, int64_t *ta
 int cv_inflate_bgzf_dev(const uint8_t *comp_dev, const int64_t *table_dev, int64_t members, uint8_t *text_dev,
                         int64_t text_cap, uint8_t *status_dev, void *stream);
 
+/* ---- the labelled training set on the device (csrc/cv_trainset.hip) -------------------------------------------------
+ * What utils_v2.GetTrainingArray's per-row loop does (utils_v2.py:62-186), for rows cv_parse_tensor_text_dev left in
+ * HBM; the host loop stays the definition of the result.  Every call is enqueued on `stream` and neither allocates nor
+ * synchronises; workspaces (256-byte aligned) are sized by the *_workspace functions and belong to the call until its
+ * kernels have run.
+ *
+ * cv_trainset_tokens, per slab: row r < nrows is line index_dev[r] of the slab (index_dev null: line r); text_dev /
+ * meta_dev as the parser left them.
+ *   pos_dev[r] int64, digits_dev[r]  the coordinate token and its length; CV_TRAINSET_BAD_COORD in flags_dev[r] (and
+ *                                    digits 0) when it is not canonical decimal: digits only, no leading zero unless it
+ *                                    is "0", at most CV_TRAINSET_MAX_DIGITS digits;
+ *   centre_dev[r]                    the 17th character of the sequence token, upper-cased: A,C,G,T -> 0..3;
+ *   flags_dev[r]                     CV_TRAINSET_RUN_START: the contig token differs byte for byte from row r - 1's (row 0:
+ *                                    always); CV_TRAINSET_BAD_SEQ: the sequence token holds ':' or a byte >= 0x80;
+ *   run_dev[r] int32                 index of the row's contig run inside the slab (run starts in front of it, minus 1).
+ * cv_trainset_join, per slab: run_ctg_dev[nruns] = contig id of each run (the host compares the run-start tokens
+ * byte for byte).  Contig ids below `ntab` have rows in the tables: bed_off_dev[ntab + 1] into bed_begin_dev (sorted)
+ * / bed_emax_dev (running maximum of the ends), truth_off_dev[ntab + 1] into truth_pos_dev (sorted per contig; null: no
+ * truth).  ctg_dev[r] = contig id; keep_dev[r] = !has_bed, or upper_bound(begin, pos) = k > 0 and emax[k - 1] > pos;
+ * truth_dev[r] = index of (contig, pos) in truth_pos_dev or -1.
+ * cv_trainset_finish, once over all nrows rows in arrival order: the kept rows sorted (stable) by
+ * rank_dev[ctg] << 48 | pos * 10^(12 - digits) << 4 | digits -- the order of sorted() over "contig:pos" strings when
+ * rank_dev[nctg] orders the contigs by the bytes of name + ":" --, one entry per distinct key:
+ *   *total_dev            entries;
+ *   src_dev[e] int64      arrival index of the LAST row with the key (buffer of nrows);
+ *   y_dev[e][16] fp32     labels_dev[truth][16] when truth >= 0, else HOM, REF, length 0 = 1 and 1 at the centre base
+ *                         of the FIRST row with the key (buffer of nrows * 16).
+ * cv_trainset_gather: x_out_dev[r][528] = x_all_dev[src_dev[p]][528], y_out_dev[r][16] = y_dev[p][16], p = perm_dev[r]
+ * (null: r), r < total; all four tensors 16-byte aligned.                                                            */
+#define CV_TRAINSET_RUN_START 1
+#define CV_TRAINSET_BAD_COORD 2
+#define CV_TRAINSET_BAD_SEQ 4
+#define CV_TRAINSET_MAX_DIGITS 12
+#define CV_TRAINSET_MAX_CONTIGS 65535
+#define CV_TRAINSET_MAX_ROWS ((int64_t)1 << 30)
+int cv_trainset_tokens_workspace(int64_t nrows, int64_t *bytes);
+int cv_trainset_tokens(const char *text_dev, const int64_t *meta_dev, const int64_t *index_dev, int64_t nrows,
+                       int64_t *pos_dev, uint8_t *digits_dev, uint8_t *centre_dev, uint8_t *flags_dev, int32_t *run_dev,
+                       void *workspace_dev, int64_t workspace_bytes, void *stream);
+int cv_trainset_join(int64_t nrows, const int32_t *run_dev, const int32_t *run_ctg_dev, int64_t nruns,
+                     const int64_t *pos_dev, int32_t ntab, int has_bed, const int64_t *bed_off_dev,
+                     const int64_t *bed_begin_dev, const int64_t *bed_emax_dev, const int64_t *truth_off_dev,
+                     const int64_t *truth_pos_dev, int32_t *ctg_dev, uint8_t *keep_dev, int32_t *truth_dev, void *stream);
+int cv_trainset_finish_workspace(int64_t nrows, int64_t *bytes);
+int cv_trainset_finish(int64_t nrows, const int32_t *ctg_dev, const int64_t *pos_dev, const uint8_t *digits_dev,
+                       const uint8_t *centre_dev, const uint8_t *keep_dev, const int32_t *truth_dev,
+                       const int32_t *rank_dev, int32_t nctg, const float *labels_dev, int64_t ntruth, int64_t *src_dev,
+                       float *y_dev, int64_t *total_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int cv_trainset_gather(const float *x_all_dev, const float *y_dev, const int64_t *src_dev, const int64_t *perm_dev,
+                       int64_t total, float *x_out_dev, float *y_out_dev, void *stream);
+
 /* c-blosc 1.x chunk codec for the 500-item blocks of the `.bin` training file
  * (utils_v2.py:159-186 blosc.pack_array(cname='lz4hc'), :189-207 blosc.unpack_array;
  * tensor2Bin.py:24-28).  Decoder: LZ4/LZ4HC streams, byte shuffle, split blocks, memcpy'd
