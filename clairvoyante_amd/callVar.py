@@ -570,12 +570,19 @@ TEXT_DEVICE_MIN_BYTES = (150000000, None)
 # (3.8 MB on disk) upwards, 1.2 M rows/s against the host reader's 0.2-0.25 M there and 4.1 M against 0.37 M at 1 M rows;
 # at 1 000 rows (0.23 MB) the fixed cost of the device path loses.
 BGZF_DEVICE_MIN_BYTES = 3800000
+# The same for an ordinary gzip file (one DEFLATE stream: `gzip`, Python's gzip module), whose block starts the device
+# finds and whose chunks it inflates itself (utils_v2._gzip_slabs): bytes on disk, None = never.
+# Measured (profiles/r09/gzip_device.txt, `gzip -6` files): the device wins from the 200 000-row rung (24.5 MB on disk)
+# upwards, 0.79 M rows/s against the host reader's 0.55 M there and 1.41 M against 0.56 M at 1 M rows; at 65 536 rows
+# (8 MB) and below it loses: one block is ~32 768 symbols decoded by one lane, twice (count, write), which is ~90 ms
+# whatever the size of the file.
+GZIP_DEVICE_MIN_BYTES = 24500000
 
 
 def parses_on_device(tensor_fn):
     """Which text reader a one-file run uses is decided from the input, not by the user: the device parser
     (utils_v2.GetTensorDevice) for a regular file of at least TEXT_DEVICE_MIN_BYTES (BGZF_DEVICE_MIN_BYTES for a BGZF
-    file, which that reader also inflates on the device), the host parser below that and for PIPE.  CV_TEXT_PARSE=host|device forces one side for a regular file -- it exists so that tests and
+    file, GZIP_DEVICE_MIN_BYTES for an ordinary gzip file, both of which that reader also inflates on the device), the host parser below that and for PIPE.  CV_TEXT_PARSE=host|device forces one side for a regular file -- it exists so that tests and
     tools/gpu_callvar_text_probe.py can run both readers over the same input, like CV_TEXT=stream."""
     from . import utils_v2
     if tensor_fn == "PIPE" or not os.path.isfile(tensor_fn):
@@ -586,7 +593,12 @@ def parses_on_device(tensor_fn):
     if forced:
         raise ValueError("CV_TEXT_PARSE must be 'host' or 'device', got %r" % forced)
     if utils_v2.is_compressed(tensor_fn):
-        floor = BGZF_DEVICE_MIN_BYTES if utils_v2.is_bgzf(tensor_fn) else TEXT_DEVICE_MIN_BYTES[1]
+        if utils_v2.is_bgzf(tensor_fn):
+            floor = BGZF_DEVICE_MIN_BYTES
+        else:                                    # (the floor of every compressed file, or the lower one of a gzip file's own)
+            floor = TEXT_DEVICE_MIN_BYTES[1]
+            if GZIP_DEVICE_MIN_BYTES is not None and utils_v2._map_gzip(tensor_fn) is not None:
+                floor = GZIP_DEVICE_MIN_BYTES if floor is None else min(floor, GZIP_DEVICE_MIN_BYTES)
     else:
         floor = TEXT_DEVICE_MIN_BYTES[0]
     return floor is not None and os.path.getsize(tensor_fn) >= max(floor, 1)

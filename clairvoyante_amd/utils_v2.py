@@ -724,6 +724,181 @@ def _bgzf_slabs(tensor_fn, data, table, num):
 bgzf_member_counts = {"device": 0, "host": 0}       # members GetTensorDevice inflated on the device / handed to the host
 
 
+# ---- ordinary gzip: one DEFLATE stream whose block starts the GPU finds (csrc/cv_gzip_dev.hip) --------------------------
+# chunks (runs of blocks between two found starts) GetTensorDevice inflated on the device / times it handed the rest of a
+# file to the host reader
+gzip_chunk_counts = {"device": 0, "host": 0}
+# spacing of the finder's guesses (CV_GZIP_GUESS_BYTES).  `gzip` ends a block after some tens of KB, so most guesses find
+# nothing and a chunk is one block either way: the spacing only sets how many waves share the scan
+GZIP_GUESS_BYTES = 4096
+GZIP_SLAB_BYTES = 128 << 20    # compressed bytes per slab: a few thousand chunks, about one per wave the chip holds
+GZIP_TEXT_BYTES = 1 << 30      # inflated bytes per slab: a slab that turns out larger is cut at a chunk, the next ones are sized by its ratio
+TEXT_SLAB_MAX = 1 << 31        # CV_TEXT_SLAB_MAX of include/clairvoyante_amd.h
+GZIP_SLAB_MAX = 1 << 30        # a slab grows to this in search of a block start before the host takes the file
+GZIP_ROUNDS = 8                # counting passes per slab: every round drops the decoy starts one chunk ran over
+
+
+def _map_gzip(tensor_fn):
+    """-> (uint8 array over the memory-mapped file, byte at which the first member's DEFLATE data starts) for a regular
+    file that starts with a gzip header (RFC 1952: FEXTRA / FNAME / FCOMMENT / FHCRC skipped); else None"""
+    import mmap
+    if tensor_fn == "PIPE" or not os.path.isfile(tensor_fn) or os.environ.get("CV_GZIP") == "external":
+        return None
+    try:
+        with open(tensor_fn, "rb") as fh:
+            head = fh.read(4)
+            if len(head) < 4 or head[:3] != b"\x1f\x8b\x08" or (head[3] & 0xe0):
+                return None
+            mm = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
+    except (OSError, ValueError):
+        return None
+    b = np.frombuffer(mm, dtype=np.uint8)
+    n, flg, p = len(b), int(b[3]), 10
+    if n < 18:
+        return None
+    if flg & 4:
+        p += 2 + int(b[p]) + 256 * int(b[p + 1])
+    for bit in (8, 16):
+        if flg & bit:
+            while p < n and b[p] != 0:
+                p += 1
+            p += 1
+    if flg & 2:
+        p += 2
+    return (b, p) if p + 8 <= n else None
+
+
+def _crc_operators():
+    """M[k] = the CRC-32 register after 2^k zero bytes, as a GF(2) matrix: 32 columns, column i = where bit i goes"""
+    table = np.arange(256, dtype=np.uint32)
+    for _ in range(8):
+        table = np.where(table & 1, np.uint32(0xEDB88320) ^ (table >> 1), table >> 1).astype(np.uint32)
+    col = np.uint32(1) << np.arange(32, dtype=np.uint32)
+    ops = [table[col & 0xff] ^ (col >> 8)]
+    for _ in range(1, 48):
+        ops.append(_crc_apply(ops[-1], ops[-1]))
+    return ops
+
+
+def _crc_apply(op, v):
+    """the operator applied to the register(s) v (uint32 scalar or array)"""
+    v = np.asarray(v, dtype=np.uint32)
+    out = np.zeros(v.shape, dtype=np.uint32)
+    for b in range(32):
+        out ^= np.where((v >> np.uint32(b)) & np.uint32(1), op[b], np.uint32(0)).astype(np.uint32)
+    return out
+
+
+_CRC_OPS = []
+_CRC_BYTE_TABLES = {}
+
+
+def _crc_apply_many(k, v):
+    """_crc_apply(_CRC_OPS[k], v) for a long array: four look-ups per register in tables of the operator's images of
+    every byte value at every byte position (built once per level), instead of 32 masked passes"""
+    t = _CRC_BYTE_TABLES.get(k)
+    if t is None:
+        byte = np.arange(256, dtype=np.uint32)
+        t = _CRC_BYTE_TABLES[k] = [_crc_apply(_CRC_OPS[k], byte << np.uint32(8 * j)) for j in range(4)]
+    return t[0][v & 0xff] ^ t[1][(v >> 8) & 0xff] ^ t[2][(v >> 16) & 0xff] ^ t[3][v >> 24]
+
+
+def _crc_shift(reg, nbytes):
+    """the register `reg` after `nbytes` zero bytes"""
+    if not _CRC_OPS:
+        _CRC_OPS.extend(_crc_operators())
+    k = 0
+    while nbytes:
+        if nbytes & 1:
+            reg = _crc_apply(_CRC_OPS[k], reg)
+        nbytes >>= 1; k += 1
+    return int(reg)
+
+
+def _crc_fold(parts):
+    """cv_gzip_crc_dev's registers (1 KiB pieces aligned to the end, each started from 0) -> the register of the whole
+    text started from 0: a tree, level k joins neighbours with the operator '1024 * 2^k zero bytes follow'"""
+    if not _CRC_OPS:
+        _CRC_OPS.extend(_crc_operators())
+    parts, k = np.asarray(parts, dtype=np.uint32), 10
+    if len(parts) == 0:
+        return 0
+    while len(parts) > 1:
+        if len(parts) & 1:
+            parts = np.concatenate((np.zeros(1, dtype=np.uint32), parts))     # (nothing in front: a zero register)
+        parts = (_crc_apply_many(k, parts[0::2]) if len(parts) > 4096 else _crc_apply(_CRC_OPS[k], parts[0::2])) ^ parts[1::2]
+        k += 1
+    return int(parts[0])
+
+
+class _GzipText(object):
+    """a slab of an ordinary gzip file, inflated on the device: `up` = the handle upload() gives, `end` = the end of the
+    text in its buffer (which starts at BGZF_HEADROOM), `last` = no slab follows"""
+
+    def __init__(self, up, end, last):
+        self.up, self.end, self.last = up, end, last
+
+
+def _gzip_slabs(tensor_fn, data, first, num, dev):
+    """The slabs of an ordinary gzip file for GetTensorDevice: _GzipText while the device vouches for what it inflates --
+    every chunk decoded from a start that the chunk in front ended on, the first right behind the gzip header; CRC-32 and
+    ISIZE checked at the member's end --, and from its first doubt on the spans of whole lines of the host reader
+    (_text_spans, the text the device already delivered dropped; the first span then starts in the middle of a line)."""
+    n = len(data)
+    forced = os.environ.get("CV_TEXT_SLAB_BYTES")
+    want = max(1, int(forced)) if forced else GZIP_SLAB_BYTES
+    spacing = max(64, int(os.environ.get("CV_GZIP_GUESS_BYTES") or GZIP_GUESS_BYTES))
+    bit, total, reg, window, why = first * 8, 0, 0xffffffff, None, None
+    while why is None:
+        lo = bit >> 3
+        hi = min(lo + want, n)
+        got = dev.inflate_gzip(data[lo:hi], bit - lo * 8, hi == n, bit != first * 8, window, BGZF_HEADROOM, spacing)
+        if got is None:                                          # no block start to cut at: more bytes
+            if hi - lo >= GZIP_SLAB_MAX:
+                why = "no block start in %d bytes" % (hi - lo)
+            want *= 4
+            continue
+        if isinstance(got, str):
+            why = got
+            break
+        reg = _crc_shift(reg, got["n"]) ^ _crc_fold(got["parts"])
+        last = False
+        if got["ended"]:
+            t = lo + ((got["next_bit"] + 7) >> 3)
+            if t + 8 > n:
+                why = "a truncated trailer"
+                break
+            want_crc = int.from_bytes(bytes(data[t:t + 4]), "little")
+            want_len = int.from_bytes(bytes(data[t + 4:t + 8]), "little")
+            if want_crc != reg ^ 0xffffffff or want_len != ((total + got["n"]) & 0xffffffff):
+                raise _lib.CvError("gzip stream broke off after %d bytes: %s: CRC-32 / length of a member do not match its trailer"
+                                   % (total, tensor_fn))
+            last = not data[t + 8:].any()                        # (zero padding behind the member is legal)
+        gzip_chunk_counts["device"] += got["chunks"]
+        total += got["n"]
+        window = got["window"]
+        up, end = dev.gzip_handle(got, BGZF_HEADROOM, last)
+        yield _GzipText(up, end, last)
+        if last:
+            return
+        if got["ended"]:
+            why = "a second member or trailing bytes"
+        bit = lo * 8 + got["next_bit"]
+        if not forced and got["n"]:                              # the next slab: about GZIP_TEXT_BYTES of text at this slab's ratio
+            used = max(1, (got["next_bit"] + 7) >> 3)
+            want = max(1 << 20, min(GZIP_SLAB_BYTES, int(GZIP_TEXT_BYTES * (used / float(got["n"])))))
+    gzip_chunk_counts["host"] += 1
+    import logging
+    logging.info("%s: %s: the host reader takes the file from byte %d of its text on" % (tensor_fn, why, total))
+    skip = total
+    for span in _text_spans(tensor_fn, lambda first_line: _slab_bytes(first_line, num)):
+        if skip >= len(span):
+            skip -= len(span)
+            continue
+        yield span[skip:] if skip else span
+        skip = 0
+
+
 # ---- the text reader on the device (csrc/cv_textparse.hip) -------------------------------------------------------------
 TEXT_SKIP, TEXT_ROW, TEXT_HOST = 0, 1, 2            # CV_TEXT_* of include/clairvoyante_amd.h
 text_parse_counts = {"device": 0, "host": 0}        # GetTensorDevice / GetTensor runs callVar.Test started (tests read it)
@@ -955,6 +1130,110 @@ class _TextSlabDevice(object):
                 at = head + int(slab.table[i, 2])
                 text[at:at + len(out)].copy_(torch.from_numpy(out))
 
+    # -- a slab of an ordinary gzip file: find block starts, count, check the chain, write symbols, resolve, CRC -- all on
+    # the copy stream; the host reads back the found starts, the counts and the final statuses
+    def inflate_gzip(self, comp, first_bit, final, sole_ok, window, head, spacing):
+        """comp: the file's bytes from the byte that holds the slab's first block header (at bit `first_bit` of it, a
+        TRUE block start) on; final: they reach the end of the file; window: the last <= 32 KiB of text in front (device
+        tensor or None); sole_ok: a slab without any dynamic header behind its start is decoded as one chunk.
+        -> None: no block start to cut at, the caller comes back with more bytes;  str: why the device does not vouch for
+        the slab;  dict: text (device buffer, the inflated bytes from `head` on, the window in front of them), n,
+        next_bit (where the slab's last chunk ended = the next slab's first block header), ended (at BFINAL), parts
+        (cv_gzip_crc_dev), chunks, window (of the slab that follows)."""
+        torch, lib, np_ = self.torch, self.lib, np
+        nb = len(comp)
+        s = ctypes.c_void_p(self.copy_stream.cuda_stream)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+        with torch.cuda.device(self.device), torch.cuda.stream(self.copy_stream):
+            cdev = torch.empty(nb + 8, dtype=torch.uint8, device=self.device)
+            stage = self._to_device(cdev[:nb], comp)
+            guesses = max(1, -(-(nb * 8 - first_bit) // (spacing * 8)))
+            found = torch.empty(guesses, dtype=torch.int64, device=self.device)
+            _lib.check(lib.cv_gzip_find_dev(ptr(cdev), nb, first_bit, spacing, guesses, ptr(found), s))
+            f = found.cpu().numpy()
+            f = f[f >= 0]
+            if len(f) == 0 and not (final and sole_ok):
+                return "no dynamic block" if final else None
+            starts = np_.concatenate((np_.array([first_bit], dtype=np_.int64), f))
+            hist = 0 if window is None else int(window.shape[0])
+
+            def decode(rows, sym, cap):
+                table = torch.from_numpy(rows).to(self.device)
+                result = torch.empty((len(rows), 4), dtype=torch.int64, device=self.device)
+                _lib.check(lib.cv_gzip_decode_dev(ptr(cdev), nb, ptr(table), len(rows), ptr(sym) if sym is not None else None, cap,
+                                                  ptr(result), s))
+                return result
+
+            res, verified, ended = np_.zeros((0, 4), dtype=np_.int64), 0, False
+            for _round in range(GZIP_ROUNDS):
+                chunks = len(starts) if final else len(starts) - 1
+                if chunks < 1:
+                    return None
+                ends = np_.append(starts[1:], -1)[:chunks]
+                rows = np_.zeros((chunks - verified, 6), dtype=np_.int64)
+                rows[:, 0], rows[:, 1], rows[:, 4] = starts[verified:chunks], ends[verified:], 32768
+                if verified == 0:
+                    rows[0, 4] = hist
+                res = np_.concatenate((res[:verified], decode(rows, None, 0).cpu().numpy()))
+                off_chain = np_.flatnonzero(res[:, 2] != 1)              # CV_GZIP_LANDED: ended where the next was found
+                if len(off_chain) == 0:
+                    break
+                k = int(off_chain[0])
+                if res[k, 2] == 2:                                       # CV_GZIP_FINAL: the stream ends in chunk k
+                    chunks, ended = k + 1, True
+                    break
+                if res[k, 2] != 3:                                       # CV_GZIP_PASSED
+                    return "a chunk the device does not vouch for"
+                # chunk k is true, so every start it ran over is a decoy (the next one at the least)
+                starts = starts[(starts <= starts[k]) | ((starts >= res[k, 1]) & (starts != starts[k + 1]))]
+                verified = k
+            else:
+                return "a chain of block starts that could not be repaired"
+            cum = np_.cumsum(res[:chunks, 0])
+            if cum[-1] > GZIP_TEXT_BYTES and chunks > 1:                 # more text than a slab should hold: the first chunks only
+                fit = max(1, int(np_.searchsorted(cum, GZIP_TEXT_BYTES, side="right")))
+                if fit < chunks:
+                    chunks, ended = fit, False
+            if int(cum[chunks - 1]) + head + 64 > TEXT_SLAB_MAX:
+                return "a chunk with more text than the parser takes in one slab"
+            res = res[:chunks]
+            off = np_.concatenate((np_.zeros(1, dtype=np_.int64), np_.cumsum(res[:, 0])))
+            total = int(off[-1])
+            rows = np_.zeros((chunks, 6), dtype=np_.int64)
+            rows[:, 0], rows[:, 1], rows[:, 4] = starts[:chunks], np_.append(starts[1:], -1)[:chunks], 32768
+            rows[0, 4] = hist
+            rows[:, 2], rows[:, 3] = off[:-1], res[:, 0]
+            sym = torch.empty(total + 8, dtype=torch.int16, device=self.device)
+            again = decode(rows, sym, total)
+            text = torch.empty(head + total + 1 + 32, dtype=torch.uint8, device=self.device)
+            if hist:
+                text[head - hist:head].copy_(window)
+            offs = torch.from_numpy(off).to(self.device)
+            pieces = (total + 1023) // 1024
+            tailinfo = torch.zeros(2 + pieces, dtype=torch.int32, device=self.device)     # bad | pad | CRC parts
+            _lib.check(lib.cv_gzip_resolve_dev(ptr(sym), ptr(offs), chunks, total, hist, ctypes.c_void_p(text.data_ptr() + head),
+                                               ptr(tailinfo), s))
+            _lib.check(lib.cv_gzip_crc_dev(ctypes.c_void_p(text.data_ptr() + head), total, ctypes.c_void_p(tailinfo.data_ptr() + 8), s))
+            again, info = again.cpu().numpy(), tailinfo.cpu().numpy()
+            del stage
+            if not np_.array_equal(again[:, :3], res[:, :3]):
+                return "a writing pass that differs from the counting pass"
+            if info[0]:
+                return "a match that reaches in front of the stream's start"
+            keep = min(32768, hist + total)
+            return {"text": text, "n": total, "next_bit": int(res[-1, 1]), "ended": ended, "chunks": chunks,
+                    "parts": info[2:].view(np_.uint32), "window": text[head + total - keep:head + total]}
+
+    def gzip_handle(self, got, head, last):
+        """-> (handle as upload() gives it, end of the text in the buffer) of an inflated gzip slab"""
+        torch = self.torch
+        end = head + got["n"] + (1 if last else 0)
+        with torch.cuda.device(self.device), torch.cuda.stream(self.copy_stream):
+            if last:
+                got["text"][end - 1:end].fill_(10)                   # (as upload_bgzf)
+            ev = torch.cuda.Event(); ev.record(self.copy_stream)
+        return (got["text"], end, ev, None), end
+
     def carry(self, frm, lo, hi, up, at):
         """the text frm[lo, hi) in front of the inflated text of `up`, at byte `at`"""
         with self.torch.cuda.device(self.device), self.torch.cuda.stream(self.stream):
@@ -1095,7 +1374,7 @@ def _closing(items, dev):
 BGZF_HEADROOM = 1 << 16        # free bytes in front of a BGZF slab's inflated text: room for the line the slab before left unfinished
 
 
-def GetTensorDevice(tensor_fn, num, device, log=True, keep_device=False):
+def GetTensorDevice(tensor_fn, num, device, log=True, keep_device=False, gzip_device=True):
     """GetTensor with the rows parsed on the GPU: generator of (endFlag, c, X_dev, pos), X_dev a [c,33,4,4] fp32 torch
     tensor on `device` (the bits GetTensor gives), pos a PosBatch over the host copy of the text.  The input is cut
     into slabs of whole lines (about `num` rows each, from the first line's length), slab k + 1 is copied to the device
@@ -1108,6 +1387,9 @@ def GetTensorDevice(tensor_fn, num, device, log=True, keep_device=False):
     (cv_inflate_bgzf_dev), so the text never exists on the host -- a slab is then whole members, not whole lines: the
     text behind its last newline is copied in front of the next slab's, the positions come back through
     cv_text_gather_tokens, and only a slab with lines the device left to the host is copied back as text.
+    An ordinary gzip file is a third: the device finds its block starts and inflates it (_gzip_slabs; a slab is then
+    whatever the chain of blocks gives, up to GZIP_TEXT_BYTES of text, and yields several batches).  gzip_device=False
+    keeps such a file on the host inflate, in slabs of about `num` rows.
     keep_device: every batch's `pos` also says where its tokens lie in HBM (pos.device, for GetTrainingSetDevice), which
     keeps the slab's text there for as long as the batch is held."""
     parse = _text_parser()
@@ -1115,7 +1397,12 @@ def GetTensorDevice(tensor_fn, num, device, log=True, keep_device=False):
     dev = _TextSlabDevice(device, cap)
     done, held = _flagged(log), None
     bgzf = _map_bgzf(tensor_fn) if os.environ.get("CV_TEXT") != "stream" else None
-    if bgzf is None:
+    # (a stand-in for the device without the gzip inflate keeps the host stream)
+    gz = _map_gzip(tensor_fn) if gzip_device and bgzf is None and os.environ.get("CV_TEXT") != "stream" and hasattr(dev, "inflate_gzip") else None
+    if gz is not None:
+        source = _gzip_slabs(tensor_fn, gz[0], gz[1], num, dev)
+        upload = lambda slab: (slab.up, slab.end) if isinstance(slab, _GzipText) else (dev.upload(slab), len(slab))
+    elif bgzf is None:
         source = _text_spans(tensor_fn, lambda first_line: _slab_bytes(first_line, num))
         upload = lambda slab: (dev.upload(slab), len(slab))
     else:
@@ -1123,14 +1410,22 @@ def GetTensorDevice(tensor_fn, num, device, log=True, keep_device=False):
         upload = lambda slab: dev.upload_bgzf(slab, BGZF_HEADROOM)
 
     def batches():
-        slabs = _read_ahead(source, 2)                         # (the inflate of slab k + 1 runs beside the staging of slab k)
+        # (the inflate of slab k + 1 runs beside the staging of slab k; the gzip source works on the device itself, on
+        # this thread, under the parse of the slab before)
+        slabs = _read_ahead(source, 2) if gz is None else source
         slab = next(slabs, None)
         up, end = upload(slab) if slab is not None else (None, 0)
-        tail = None                                            # BGZF: (handle, first byte, end) of the line the slab before left unfinished
+        tail = None                                            # compressed: (handle, first byte, end) of the line the slab before left unfinished
         while slab is not None:
             start = 0
-            if bgzf is not None:
-                dev.settle(up, slab, BGZF_HEADROOM)
+            inflated = not isinstance(slab, np.ndarray)        # the text exists on the device only
+            if not inflated and tail is not None:              # the host reader took over in the middle of a line
+                slab = np.concatenate((dev.host_text(tail[0], tail[1], tail[2]), slab))
+                up, end = upload(slab)
+                tail = None
+            if inflated:
+                if bgzf is not None:
+                    dev.settle(up, slab, BGZF_HEADROOM)
                 start = BGZF_HEADROOM
                 if tail is not None:
                     if tail[2] - tail[1] > start:              # one over-long line: more room in front
@@ -1145,7 +1440,7 @@ def GetTensorDevice(tensor_fn, num, device, log=True, keep_device=False):
                 info, status, meta = dev.collect(job)
                 lines = int(info[1])
                 text_line_counts["host"] += int(info[3])
-                if bgzf is None:
+                if not inflated:
                     text = slab[start:]
                 else:
                     text = dev.host_text(up, start, start + int(info[0])) if int(info[3]) else None
@@ -1170,7 +1465,7 @@ def GetTensorDevice(tensor_fn, num, device, log=True, keep_device=False):
                 if lines == 0 or start >= end:
                     break
                 job = dev.parse(up, start)
-            tail = (up, start, end) if bgzf is not None and start < end else None
+            tail = (up, start, end) if inflated and start < end else None
             slab, up, end = nxt, nxt_up, nxt_end
 
     for c, x, pos in _closing(batches(), dev):
@@ -1854,7 +2149,8 @@ def GetTrainingSetDevice(tensor_fn, var_fn, bed_fn, shuffle=True, device=None, n
         b = _TrainsetBuilder(device, names, tables, bed_fn is not None, _estimated_rows(tensor_fn))
         t_join, nbatches = 0.0, 0
         t0 = time.time()
-        batches = GetTensorDevice(tensor_fn, num, device, log=False, keep_device=True)
+        # (an ordinary .gz keeps the host inflate here: the set is built from slabs of about `num` rows)
+        batches = GetTensorDevice(tensor_fn, num, device, log=False, keep_device=True, gzip_device=False)
         try:
             for _end, c, x, pos in batches:
                 if c:

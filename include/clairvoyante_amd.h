@@ -323,6 +323,41 @@ int cv_bgzf_scan(const uint8_t *src, int64_t n, int64_t max_members, int64_t *ta
 int cv_inflate_bgzf_dev(const uint8_t *comp_dev, const int64_t *table_dev, int64_t members, uint8_t *text_dev,
                         int64_t text_cap, uint8_t *status_dev, void *stream);
 
+/* Ordinary gzip (one DEFLATE stream, block starts unknown) on the device (csrc/cv_gzip_dev.hip, cv_gzip_core.hpp).
+ * All bit offsets count from the first byte of comp_dev / src, least significant bit first.  Everything is enqueued on
+ * `stream`; nothing allocates or synchronises.  0 = enqueued, 1 = error (cv_last_error).
+ * cv_gzip_header_at (host): 1 when a non-final dynamic-Huffman block header with three complete codes and a code
+ *   for symbol 256 stands at `bit` of src[0, n).
+ * cv_gzip_chunk_host (host): the decode core's host form over one chunk [start_bit, end_bit) (end_bit < 0: to BFINAL)
+ *   -> CV_GZIP_*; *symbols and *ended (the bit it ended at) set; sym (room for cap symbols) may be null to count.
+ * cv_gzip_find_dev: found_dev[g] = the first such header in bits [first_bit + g * spacing, first_bit + (g + 1) *
+ *   spacing) of comp_dev[0, nbytes) (guess 0 starts one bit later: first_bit itself is the caller's), or -1.
+ * cv_gzip_decode_dev: table_dev[c][6] = start bit, end bit (< 0: to BFINAL), offset in sym_dev, symbols to write,
+ *   bytes of text that exist in front of the chunk (capped at 32768), 0.  sym_dev null: a counting pass, which reads
+ *   the first two and the fifth only.  result_dev[c][4] = symbols, the bit the chunk ended at, CV_GZIP_LANDED (at a
+ *   block header exactly at the end bit) / FINAL (the final block ended) / PASSED (went over the end bit) / BAD (not a
+ *   stream the core vouches for, input exhausted, more symbols than stated), 0.  A symbol is a byte, or 0x8000 | j =
+ *   byte j of the 32 KiB in front of the chunk.  A writing pass never writes outside its [offset, offset + symbols).
+ * cv_gzip_resolve_dev: symbols -> text.  off_dev[0 .. chunks] = where each chunk starts (off_dev[chunks] = total), in
+ *   sym_dev and in text_dev alike; text_dev[-hist, 0) holds the text in front of the first chunk (hist <= 32768).
+ *   *bad_dev is set (never cleared) when a marker reaches in front of the text that exists.
+ * cv_gzip_crc_dev: part_dev[p] = the CRC-32 register after the p-th 1 KiB piece of text_dev[0, n), started from 0;
+ *   pieces are aligned to the END (the first may be short).                                                        */
+#define CV_GZIP_LANDED 1
+#define CV_GZIP_FINAL 2
+#define CV_GZIP_PASSED 3
+#define CV_GZIP_BAD 4
+int cv_gzip_header_at(const uint8_t *src, int64_t n, int64_t bit);
+int cv_gzip_chunk_host(const uint8_t *src, int64_t n, int64_t start_bit, int64_t end_bit, uint16_t *sym, int64_t cap,
+                       int64_t hist, int64_t *symbols, int64_t *ended);
+int cv_gzip_find_dev(const uint8_t *comp_dev, int64_t nbytes, int64_t first_bit, int64_t spacing_bytes, int64_t guesses,
+                     int64_t *found_dev, void *stream);
+int cv_gzip_decode_dev(const uint8_t *comp_dev, int64_t nbytes, const int64_t *table_dev, int64_t chunks, uint16_t *sym_dev,
+                       int64_t sym_cap, int64_t *result_dev, void *stream);
+int cv_gzip_resolve_dev(const uint16_t *sym_dev, const int64_t *off_dev, int64_t chunks, int64_t total, int64_t hist,
+                        uint8_t *text_dev, int32_t *bad_dev, void *stream);
+int cv_gzip_crc_dev(const uint8_t *text_dev, int64_t n, uint32_t *part_dev, void *stream);
+
 /* ---- the labelled training set on the device (csrc/cv_trainset.hip) -------------------------------------------------
  * What utils_v2.GetTrainingArray's per-row loop does (utils_v2.py:62-186), for rows cv_parse_tensor_text_dev left in
  * HBM; the host loop stays the definition of the result.  Every call is enqueued on `stream` and neither allocates nor

@@ -2,12 +2,14 @@
 rows/s for a plain and a gzip-compressed tensor file, with the share of each stage.
     python tools/gpu_callvar_text_probe.py [rows] [parse=device|host]
 parse=... forces one text reader (CV_TEXT_PARSE) for the whole run.  With a ladder,
-    python tools/gpu_callvar_text_probe.py ladder=1000,16384,65536,200000,1000000 [runs=5] [gzmax=1000000]
-one process alternates parse=host and parse=device at every size, plain, .gz and BGZF (the same text re-blocked by
-clairvoyante_amd.bgzf; the device side then inflates it too): a warm-up run of each, then `runs`
-timed runs of each in turn (wall time of callVar.Test behind a loaded model, ending in a device synchronise), rows/s
-as median and range, and which side wins by more than the host side's own range.  kernels=ROWS times the parse
-kernels of one slab, and the inflate of the same slab as BGZF members, beside the forward pass of the same rows."""
+    python tools/gpu_callvar_text_probe.py ladder=1000,16384,65536,200000,1000000 [runs=5] [gzmax=1000000] [forms=plain,gz,bgzf] [gzlevel=6]
+one process alternates parse=host and parse=device at every size, plain, .gz (`gzip -6`: the device side finds its
+block starts and inflates it, the gzip-device route; its column also counts the chunks it inflated and the hand-overs to
+the host) and BGZF (the same text re-blocked by clairvoyante_amd.bgzf; the device side inflates it too): a warm-up run
+of each, then `runs` timed runs of each in turn (wall time of callVar.Test behind a loaded model, ending in a device
+synchronise), rows/s as median and range, and which side wins by more than the host side's own range.  kernels=ROWS
+times the parse kernels of one slab, the inflate of the same slab as BGZF members and as one `gzip -6` stream (find,
+counting pass, writing pass, resolve, CRC), beside the forward pass of the same rows."""
 import cProfile
 import gzip
 import os
@@ -33,7 +35,7 @@ def _write_rows(path, n, x, ngz):
             fh.write(b"\n".join(rows) + b"\n")
 
 
-def ladder(sizes, runs, gzmax):
+def ladder(sizes, runs, gzmax, want_forms=("plain", "gz", "bgzf"), gzlevel=6):
     import torch
     import common
     from oracle import cv_oracle as O
@@ -48,10 +50,11 @@ def ladder(sizes, runs, gzmax):
     for n in sizes:
         txt = os.path.join(tmp, "t%d.txt" % n)
         _write_rows(txt, n, x, ngz)
-        forms = [("plain", txt)]
-        if n <= gzmax:
-            subprocess.check_call("gzip -1 -c %s > %s.gz" % (txt, txt), shell=True)
+        forms = [("plain", txt)] if "plain" in want_forms else []
+        if n <= gzmax and "gz" in want_forms:
+            subprocess.check_call("gzip -%d -c %s > %s.gz" % (gzlevel, txt, txt), shell=True)
             forms.append(("gz", txt + ".gz"))
+        if n <= gzmax and "bgzf" in want_forms:
             bgzf.reblock(txt, txt + ".bgzf.gz", level=1)
             forms.append(("bgzf", txt + ".bgzf.gz"))
         for form, fn in forms:
@@ -59,6 +62,7 @@ def ladder(sizes, runs, gzmax):
                                       ref_fn=None, threads=None, showRef=False, v3=True, v2=False, slim=False)
             rate = {"host": [], "device": []}
             vcf = {}
+            chunks = dict(utils_v2.gzip_chunk_counts)
             for r in range(runs + 1):                       # run 0 of each side warms up
                 for side in ("host", "device"):
                     os.environ["CV_TEXT_PARSE"] = side
@@ -74,9 +78,11 @@ def ladder(sizes, runs, gzmax):
             assert vcf["host"] == vcf["device"], "the two readers disagree"
             h, d = np.array(rate["host"]), np.array(rate["device"])
             wins = np.median(d) > np.median(h) + (h.max() - h.min())
-            print("%8d %-5s %11d | %.3g (%.3g..%.3g) | %.3g (%.3g..%.3g) | %s" % (
+            grew = {k: utils_v2.gzip_chunk_counts[k] - chunks[k] for k in chunks}
+            print("%8d %-5s %11d | %.3g (%.3g..%.3g) | %.3g (%.3g..%.3g) | %s%s" % (
                 n, form, os.path.getsize(fn), np.median(h), h.min(), h.max(), np.median(d), d.min(), d.max(),
-                "device wins" if wins else "device does not win"), flush=True)
+                "device wins" if wins else "device does not win",
+                " | gzip-device: %d chunks, %d hand-overs in %d runs" % (grew["device"], grew["host"], runs + 1) if form == "gz" else ""), flush=True)
             if form != "plain":
                 os.unlink(fn)
         os.unlink(txt)
@@ -145,6 +151,53 @@ def kernels(n):
         assert int((mstat != 1).sum()) == 0 and torch.equal(dst[:len(text)], buf[:len(text)])
         inflates.append(("inflate + CRC, %d members, level %d, %.1f MB" % (len(table), level, len(blob) / 1e6), inflate))
 
+    # the same slab as ONE gzip -6 stream: the kernels of the gzip-device route one by one, tables as the reader builds them
+    import zlib
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    raw = c.compress(text) + c.flush()
+    spacing = int(os.environ.get("CV_GZIP_GUESS_BYTES") or utils_v2.GZIP_GUESS_BYTES)
+    gcomp = torch.frombuffer(bytearray(raw + b"\0" * 8), dtype=torch.uint8).cuda()
+    guesses = -(-len(raw) // spacing)
+    found = torch.empty(guesses, dtype=torch.int64, device="cuda")
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+
+    def find():
+        _lib.check(lib.cv_gzip_find_dev(P(gcomp), len(raw), 0, spacing, guesses, P(found), st))
+    find()
+    f = found.cpu().numpy()
+    starts = np.concatenate(([0], f[f >= 0]))
+    rows = np.zeros((len(starts), 6), dtype=np.int64)
+    rows[:, 0], rows[:, 1], rows[:, 4] = starts, np.append(starts[1:], -1), 32768
+    rows[0, 4] = 0
+    gtab = torch.from_numpy(rows).cuda()
+    gres = torch.zeros((len(starts), 4), dtype=torch.int64, device="cuda")
+
+    def count():
+        _lib.check(lib.cv_gzip_decode_dev(P(gcomp), len(raw), P(gtab), len(starts), None, 0, P(gres), st))
+    count()
+    r = gres.cpu().numpy()
+    assert np.all(r[:-1, 2] == 1) and r[-1, 2] == 2 and int(r[:, 0].sum()) == len(text)
+    off = np.concatenate(([0], np.cumsum(r[:, 0])))
+    rows[:, 2], rows[:, 3] = off[:-1], r[:, 0]
+    gtab2, goff = torch.from_numpy(rows).cuda(), torch.from_numpy(off).cuda()
+    gsym = torch.empty(len(text) + 8, dtype=torch.int16, device="cuda")
+    gtext = torch.zeros(65536 + len(text) + 64, dtype=torch.uint8, device="cuda")
+    gbad = torch.zeros(2 + (len(text) + 1023) // 1024, dtype=torch.int32, device="cuda")
+
+    def write():
+        _lib.check(lib.cv_gzip_decode_dev(P(gcomp), len(raw), P(gtab2), len(starts), P(gsym), len(text), P(gres), st))
+
+    def resolve():
+        _lib.check(lib.cv_gzip_resolve_dev(P(gsym), P(goff), len(starts), len(text), 0, ctypes.c_void_p(gtext.data_ptr() + 65536), P(gbad), st))
+
+    def crc():
+        _lib.check(lib.cv_gzip_crc_dev(ctypes.c_void_p(gtext.data_ptr() + 65536), len(text), ctypes.c_void_p(gbad.data_ptr() + 8), st))
+    write(); resolve(); crc(); torch.cuda.synchronize()
+    assert torch.equal(gtext[65536:65536 + len(text)], buf[:len(text)]) and int(gbad[0]) == 0
+    assert (utils_v2._crc_shift(0xffffffff, len(text)) ^ utils_v2._crc_fold(gbad.cpu().numpy()[2:].view(np.uint32))) ^ 0xffffffff == zlib.crc32(text)
+    tag = "gzip -6, %.1f MB, %d chunks at %d KiB guesses: " % (len(raw) / 1e6, len(starts), spacing >> 10)
+    inflates += [(tag + "find", find), (tag + "counting pass", count), (tag + "writing pass", write), (tag + "resolve", resolve), (tag + "CRC", crc)]
+
     for name, fn in [("index + parse", parse), ("gather of every second row", gather), ("forward pass", forward)] + inflates:
         ms = []
         for r in range(8):
@@ -152,7 +205,7 @@ def kernels(n):
             e0.record(); fn(); e1.record(); torch.cuda.synchronize()
             if r >= 3:
                 ms.append(e0.elapsed_time(e1))
-        print("%d rows, %.1f MB of text: %-48s %.3f ms median (%.3f..%.3f)" % (n, len(text) / 1e6, name, np.median(ms), min(ms), max(ms)))
+        print("%d rows, %.1f MB of text: %-64s %.3f ms median (%.3f..%.3f)" % (n, len(text) / 1e6, name, np.median(ms), min(ms), max(ms)))
     assert tuple(info.cpu().numpy()) == (len(text), n, n, 0)
     m.close()
 
@@ -165,7 +218,8 @@ def main():
     if "kernels" in opts:
         kernels(int(opts["kernels"]))
     if "ladder" in opts:
-        ladder([int(v) for v in opts["ladder"].split(",")], int(opts.get("runs", 5)), int(opts.get("gzmax", 1000000)))
+        ladder([int(v) for v in opts["ladder"].split(",")], int(opts.get("runs", 5)), int(opts.get("gzmax", 1000000)),
+               tuple(opts.get("forms", "plain,gz,bgzf").split(",")), int(opts.get("gzlevel", 6)))
     if "kernels" in opts or "ladder" in opts:
         return
     import common
