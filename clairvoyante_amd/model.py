@@ -190,6 +190,33 @@ class Clairvoyante(object):
                                         ctypes.c_void_p(out16.data_ptr()), self._stream()))
         return out16
 
+    def evaluateCounts(self, X, Y, counts=None):
+        """The evaluation report's counters of a labelled batch (train.EvaluateReport as numbers; layout:
+        include/clairvoyante_amd.h, cv_eval_counts) ADDED to `counts`, a device int64[64] tensor -- allocated and zeroed
+        when None -- which is returned.  X: numpy or a device tensor; Y [n,16]: numpy or a device tensor, compared as
+        float64 when it arrives so and as fp32 otherwise.  The pass and the counting kernel are enqueued on the current
+        stream: no output reaches the host and nothing synchronises (read the counters with .cpu())."""
+        with torch.cuda.device(self.device):
+            x = self._to_dev(X, (33, 4, 4))
+            if not torch.is_tensor(Y):
+                Y = np.asarray(Y)
+                Y = torch.from_numpy(np.ascontiguousarray(Y, dtype=np.float64 if Y.dtype == np.float64 else np.float32))
+            y = Y.to(device=self.device, dtype=torch.float64 if Y.dtype == torch.float64 else torch.float32)
+            y = y.contiguous().reshape(-1, _lib.NUM_OUT)
+            n = x.shape[0]
+            if y.shape[0] != n:
+                raise ValueError("evaluateCounts: %d candidates, %d label rows" % (n, y.shape[0]))
+            if counts is None:
+                counts = torch.zeros(64, dtype=torch.int64, device=self.device)
+            elif not (torch.is_tensor(counts) and counts.device == self.device and counts.dtype == torch.int64
+                      and counts.numel() == 64 and counts.is_contiguous()):
+                raise ValueError("evaluateCounts: counts must be a contiguous int64[64] tensor on %s" % (self.device,))
+            out16 = self.predict_device(x)
+            _lib.check(self._lib.cv_eval_counts(ctypes.c_void_p(out16.data_ptr()), ctypes.c_void_p(y.data_ptr()),
+                                                int(y.dtype == torch.float64), n, ctypes.c_void_p(counts.data_ptr()),
+                                                self._stream()))
+        return counts
+
     # predict(numpy): batches of at least PIPE_MIN candidates go to the device in parts, part k + 1's host-to-device copy on
     # a copy stream under part k's kernels (round 5: one synchronous copy, the pass, one copy back -- nothing overlapped --
     # gave a host caller 8.7 M candidates/s of the device's 18.7).  The copy moves 26 candidates/us, the kernels take 19:

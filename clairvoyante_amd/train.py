@@ -110,6 +110,7 @@ class _BatchStream(object):
         self.utils, self.XC, self.YC, self.total, self.vstart = utils, XC, YC, total, validationStart
         self.rank, self.ws = rank, ws              # data parallel: this rank only decompresses its slice of a batch
         self.vbatch = None                         # validation batch size (None: the reference's predictBatchSize)
+        self.y_dtype = np.float32                  # type of the staged labels (None: as the blocks hold them)
         self.ptr = 0
         self._q = None
         self._stop = None
@@ -171,11 +172,12 @@ class _BatchStream(object):
             import torch
             if torch.is_tensor(X) and torch.is_tensor(Y) and X.is_cuda and Y.is_cuda:
                 return X, Y, None                  # slices of a set that lies in HBM: nothing to copy
+            y_dtype = self.y_dtype or (Y.dtype if Y.dtype in (np.float32, np.float64) else np.float64)
             with torch.cuda.device(device):
                 side = torch.cuda.Stream(device=device)
                 with torch.cuda.stream(side):
                     xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(device, non_blocking=True)
-                    yd = torch.from_numpy(np.ascontiguousarray(Y, dtype=np.float32)).to(device, non_blocking=True)
+                    yd = torch.from_numpy(np.ascontiguousarray(Y, dtype=y_dtype)).to(device, non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(side)
             ev.synchronize()                       # producer thread: the host arrays may go once the copy is done
@@ -397,13 +399,72 @@ def TrainAll(args, m, utils):
     logging.info("Best validation loss at batch: %d" % history[0][1])
 
     logging.info("Testing on the training and validation dataset ...")
+    if eval_route(m) == "device":
+        XC, YC = resident_dataset(m, utils, total, XC, YC, once=True)
     PredictAndReport(m, utils, total, XC, YC)
+
+
+EVAL_PASS = 65536          # candidates per pass of the device route (the counts do not depend on it)
+
+
+def eval_route(m):
+    """Which side computes the evaluation report: "device" for a real model (it has evaluateCounts and takes batches that
+    lie in HBM), "host" for a mock or foreign model object.  CV_EVAL=host|device forces a side for a real model."""
+    forced = os.environ.get("CV_EVAL")
+    if forced and forced not in ("host", "device"):
+        raise ValueError("CV_EVAL must be 'host' or 'device', got %r" % forced)
+    if not (hasattr(m, "evaluateCounts") and getattr(m, "accepts_device_batches", False)):
+        return "host"
+    return forced or "device"
+
+
+def resident_dataset(m, utils, total, XC, YC, once=False):
+    """(XC, YC) decoded ONCE into HBM (utils.resident_from_blocks) for a real model on one rank when the set fits there;
+    the inputs unchanged otherwise.  For callers that walk the same set again and again.  once: the caller walks it one
+    time -- only a set of a single pass is then decoded ahead (there is nothing to overlap, and no thread is started);
+    a larger one is streamed, its decoding and copies under the kernels (profiles/r10/evaluate_device.txt: resident wins
+    at 16 384 and 65 536 candidates, streamed from 200 000 up)."""
+    from . import parallel
+    if not getattr(m, "accepts_device_batches", False) or not hasattr(utils, "resident_from_blocks") \
+            or parallel.world()[1] != 1 or (once and total > EVAL_PASS):
+        return XC, YC
+    return utils.resident_from_blocks(total, XC, YC, getattr(m, "device", None))
+
+
+def _counts_on_device(m, utils, total, XC, YC):
+    """The 64 counters of the report (include/clairvoyante_amd.h, cv_eval_counts) of the whole set, accumulated in ONE
+    device tensor over passes of EVAL_PASS candidates and fetched once at the end; no prediction reaches the host.
+    The passes come from the batch stream: its producer threads decode pass k + 2 and copy pass k + 1 to HBM under the
+    kernels of pass k; passes of a set that already lies in HBM are views, taken in place."""
+    import torch
+    device = m.device
+    stream = _BatchStream(utils, XC, YC, total, total)
+    stream.y_dtype = None                            # the labels are compared in the type the blocks hold: float64
+    if not all(torch.is_tensor(getattr(c, "t", None)) for c in (XC, YC)):
+        stream.prefetch(EVAL_PASS, lambda ptr: EVAL_PASS, device)
+    try:
+        with torch.cuda.device(device):
+            counts = torch.zeros(64, dtype=torch.int64, device=device)
+            last = total <= 0
+            while not last:
+                X, Y, _start, n, last = stream.fetch(EVAL_PASS)
+                if n > 0:
+                    m.evaluateCounts(X, Y, counts)
+            return counts.cpu().numpy()             # the one fetch: 512 bytes
+    finally:
+        stream._cancel()
 
 
 def PredictAndReport(m, utils, total, XC, YC):
     """train.py:163-218 / evaluate.py:51-107: predict the whole set in batches of 1 000 (the first
-    batch's end flag is not looked at), then the accuracy / confusion-matrix report"""
+    batch's end flag is not looked at), then the accuracy / confusion-matrix report.  With a real model the report's
+    counters are computed where the predictions are (eval_route)."""
     t_pred = time.time()
+    if eval_route(m) == "device":
+        counts = _counts_on_device(m, utils, total, XC, YC)
+        logging.info("Prediciton time elapsed: %.2f s" % (time.time() - t_pred))
+        log_evaluation(counts)
+        return
     step = param.predictBatchSize
     if getattr(m, "accepts_device_batches", False):
         step *= 16          # same concatenated result; a call on 1 000 candidates is latency-bound on the GPU (DESIGN.md 4)
@@ -426,19 +487,42 @@ def PredictAndReport(m, utils, total, XC, YC):
 
 def EvaluateReport(bases, zs, ts, ls, YArray):
     """train.py:190-218: top-1/top-2 base accuracy and the three confusion matrices"""
-    logging.info("Version 2 model, evaluation on base change:")
+    log_evaluation(evaluation_counts_host(bases, zs, ts, ls, YArray))
+
+
+# the report's counters: [0] candidates, [1] top-1, [2] top-2, then the matrices row = truth (include/clairvoyante_amd.h)
+_EVAL_HEADS = (("Zygosity", 4, 6, 4), ("variant type", 6, 10, 8), ("indel length", 10, 16, 24))   # title, Y columns, offset
+
+
+def evaluation_counts_host(bases, zs, ts, ls, YArray):
+    """train.py:190-218 as numbers -> np.int64[64] in the layout of cv_eval_counts: the definition the device route is
+    held to"""
     n = len(bases)
+    counts = np.zeros(64, dtype=np.int64)
     truth = np.argmax(YArray[:n, 0:4], axis=1)
     order = np.argsort(bases, axis=1, kind="stable")[:, ::-1]
     top1 = int(np.sum(order[:, 0] == truth))
     top2 = top1 + int(np.sum((order[:, 0] != truth) & (order[:, 1] == truth)))
-    logging.info("all/top1/top2/top1p/top2p: %d/%d/%d/%.2f/%.2f" %
-                 (n, top1, top2, float(top1) / n * 100, float(top2) / n * 100))
-    for title, pred, lo, hi in (("Zygosity", zs, 4, 6), ("variant type", ts, 6, 10), ("indel length", ls, 10, 16)):
-        logging.info("Version 2 model, evaluation on %s:" % title)
+    counts[0:3] = n, top1, top2
+    for (_title, lo, hi, off), pred in zip(_EVAL_HEADS, (zs, ts, ls)):
         k = hi - lo
         ed = np.zeros((k, k), dtype=np.int64)
         np.add.at(ed, (np.argmax(YArray[:n, lo:hi], axis=1), np.argmax(pred, axis=1)), 1)
+        counts[off:off + k * k] = ed.ravel()
+    return counts
+
+
+def log_evaluation(counts):
+    """the report's log lines (train.py:190-218) from the 64 counters"""
+    counts = np.asarray(counts, dtype=np.int64)
+    logging.info("Version 2 model, evaluation on base change:")
+    n, top1, top2 = int(counts[0]), int(counts[1]), int(counts[2])
+    logging.info("all/top1/top2/top1p/top2p: %d/%d/%d/%.2f/%.2f" %
+                 (n, top1, top2, float(top1) / n * 100, float(top2) / n * 100))
+    for title, lo, hi, off in _EVAL_HEADS:
+        logging.info("Version 2 model, evaluation on %s:" % title)
+        k = hi - lo
+        ed = counts[off:off + k * k].reshape(k, k)
         for r in range(k):
             logging.info("\t".join([str(ed[r][j]) for j in range(k)]))
 

@@ -2293,3 +2293,46 @@ def DecompressArray(array, start, num, maximum):
     if leftEnd != 0 or num % bs != 0:
         out = out[leftEnd:(leftEnd + num)]
     return out, num, endFlag
+
+
+RESIDENT_STEP = 65536       # candidates per decode-and-copy step of resident_from_blocks
+
+
+def resident_from_blocks(total, XC, YC, device=None):
+    """The block lists of a .bin decoded ONCE into HBM -> (ResidentBlocks of X fp32, ResidentBlocks of Y in the type its
+    blocks hold: float64), for consumers that walk the set more than once (evaluateListOfModels, calTrainDevDiff) or
+    count on the device (train.PredictAndReport).  Applies when a GPU is present and total * (2112 + 128) bytes fit into
+    half of the free device memory (the rule, and the TRAINSET_FREE_BYTES override, of trainset_host_reason); returns
+    (XC, YC) unchanged otherwise -- and for lists that already lie there -- and the consumers then stream.
+    Step k + 1 is decoded by the host threads while step k crosses to the device."""
+    if isinstance(XC, ResidentBlocks) or isinstance(YC, ResidentBlocks) or total <= 0 or not _gpu_present():
+        return XC, YC
+    import torch
+    free = TRAINSET_FREE_BYTES
+    with torch.cuda.device(device):
+        if free is None:
+            free = torch.cuda.mem_get_info()[0]
+        if total * (_ROW_BYTES + 16 * 8) > free // 2:
+            return XC, YC
+        dev = torch.device("cuda", torch.cuda.current_device())
+        X = Y = None
+        pending = None                                # (event, host arrays) of the copy in flight
+        for ptr in range(0, total, RESIDENT_STEP):
+            xb, xn, _ = DecompressArray(XC, ptr, RESIDENT_STEP, total)
+            yb, yn, _ = DecompressArray(YC, ptr, RESIDENT_STEP, total)
+            if xn != yn:
+                raise _lib.CvError("Inconsistency between decompressed arrays: %d/%d" % (xn, yn))
+            xb = np.ascontiguousarray(xb, dtype=np.float32)
+            yb = np.ascontiguousarray(yb, dtype=yb.dtype if yb.dtype in (np.float32, np.float64) else np.float64)
+            if X is None:
+                X = torch.empty((total,) + xb.shape[1:], dtype=torch.float32, device=dev)
+                Y = torch.empty((total,) + yb.shape[1:], dtype=torch.from_numpy(yb[:0]).dtype, device=dev)
+            if pending is not None:
+                pending[0].synchronize()              # its page-locked buffers may go back to their pool
+            X[ptr:ptr + xn].copy_(torch.from_numpy(xb), non_blocking=True)
+            Y[ptr:ptr + yn].copy_(torch.from_numpy(yb), non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            pending = (ev, xb, yb)
+        pending[0].synchronize()
+    return ResidentBlocks(X), ResidentBlocks(Y)

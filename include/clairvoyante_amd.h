@@ -91,6 +91,30 @@ int cv_forward(cv_model *m, const float *x_dev, int64_t n, float *out16_dev, voi
 int cv_call_postproc(cv_model *m, const float *x_dev, const float *out16_dev, int64_t n,
                      int32_t *call_dev, float *qual_dev, void *stream);
 
+/* Device side of the evaluation report (evaluate.py:78-107, train.EvaluateReport): ADDS what n candidates contribute
+ * to counts_dev[64] (int64, on the device, 8-byte aligned; the caller zeroes it):
+ *   [0] candidates, [1] top-1 hits, [2] top-2 hits of the base head, [3] unused,
+ *   [4..8)   zygosity      2 x 2, row = truth, column = prediction,
+ *   [8..24)  variant type  4 x 4,
+ *   [24..60) indel length  6 x 6,
+ *   [60..64) untouched.
+ * out16_dev [n,16] fp32 as cv_forward writes it; y_dev [n,16] labels, fp32 (y_is_f64 == 0) or float64, compared in
+ * that type; both 16-byte aligned.  The truth index of a head and the prediction of the three softmax heads are
+ * np.argmax (the first maximum; NaN counts as the maximum, the first NaN wins); the base head is ordered as
+ * argsort(kind="stable")[::-1] orders it (descending, NaN above every number, of equal values -- +0 and -0 among
+ * them -- the higher index first): top-1 counts truth == first, top-2 truth == first or second.
+ * No model handle: the kernel runs on the current device, enqueued on `stream`; nothing synchronises or allocates.
+ * n == 0 returns 0 and touches nothing; n < 0, a null pointer or a misaligned one returns 1.                        */
+#define CV_EVAL_COUNTS 64
+#define CV_EVAL_ALL 0
+#define CV_EVAL_TOP1 1
+#define CV_EVAL_TOP2 2
+#define CV_EVAL_ZYGOSITY 4
+#define CV_EVAL_VARTYPE 8
+#define CV_EVAL_INDEL 24
+int cv_eval_counts(const float *out16_dev, const void *y_dev, int y_is_f64, int64_t n, int64_t *counts_dev,
+                   void *stream);
+
 /* Host half of callVar.Output (callVar.py:72-153): the VCF records of n candidates from the decisions of
  * cv_call_postproc -- quality int(-4.343*log((p2+1e-300)/(p1+1e-300))), SNP / REF allele, inserted bases and
  * indel-length guess from the tensor, <INS>/<DEL> + SVTYPE, LENGUESS, GT, FILTER, "%.4f" allele fraction -- as text,
