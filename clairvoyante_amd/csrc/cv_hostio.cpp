@@ -653,6 +653,69 @@ extern "C" int cv_blosc_compress_lz4(const uint8_t *src, int64_t n, int typesize
     return 0;
 }
 
+// c-blosc's own layout: blocks of `blocksize` bytes, each shuffled on its own and -- unless it is the leftover or has
+// fewer than 128 elements -- split into `typesize` byte-plane streams (the rule cv_blosc_decompress reads).  The device
+// decoder takes one wave per stream, so a chunk written this way is many short chains instead of one long one.
+extern "C" int64_t cv_blosc_blocks_bound(int64_t n, int typesize, int64_t blocksize)
+{
+    if (n < 0 || typesize < 1 || typesize > 16 || blocksize < 1) return -1;
+    if (blocksize > typesize) blocksize = blocksize / typesize * typesize;
+    const int64_t nblocks = (n + blocksize - 1) / blocksize + 1;
+    return n + 16 + 4 * nblocks * (1 + typesize) + 64;
+}
+
+extern "C" int cv_blosc_compress_lz4_blocks(const uint8_t *src, int64_t n, int typesize, int64_t blocksize, uint8_t *dst,
+                                            int64_t dstcap, int64_t *clen)
+{
+    if (!src || !dst || !clen || n < 0 || n > 0x7fffff00) { cv_set_error("blosc: bad compress arguments"); return 1; }
+    if (typesize < 1 || typesize > 16 || blocksize < typesize || blocksize > 0x7fffff00) {
+        cv_set_error("blosc: the block writer takes 1 <= typesize <= 16 and a blocksize of at least one element");
+        return 1;
+    }
+    if (dstcap < cv_blosc_blocks_bound(n, typesize, blocksize)) { cv_set_error("blosc: destination too small"); return 1; }
+    // c-blosc's own rule (and its decoder's demand): no block larger than the data, whole elements per block
+    if (blocksize > n) blocksize = n > 0 ? n : 1;
+    if (blocksize > typesize) blocksize = blocksize / typesize * typesize;
+    const bool sh = typesize > 1;
+    dst[0] = 2; dst[1] = 1; dst[3] = (uint8_t)typesize;
+    wr32(dst + 4, (int32_t)n); wr32(dst + 8, (int32_t)blocksize);
+    int flags = (1 << 5) | (sh ? 1 : 0);
+    int64_t total = -1;
+    if (n >= 64) {
+        const int64_t nblocks = (n + blocksize - 1) / blocksize;
+        uint8_t *tmp = (uint8_t *)malloc((size_t)(blocksize < n ? blocksize : n));
+        if (!tmp) { cv_set_error("blosc: out of memory"); return 1; }
+        int64_t op = 16 + 4 * nblocks;
+        for (int64_t b = 0; b < nblocks; b++) {
+            int32_t bsize = (int32_t)blocksize;
+            bool leftover = false;
+            if (b == nblocks - 1 && n % blocksize) { bsize = (int32_t)(n % blocksize); leftover = true; }
+            const uint8_t *blk = src + b * blocksize;
+            if (sh) { shuffle_bytes(blk, tmp, bsize, typesize); blk = tmp; }
+            const int nsplits = (blocksize / typesize >= 128 && !leftover) ? typesize : 1;
+            const int32_t neblock = bsize / nsplits;
+            wr32(dst + 16 + 4 * b, (int32_t)op);
+            for (int s = 0; s < nsplits; s++) {
+                int c = lz4_compress(blk + (size_t)s * neblock, neblock, dst + op + 4, neblock - 1);
+                if (c <= 0 || c >= neblock) { memcpy(dst + op + 4, blk + (size_t)s * neblock, (size_t)neblock); c = neblock; }
+                wr32(dst + op, c);
+                op += 4 + c;
+            }
+        }
+        free(tmp);
+        if (op < 16 + n) total = op;
+    }
+    if (total < 0) {                                   // incompressible / tiny: memcpy'd chunk
+        flags = (1 << 5) | 0x2;
+        memcpy(dst + 16, src, (size_t)n);
+        total = 16 + n;
+    }
+    dst[2] = (uint8_t)flags;
+    wr32(dst + 12, (int32_t)total);
+    *clen = total;
+    return 0;
+}
+
 // ---- CRC32C (Castagnoli) for the TensorFlow checkpoint bundle -------------------------------
 namespace {
 uint32_t crc_table[8][256];

@@ -31,6 +31,8 @@ def Convert(args, utils):
 def Run(args):
     from . import utils_v2 as utils
     utils.SetupEnv()
+    if getattr(args, "blosc_blocksize", None):
+        utils.PACK_BLOCKSIZE = int(args.blosc_blocksize)
     Convert(args, utils)
 
 
@@ -42,6 +44,9 @@ def main():
         parser.add_argument(flag, type=str, default=default, help=text)
     for flag, default, text in (("--v3", True, "Use Clairvoyante version 3"), ("--v2", False, "Use Clairvoyante version 2")):
         parser.add_argument(flag, type=param.str2bool, nargs='?', const=True, default=default, help=text)
+    parser.add_argument("--blosc_blocksize", type=int, default=None,
+                        help="Write c-blosc's multi-block layout with blocks of this many bytes (e.g. 65536: many short "
+                             "streams per chunk, what the device decoder likes); default: one stream per chunk")
     args = parser.parse_args()
     if not sys.argv[1:]:
         parser.print_help()

@@ -119,7 +119,25 @@ class _BatchStream(object):
         self._cancel()
         self.ptr = 0
 
-    def _fetch_at(self, ptr, size):
+    def _decode(self, blocks, ptr, size, device, dtype):
+        """DecompressArray -- on the device, straight into HBM, where the producer stages there and the rule says so
+        (utils.bin_decode_route); the batch is complete when this returns, in the type the staged copy would have"""
+        if device is not None and hasattr(self.utils, "bin_decode_route") and not hasattr(blocks, "t"):
+            chunks = (ptr % param.bloscBlockSize + size + param.bloscBlockSize - 1) // param.bloscBlockSize
+            if self.utils.bin_decode_route(blocks, chunks) == "device":
+                got = self.utils.DecompressArrayDevice(blocks, ptr, size, self.total, device)
+                if got is not None:
+                    import torch
+                    t = got[0]
+                    if dtype is not None:
+                        t = t.to(torch.from_numpy(np.empty(0, dtype=dtype)).dtype)
+                    elif t.dtype not in (torch.float32, torch.float64):
+                        t = t.to(torch.float64)
+                    torch.cuda.current_stream(t.device).synchronize()
+                    return t, got[1], got[2]
+        return self.utils.DecompressArray(blocks, ptr, size, self.total)
+
+    def _fetch_at(self, ptr, size, device=None):
         """-> (X, Y, start, count of the WHOLE batch, last); with ws > 1 X / Y hold this rank's slice only"""
         if self.ws > 1:
             from . import parallel
@@ -131,8 +149,8 @@ class _BatchStream(object):
             if xn != yn:
                 sys.exit("Inconsistency between decompressed arrays: %d/%d" % (xn, yn))
             return X, Y, ptr, n, last
-        X, xn, xe = self.utils.DecompressArray(self.XC, ptr, size, self.total)
-        Y, yn, ye = self.utils.DecompressArray(self.YC, ptr, size, self.total)
+        X, xn, xe = self._decode(self.XC, ptr, size, device, np.float32)
+        Y, yn, ye = self._decode(self.YC, ptr, size, device, self.y_dtype)
         if xn != yn or xe != ye:
             sys.exit("Inconsistency between decompressed arrays: %d/%d" % (xn, yn))
         return X, Y, ptr, xn, xe != 0
@@ -205,7 +223,7 @@ class _BatchStream(object):
             try:
                 ptr, size = start_ptr, first_size
                 while not stop.is_set():
-                    X, Y, st, n, last = self._fetch_at(ptr, size)
+                    X, Y, st, n, last = self._fetch_at(ptr, size, device)
                     if not put(out_q, ((ptr, size), (X, Y, st, n, last), None)) or last:
                         break
                     ptr += n

@@ -1488,17 +1488,33 @@ def blosc_decompress(chunk):
     return out.raw[:n]
 
 
-def blosc_compress(data, typesize):
+PACK_BLOCKSIZE = None       # tensor2Bin --blosc_blocksize: pack_array's blocksize when its caller names none
+
+
+def blosc_compress(data, typesize, blocksize=None):
+    """blocksize None: one unsplit LZ4 stream per chunk (the writer this project has always had).  A number: c-blosc's own
+    layout, blocks of that many bytes split into `typesize` byte-plane streams (cv_blosc_compress_lz4_blocks)."""
     lib = _lib.load()
-    out = ctypes.create_string_buffer(len(data) + 64)
     clen = ctypes.c_int64()
-    _lib.check(lib.cv_blosc_compress_lz4(data, len(data), int(typesize), out, len(out), ctypes.byref(clen)))
+    if blocksize is None:
+        out = ctypes.create_string_buffer(len(data) + 64)
+        _lib.check(lib.cv_blosc_compress_lz4(data, len(data), int(typesize), out, len(out), ctypes.byref(clen)))
+        return out.raw[:clen.value]
+    cap = lib.cv_blosc_blocks_bound(len(data), int(typesize), int(blocksize))
+    if cap < 0:
+        raise _lib.CvError("blosc: the block writer takes 1 <= typesize <= 16 and a positive blocksize")
+    out = ctypes.create_string_buffer(int(cap))
+    _lib.check(lib.cv_blosc_compress_lz4_blocks(data, len(data), int(typesize), int(blocksize), out, len(out), ctypes.byref(clen)))
     return out.raw[:clen.value]
 
 
-def pack_array(arr):
+def pack_array(arr, blocksize=None):
     """blosc.pack_array: compress(pickle.dumps(array, HIGHEST_PROTOCOL), typesize=itemsize)"""
-    return blosc_compress(pickle.dumps(arr, pickle.HIGHEST_PROTOCOL), arr.itemsize)
+    if blocksize is None:
+        blocksize = PACK_BLOCKSIZE
+    if blocksize is not None and not 1 <= arr.itemsize <= 16:
+        blocksize = None                      # (string arrays: c-blosc neither splits nor does this writer take them)
+    return blosc_compress(pickle.dumps(arr, pickle.HIGHEST_PROTOCOL), arr.itemsize, blocksize)
 
 
 def unpack_array(chunk):
@@ -2295,6 +2311,201 @@ def DecompressArray(array, start, num, maximum):
     return out, num, endFlag
 
 
+# ---- the same blocks decoded on the device (csrc/cv_blosc_dev.hip) ----------------------
+bin_decode_chunk_counts = {"device": 0, "host": 0}
+
+# Candidates per call from which the device route wins in every run of tools/gpu_bin_decode_probe.py against the host
+# route on the same box, per layout of the set; None = it wins nowhere (or has not been measured): host.
+BIN_DECODE_FLOOR = {"cblosc": None, "own": None, "own64k": None}
+
+
+def bin_decode_counts():
+    """chunks decoded on the device / handed to the host decoder by DecompressArrayDevice so far"""
+    return dict(bin_decode_chunk_counts)
+
+
+def bin_layout(array):
+    """which writer's layout a block list has, from its first chunk's header: "own" (one unsplit stream), "cblosc"
+    (blocks of 1 MiB and more, split) or "own64k" (finer blocks); None when there is nothing to read"""
+    try:
+        head = bytes(array[0][:16]) if not isinstance(array[0], str) else array[0][:16].encode("latin1")
+    except (IndexError, TypeError):
+        return None
+    if len(head) < 16:
+        return None
+    if head[2] & 0x10:
+        return "own"
+    nbytes, blocksize = int.from_bytes(head[4:8], "little"), max(1, int.from_bytes(head[8:12], "little"))
+    return "cblosc" if -(-nbytes // blocksize) <= 2 else "own64k"
+
+
+def bin_decode_route(array, chunks):
+    """-> "host" or "device" for a DecompressArray call over `chunks` blocks of `array`.  CV_BIN_DECODE=host|device
+    forces a side (device still needs a GPU and a plain block list)."""
+    want = os.environ.get("CV_BIN_DECODE", "")
+    if want not in ("", "host", "device"):
+        raise _lib.CvError("CV_BIN_DECODE must be host or device, not %r" % want)
+    if isinstance(array, ResidentBlocks) or want == "host" or not _gpu_present():
+        return "host"
+    if want == "device":
+        return "device"
+    floor = BIN_DECODE_FLOOR.get(bin_layout(array))
+    return "device" if floor is not None and chunks * param.bloscBlockSize >= floor else "host"
+
+
+class _BinDecodeBuffers(object):
+    """the work buffers of DecompressArrayDevice on one device, kept between calls and grown when needed: the pinned
+    slab the compressed chunks are gathered into, its copy in HBM, the tables, the byte-plane scratch"""
+
+    def __init__(self, dev):
+        import threading
+        self.dev = dev
+        self.lock = threading.Lock()
+        self.t = {}
+        self.pending = None                   # event of the last copy out of the pinned buffers
+
+    def get(self, name, nbytes, pinned=False):
+        import torch
+        t = self.t.get(name)
+        if t is None or t.numel() < nbytes:
+            cap = max(int(nbytes) * 5 // 4, 4096)
+            t = torch.empty(cap, dtype=torch.uint8, pin_memory=True) if pinned else torch.empty(cap, dtype=torch.uint8, device=self.dev)
+            self.t[name] = t
+        return t
+
+
+_bin_decode_buffers = {}
+
+
+def _host_window(blocks, key):
+    """what DecompressArray makes of these blocks (before its slicing): one array, or its exception"""
+    out = _unpack_into_one(blocks, key)
+    if out is None:
+        parts = unpack_arrays(blocks)
+        out = np.concatenate(parts[:]) if len(parts) > 1 else parts[0]
+    return out
+
+
+def DecompressArrayDevice(array, start, num, maximum, device=None):
+    """DecompressArray with the blocks decoded on the device -> (torch tensor in HBM, count, endFlag): the same clipping,
+    slicing and end flag, the dtype the blocks hold.  The compressed chunks are gathered into one pinned slab and cross in
+    one copy; cv_blosc_decode_dev and cv_blosc_unpack_dev write the window; the per-chunk status (a few bytes) is the
+    only synchronisation.  A chunk the plan refused or the device handed back is decoded by the host into the same
+    place, and a window the host's direct path does not take either goes through unpack_arrays: the same array or the
+    same exception as DecompressArray.  None: no GPU, or not the plain layout (string arrays) -- use the host path."""
+    endFlag = 0
+    if start + num >= maximum:
+        num = maximum - start
+        endFlag = 1
+    if isinstance(array, ResidentBlocks):
+        return array.t[start:start + num], num, endFlag
+    if not _gpu_present():
+        return None
+    import torch
+    bs = param.bloscBlockSize
+    leftEnd = start % bs
+    first = int(start / bs)
+    last = int((start + num - 1) / bs)
+    key = (id(array), len(array), bytes(array[0][:48]) if len(array) and not isinstance(array[0], str) else None)
+    blocks = array[first:last + 1]
+    n = len(blocks)
+    lay = _block_layout.get(key) if key[2] is not None else None
+    if lay is None:
+        a0 = unpack_array(blocks[0]) if n else None
+        if not isinstance(a0, np.ndarray) or a0.ndim < 1 or not a0.flags.c_contiguous or a0.dtype.kind not in "fiub" \
+                or len(a0) != bs:
+            return None
+        lay = (a0.dtype, a0.shape[1:])
+        if key[2] is not None:
+            if len(_block_layout) > 64:
+                _block_layout.clear()
+            _block_layout[key] = lay
+    dtype, ishape = lay
+    item = int(np.prod(ishape, dtype=np.int64)) * dtype.itemsize
+    block_bytes = bs * item
+    tdtype = torch.from_numpy(np.empty(0, dtype=dtype)).dtype
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        dev = torch.device("cuda", torch.cuda.current_device())
+        bufs = _bin_decode_buffers.get(dev.index)
+        if bufs is None:
+            bufs = _bin_decode_buffers[dev.index] = _BinDecodeBuffers(dev)
+        raw = [c.encode("latin1") if isinstance(c, str) else c for c in blocks]
+        hold = [np.frombuffer(r, dtype=np.uint8) for r in raw]
+        src = (ctypes.c_void_p * n)(*[h.ctypes.data for h in hold])
+        clen = (ctypes.c_int64 * n)(*[len(h) for h in hold])
+        # a block that is what it should be holds block_bytes and a pickle's head and tail; 16 streams per blosc block
+        max_nbytes = block_bytes + 4096
+        max_streams = n * 4096
+        srows = np.empty((max_streams, 5), dtype=np.int64)
+        crows = np.zeros((n, 10), dtype=np.int64)
+        ns, comp_bytes, scratch_bytes = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        refused = lib.cv_blosc_plan(src, clen, n, max_nbytes, max_streams, srows.ctypes.data_as(ctypes.c_void_p),
+                                    crows.ctypes.data_as(ctypes.c_void_p), ctypes.byref(ns), ctypes.byref(comp_bytes),
+                                    ctypes.byref(scratch_bytes))
+        if refused < 0:
+            _lib.check(1)
+        ns, comp_bytes, scratch_bytes = ns.value, comp_bytes.value, scratch_bytes.value
+        srows = srows[:ns]
+        tab_bytes = srows.nbytes + crows.nbytes
+        out = torch.empty((n * bs,) + tuple(ishape), dtype=tdtype, device=dev)
+        with bufs.lock:
+            if bufs.pending is not None:
+                bufs.pending.synchronize()        # the pinned buffers are free again
+            slab = bufs.get("slab_host", comp_bytes + tab_bytes + 16, pinned=True)
+            sl = slab.numpy()
+            tab_at = (comp_bytes + 15) & ~15
+            for i in range(n):
+                if not crows[i, 7]:
+                    o = int(crows[i, 8])
+                    sl[o:o + len(hold[i])] = hold[i]
+            sl[tab_at:tab_at + srows.nbytes] = srows.reshape(-1).view(np.uint8)
+            sl[tab_at + srows.nbytes:tab_at + tab_bytes] = crows.reshape(-1).view(np.uint8)
+            total = tab_at + tab_bytes
+            comp = bufs.get("slab_dev", total)
+            comp[:total].copy_(slab[:total], non_blocking=True)
+            bufs.pending = torch.cuda.Event()
+            bufs.pending.record()
+            scratch = bufs.get("scratch", scratch_bytes + 16)
+            state = bufs.get("state", ns + 16 + n * 16)     # stream status | lens int64[n] | status int32[n]
+            lens_at = (ns + 15) & ~15
+            st_at = lens_at + 8 * n
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            base = comp.data_ptr()
+            _lib.check(lib.cv_blosc_decode_dev(base, comp_bytes, base + tab_at, ns, scratch.data_ptr(), scratch_bytes,
+                                               state.data_ptr(), stream))
+            _lib.check(lib.cv_blosc_unpack_dev(base + tab_at + srows.nbytes, n, state.data_ptr(), ns, scratch.data_ptr(),
+                                               scratch_bytes, out.data_ptr(), block_bytes, state.data_ptr() + lens_at,
+                                               state.data_ptr() + st_at, stream))
+            got = state[lens_at:st_at + 4 * n].cpu().numpy()    # the only synchronisation
+        lens = got[:8 * n].view(np.int64).copy()
+        status = got[8 * n:].view(np.int32)
+        bad = [i for i in range(n) if status[i]]
+        bin_decode_chunk_counts["device"] += n - len(bad)
+        bin_decode_chunk_counts["host"] += len(bad)
+        whole = None
+        for i in bad:
+            # the host decoder on this chunk alone, under the rule for its place in the window
+            one = np.empty(block_bytes, dtype=np.uint8)
+            l1, s1 = (ctypes.c_int64 * 1)(), (ctypes.c_int32 * 1)()
+            rc = lib.cv_blosc_unpack_blocks((ctypes.c_void_p * 1)(src[i]), (ctypes.c_int64 * 1)(clen[i]), 1,
+                                            one.ctypes.data_as(ctypes.c_void_p), block_bytes, l1, s1)
+            if rc != 0 or (i < n - 1 and l1[0] != block_bytes):
+                whole = _host_window(blocks, key)
+                break
+            lens[i] = l1[0]
+            out.view(torch.uint8).reshape(-1)[i * block_bytes:i * block_bytes + l1[0]].copy_(torch.from_numpy(one[:l1[0]]))
+        if whole is None and lens[n - 1] % item:
+            whole = _host_window(blocks, key)
+        if whole is not None:
+            out = torch.from_numpy(np.ascontiguousarray(whole)).to(dev)
+        else:
+            out = out[:(n - 1) * bs + int(lens[n - 1]) // item]
+        if leftEnd != 0 or num % bs != 0:
+            out = out[leftEnd:(leftEnd + num)]
+        return out, num, endFlag
+
+
 RESIDENT_STEP = 65536       # candidates per decode-and-copy step of resident_from_blocks
 
 
@@ -2318,6 +2529,21 @@ def resident_from_blocks(total, XC, YC, device=None):
         X = Y = None
         pending = None                                # (event, host arrays) of the copy in flight
         for ptr in range(0, total, RESIDENT_STEP):
+            chunks = min(RESIDENT_STEP, total - ptr) // param.bloscBlockSize + 1
+            if bin_decode_route(XC, chunks) == "device":
+                # the compressed bytes cross instead: no pinned decode buffer, the blocks are decoded where they will lie
+                xd = DecompressArrayDevice(XC, ptr, RESIDENT_STEP, total, dev)
+                yd = DecompressArrayDevice(YC, ptr, RESIDENT_STEP, total, dev) if xd is not None else None
+                if xd is not None and yd is not None:
+                    if xd[1] != yd[1]:
+                        raise _lib.CvError("Inconsistency between decompressed arrays: %d/%d" % (xd[1], yd[1]))
+                    if X is None:
+                        ydt = yd[0].dtype if yd[0].dtype in (torch.float32, torch.float64) else torch.float64
+                        X = torch.empty((total,) + tuple(xd[0].shape[1:]), dtype=torch.float32, device=dev)
+                        Y = torch.empty((total,) + tuple(yd[0].shape[1:]), dtype=ydt, device=dev)
+                    X[ptr:ptr + xd[1]].copy_(xd[0])
+                    Y[ptr:ptr + yd[1]].copy_(yd[0])
+                    continue
             xb, xn, _ = DecompressArray(XC, ptr, RESIDENT_STEP, total)
             yb, yn, _ = DecompressArray(YC, ptr, RESIDENT_STEP, total)
             if xn != yn:
@@ -2334,5 +2560,6 @@ def resident_from_blocks(total, XC, YC, device=None):
             ev = torch.cuda.Event()
             ev.record()
             pending = (ev, xb, yb)
-        pending[0].synchronize()
+        if pending is not None:
+            pending[0].synchronize()
     return ResidentBlocks(X), ResidentBlocks(Y)

@@ -451,6 +451,49 @@ int cv_blosc_decompress_many(const uint8_t *const *chunks, const int64_t *clens,
  * caller then un-pickles instead).  Returns 0 only if all blocks are ok.                                */
 int cv_blosc_unpack_blocks(const uint8_t *const *chunks, const int64_t *clens, int64_t n, uint8_t *dst,
                            int64_t block_bytes, int64_t *lens, int32_t *status);
+/* A second writer: c-blosc's own multi-block layout.  The data is cut into blocks of `blocksize` bytes (rounded down
+ * to whole elements and to the data, as c-blosc does; 1 <= typesize <= 16); every block is byte-shuffled on its own and, when blocksize / typesize >= 128 and the
+ * block is not the leftover, split into `typesize` byte-plane LZ4 streams (the rule cv_blosc_decompress reads); a
+ * split whose LZ4 form is not smaller is stored.  Chunks of fewer than 64 bytes, and chunks that do not shrink, are
+ * memcpy'd.  dstcap >= cv_blosc_blocks_bound(n, typesize, blocksize).  cv_blosc_compress_lz4 stays the default writer. */
+int64_t cv_blosc_blocks_bound(int64_t n, int typesize, int64_t blocksize);
+int cv_blosc_compress_lz4_blocks(const uint8_t *src, int64_t n, int typesize, int64_t blocksize, uint8_t *dst,
+                                 int64_t dstcap, int64_t *clen);
+
+/* The same blocks decoded on the device (csrc/cv_blosc_dev.hip): the compressed chunks cross to HBM, not 2 112 bytes
+ * per candidate.  None of the three allocates or synchronises; the two *_dev calls are enqueued on `stream`.
+ * cv_blosc_plan (host, no GPU) reads the 16-byte header, bstarts and per-split length words of n chunks with the checks
+ * of cv_blosc_decompress and lays the chunks out back to back (16-byte aligned) in a slab of *comp_bytes and their
+ * byte planes in a scratch of *scratch_bytes.  It writes
+ *   stream_rows[CV_BLOSC_STREAM_ROW * s]: offset of the stream in the slab, cb, offset in the scratch, neblock,
+ *                                         1 = stored (cb == neblock, a plain copy; a memcpy'd chunk is one such row)
+ *   chunk_rows[CV_BLOSC_CHUNK_ROW * i]:   typesize, shuffle flag, nbytes, blocksize, first stream, stream count,
+ *                                         scratch offset, 1 = not for the device, offset of the chunk in the slab, clen
+ * A chunk is "not for the device" when the host decoder would refuse it (version != 2, truncated tables, bad offsets),
+ * when it is not byte-shuffled LZ4 (bit shuffle, another codec), when typesize is not 1, 4 or 8, when nbytes >
+ * max_nbytes or when max_streams rows do not hold it; it takes no room in the slab.  Returns the number of such chunks
+ * (0 = all planned), -1 on a bad argument.
+ * cv_blosc_decode_dev decodes `streams` rows, one wave per row, from the slab into the scratch; status_dev[s] =
+ * CV_BLOSC_OK: the stream consumed exactly cb bytes and produced exactly neblock; CV_BLOSC_HOST: anything else -- the
+ * device neither accepts nor rejects it, the host decoder has the last word.  Rows that do not lie inside
+ * [0, comp_bytes) / [0, scratch_bytes) are not touched (HOST).
+ * cv_blosc_unpack_dev unshuffles each chunk's planes (per blosc block; the leftover block has its own element count),
+ * finds the pickled ndarray's data in the first 1 KiB by the rule of cv_blosc_unpack_blocks and writes it to
+ * dst_dev + i * block_bytes.  lens_dev[i] = data bytes of chunk i; status_dev[i] as cv_blosc_unpack_blocks: 0 ok, 1 a
+ * stream came back HOST or the chunk was not planned, 2 payload not recognised or of unexpected size (not block_bytes
+ * for a chunk that is not the last, more than block_bytes); a last chunk of fewer than 512 bytes without a payload
+ * (the always-appended empty block) is ok with length 0.  At most 65535 chunks per call.                          */
+#define CV_BLOSC_OK 1
+#define CV_BLOSC_HOST 2
+#define CV_BLOSC_STREAM_ROW 5
+#define CV_BLOSC_CHUNK_ROW 10
+int cv_blosc_plan(const uint8_t *const *chunks, const int64_t *clens, int64_t n, int64_t max_nbytes, int64_t max_streams,
+                  int64_t *stream_rows, int64_t *chunk_rows, int64_t *streams, int64_t *comp_bytes, int64_t *scratch_bytes);
+int cv_blosc_decode_dev(const uint8_t *comp_dev, int64_t comp_bytes, const int64_t *stream_rows_dev, int64_t streams,
+                        uint8_t *scratch_dev, int64_t scratch_bytes, uint8_t *status_dev, void *stream);
+int cv_blosc_unpack_dev(const int64_t *chunk_rows_dev, int64_t chunks, const uint8_t *stream_status_dev, int64_t streams,
+                        const uint8_t *scratch_dev, int64_t scratch_bytes, uint8_t *dst_dev, int64_t block_bytes,
+                        int64_t *lens_dev, int32_t *status_dev, void *stream);
 
 /* CRC32C (Castagnoli) of the tensor bytes / table blocks of the TensorFlow V2 checkpoint
  * bundle written by saveParameters and read by restoreParameters (v3.py:243-251).        */
