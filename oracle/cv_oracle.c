@@ -587,11 +587,13 @@ static void backward_one(const cvo_arch *a, const cvo_layout *L, const cvo_shape
  *   + lambda * sum_{non-bias kernels} sum(w^2)/2
  * losses[0..4] = loss1..loss4, lossL2 ; returns total.
  * grads: NULL or 18 buffers (same sizes as P) that RECEIVE d loss / d param.
- * mask4 / rate4: alpha-dropout keep mask on fc4 (NULL = phase False).        */
-double cvo_loss_grad(const cvo_arch *a, const float *const *P, const float *x, const float *y,
-                     int64_t n, float lambda, const float *mask4, float rate4,
-                     double *losses, float *const *grads)
+ * mask4 / rate4: alpha-dropout keep mask on fc4 (NULL = phase False).
+ * grads64 (cvo_loss_grad64): the same 18 gradients as the doubles they were accumulated in, not rounded to float. */
+static double loss_grad_impl(const cvo_arch *a, const float *const *P, const float *x, const float *y,
+                             int64_t n, float lambda, const float *mask4, float rate4,
+                             double *losses, float *const *grads32, double *const *grads64)
 {
+    const int grads = grads32 != NULL || grads64 != NULL;
     cvo_layout L; cvo_make_layout(a, &L);
     cvo_shape s; cvo_shapes(a, &s);
     int64_t psz[CVO_NPARAM]; cvo_param_sizes(a, psz);
@@ -671,7 +673,8 @@ double cvo_loss_grad(const cvo_arch *a, const float *const *P, const float *x, c
             for (int64_t k = 0; k < psz[p]; k++) {
                 double v = gacc[p][k];
                 if ((p & 1) == 0) v += (double)lambda * P[p][k];
-                grads[p][k] = (float)v;
+                if (grads32) grads32[p][k] = (float)v;
+                if (grads64) grads64[p][k] = v;
             }
             free(gacc[p]);
         }
@@ -680,6 +683,20 @@ double cvo_loss_grad(const cvo_arch *a, const float *const *P, const float *x, c
     double total = lsum[0] + lsum[1] + lsum[2] + lsum[3] + l2;
     free(lsum_t); free(gacc_t);
     return total;
+}
+
+double cvo_loss_grad(const cvo_arch *a, const float *const *P, const float *x, const float *y,
+                     int64_t n, float lambda, const float *mask4, float rate4,
+                     double *losses, float *const *grads)
+{
+    return loss_grad_impl(a, P, x, y, n, lambda, mask4, rate4, losses, grads, NULL);
+}
+
+double cvo_loss_grad64(const cvo_arch *a, const float *const *P, const float *x, const float *y,
+                       int64_t n, float lambda, const float *mask4, float rate4,
+                       double *losses, double *const *grads)
+{
+    return loss_grad_impl(a, P, x, y, n, lambda, mask4, rate4, losses, NULL, grads);
 }
 
 

@@ -74,6 +74,7 @@ def lib():
         _lib.cvo_flat_size.restype = ctypes.c_int
         _lib.cvo_record_size.restype = ctypes.c_int64
         _lib.cvo_loss_grad.restype = ctypes.c_double
+        _lib.cvo_loss_grad64.restype = ctypes.c_double
     return _lib
 
 
@@ -206,8 +207,9 @@ def backward_maps(arch_name, params, x, y, mask4=None, rate4=0.0):
     return res
 
 
-def loss_grad(arch_name, params, x, y, lam=0.0, mask4=None, rate4=0.0, want_grads=True):
-    """Returns (loss, losses[5], grads dict|None); sums over the batch (v3.py:140-151)."""
+def loss_grad(arch_name, params, x, y, lam=0.0, mask4=None, rate4=0.0, want_grads=True, f64=False):
+    """Returns (loss, losses[5], grads dict|None); sums over the batch (v3.py:140-151).  f64: the gradients as the
+    doubles the oracle accumulated them in (cvo_loss_grad64) instead of rounded to float."""
     a = ARCH[arch_name]
     x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, H, W, CIN)
     y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1, NOUT)
@@ -216,15 +218,16 @@ def loss_grad(arch_name, params, x, y, lam=0.0, mask4=None, rate4=0.0, want_grad
     losses = (ctypes.c_double * 5)()
     grads, gptrs = None, None
     if want_grads:
-        grads = [np.zeros_like(a_) for a_ in arrs]
+        grads = [np.zeros(a_.shape, dtype=np.float64 if f64 else np.float32) for a_ in arrs]
         gptrs = (ctypes.c_void_p * len(grads))(*[g.ctypes.data for g in grads])
     mptr = None
     if mask4 is not None:
         mask4 = np.ascontiguousarray(mask4, dtype=np.float32)
         mptr = ctypes.c_void_p(mask4.ctypes.data)
-    loss = lib().cvo_loss_grad(ctypes.byref(a), ptrs, ctypes.c_void_p(x.ctypes.data),
-                               ctypes.c_void_p(y.ctypes.data), ctypes.c_int64(n), ctypes.c_float(lam),
-                               mptr, ctypes.c_float(rate4), losses, gptrs)
+    fn = lib().cvo_loss_grad64 if f64 and want_grads else lib().cvo_loss_grad
+    loss = fn(ctypes.byref(a), ptrs, ctypes.c_void_p(x.ctypes.data),
+              ctypes.c_void_p(y.ctypes.data), ctypes.c_int64(n), ctypes.c_float(lam),
+              mptr, ctypes.c_float(rate4), losses, gptrs)
     gd = dict(zip(PARAM_NAMES, grads)) if want_grads else None
     return float(loss), list(losses), gd
 
