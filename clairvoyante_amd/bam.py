@@ -14,6 +14,7 @@ class BamFile(object):
     def __init__(self, path, threads=None):
         self.lib = _lib.load()
         self.h = ctypes.c_void_p()
+        self.path = os.fspath(path)
         t = min(_lib.usable_cores(), 16) if threads is None else int(threads)
         _lib.check(self.lib.cv_bam_open(os.fsencode(path), t, ctypes.byref(self.h)))
 

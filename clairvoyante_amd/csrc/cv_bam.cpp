@@ -15,8 +15,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/mman.h>
 #include <zlib.h>
 
+#include <algorithm>
 #include <string>
 #include <thread>
 #include <vector>
@@ -82,6 +84,13 @@ struct cv_bam {
     bool eof = false;
     bytebuf comp;                            // scratch: compressed blocks of one batch
     std::vector<uint32_t> rec_offs;          // cv_bam_view_records: starts of the selected records in `data`
+    // ---- plan of the current view (cv_bam_view_plan): the file mapped, the slab handed out last
+    const uint8_t *map = nullptr;
+    int64_t map_len = 0;
+    int64_t plan_coff = 0;                   // file offset of the next member to plan
+    uint64_t plan_start = 0;                 // virtual offset the view starts at
+    bool plan_first = true;
+    std::vector<int64_t> plan_table, plan_hdr, plan_anchors;
 };
 
 namespace {
@@ -307,6 +316,7 @@ extern "C" int cv_bam_open(const char *path, int threads, cv_bam **out)
 extern "C" void cv_bam_close(cv_bam *b)
 {
     if (!b) return;
+    if (b->map) munmap(const_cast<uint8_t *>(b->map), (size_t)b->map_len);
     if (b->fp) fclose(b->fp);
     delete b;
 }
@@ -363,15 +373,16 @@ extern "C" int cv_bam_record_cigar(const uint8_t *rec, const uint8_t **ops, int6
     return 1;
 }
 
-extern "C" int cv_bam_view_begin(cv_bam *b, const char *ref, int64_t beg1, int64_t end1, int exclude_flags, int with_qual)
+// the selection of a view and where it starts: 0 = *voff / *from_start set, 1 = the view is empty (b->done)
+static int view_select(cv_bam *b, const char *ref, int64_t beg1, int64_t end1, int exclude_flags, int with_qual, uint64_t *voff_out,
+                       bool *from_start_out)
 {
-    if (!b || !ref) { cv_set_error("cv_bam_view_begin: null argument"); return 1; }
     b->tid = -1;
     for (size_t i = 0; i < b->refs.size(); i++)
         if (b->refs[i].name == ref) { b->tid = (int)i; break; }
     b->done = false;
     b->exclude = exclude_flags; b->with_qual = with_qual;
-    if (b->tid < 0) { b->done = true; return 0; }         // samtools prints nothing for an unknown contig (and warns)
+    if (b->tid < 0) { b->done = true; return 1; }         // samtools prints nothing for an unknown contig (and warns)
     if (beg1 <= 0 && end1 <= 0) { b->beg0 = 0; b->end0 = (int64_t)1 << 40; }
     else { b->beg0 = beg1 > 0 ? beg1 - 1 : 0; b->end0 = end1 > 0 ? end1 : (int64_t)1 << 40; }
     // where to start: the linear index gives the first record overlapping the 16 kb window of `beg`; records of
@@ -388,8 +399,18 @@ extern "C" int cv_bam_view_begin(cv_bam *b, const char *ref, int64_t beg1, int64
             while (v == 0 && w + 1 < li.size()) v = li[++w];   // empty windows hold 0: the next filled one is a valid start
         }
         if (v) { voff = v; from_start = false; }
-        else if (li.empty()) { b->done = true; return 0; }     // no alignment on this contig
+        else if (li.empty()) { b->done = true; return 1; }     // no alignment on this contig
     }
+    *voff_out = voff; *from_start_out = from_start;
+    return 0;
+}
+
+extern "C" int cv_bam_view_begin(cv_bam *b, const char *ref, int64_t beg1, int64_t end1, int exclude_flags, int with_qual)
+{
+    if (!b || !ref) { cv_set_error("cv_bam_view_begin: null argument"); return 1; }
+    uint64_t voff = 0;
+    bool from_start = true;
+    if (view_select(b, ref, beg1, end1, exclude_flags, with_qual, &voff, &from_start)) return 0;
     b->data.clear(); b->data_pos = 0; b->eof = false;
     if (from_start) {
         b->next_coff = 0;
@@ -402,6 +423,116 @@ extern "C" int cv_bam_view_begin(cv_bam *b, const char *ref, int64_t beg1, int64
         if (!need(b, (size_t)(voff & 0xffff), &err)) { b->done = true; return err; }
         b->data_pos = (size_t)(voff & 0xffff);
     }
+    return 0;
+}
+
+// ---- the same view as a plan for the device reader (cv_bam_dev.hip): nothing is inflated here ---------------------
+extern "C" int cv_bam_view_plan_begin(cv_bam *b, const char *ref, int64_t beg1, int64_t end1, int exclude_flags, int *usable)
+{
+    if (!b || !ref || !usable) { cv_set_error("cv_bam_view_plan_begin: null argument"); return 1; }
+    *usable = 0;
+    if (!b->has_index) return 0;
+    uint64_t voff = 0;
+    bool from_start = true;
+    if (view_select(b, ref, beg1, end1, exclude_flags, 0, &voff, &from_start)) { *usable = 1; return 0; }   // empty view
+    if (from_start) { b->done = true; return 0; }          // an index without a start for this contig: the host route
+    if (!b->map) {
+        if (fseeko(b->fp, 0, SEEK_END)) { cv_set_error("bam: seek failed"); return 1; }
+        const off_t len = ftello(b->fp);
+        if (len <= 0) { cv_set_error("bam: %s is empty or truncated", b->path.c_str()); return 1; }
+        void *m = mmap(nullptr, (size_t)len, PROT_READ, MAP_PRIVATE, fileno(b->fp), 0);
+        if (m == MAP_FAILED) { cv_set_error("bam: cannot map %s", b->path.c_str()); return 1; }
+        b->map = (const uint8_t *)m; b->map_len = (int64_t)len;
+    }
+    b->plan_coff = (int64_t)(voff >> 16);
+    b->plan_start = voff;
+    b->plan_first = true;
+    *usable = 1;
+    return 0;
+}
+
+extern "C" int cv_bam_view_plan(cv_bam *b, int64_t slab_bytes, int64_t info[8], const uint8_t **comp, const int64_t **table,
+                                const int64_t **anchors)
+{
+    if (!b || !info || !comp || !table || !anchors) { cv_set_error("cv_bam_view_plan: null argument"); return 1; }
+    for (int k = 0; k < 8; k++) info[k] = 0;
+    *comp = nullptr; *table = nullptr; *anchors = nullptr;
+    b->plan_table.clear(); b->plan_hdr.clear(); b->plan_anchors.clear();
+    if (b->done || !b->map) { info[5] = 1; return 0; }
+    if (slab_bytes < 1) slab_bytes = 1;
+    int64_t p = b->plan_coff, out = 0;
+    bool eof = false;
+    while (p - b->plan_coff < slab_bytes && out < ((int64_t)1 << 30)) {
+        if (p >= b->map_len) { eof = true; break; }
+        const int s = bgzf_block_size(b->map + p, (size_t)(b->map_len - p));
+        if (s < 0) { cv_set_error("bam: %s is not BGZF-compressed at offset %lld", b->path.c_str(), (long long)p); return 1; }
+        if (s == 0 || p + s > b->map_len) { eof = true; break; }             // trailing bytes shorter than a block
+        const int xlen = rd_u16(b->map + p + 10);
+        const uint32_t isize = rd_u32(b->map + p + s - 4), crc = rd_u32(b->map + p + s - 8);
+        if (isize > 65536) { cv_set_error("bam: corrupt BGZF block at offset %lld", (long long)p); return 1; }
+        b->plan_hdr.push_back(p);
+        b->plan_table.push_back(p + 12 + xlen);
+        b->plan_table.push_back((int64_t)s - 12 - xlen - 8);
+        b->plan_table.push_back(out);
+        b->plan_table.push_back((int64_t)(((uint64_t)isize << 32) | crc));
+        out += isize; p += s;
+    }
+    if (p >= b->map_len) eof = true;
+    const int64_t members = (int64_t)b->plan_hdr.size();
+    info[0] = members; info[2] = out; info[5] = eof ? 1 : 0; info[6] = b->plan_coff; info[7] = b->plan_first ? 1 : 0;
+    if (members == 0) return 0;
+    info[1] = p - b->plan_table[0];
+    info[3] = b->plan_first ? (int64_t)(b->plan_start & 0xffff) : 0;
+    // anchors: the linear-index entries of the contig that point into this slab, behind the start of the view, as
+    // ascending distinct offsets in the slab's inflated bytes.  What is dropped costs a walker, never a record.
+    const std::vector<uint64_t> &li = b->linear[(size_t)b->tid];
+    int64_t last = b->plan_first ? info[3] : -1;
+    for (size_t w = 0; w < li.size(); w++) {
+        const uint64_t v = li[w];
+        if (v == 0 || v <= b->plan_start) continue;
+        const int64_t coff = (int64_t)(v >> 16), uoff = (int64_t)(v & 0xffff);
+        if (coff < b->plan_coff || coff >= p) continue;
+        const auto it = std::lower_bound(b->plan_hdr.begin(), b->plan_hdr.end(), coff);
+        if (it == b->plan_hdr.end() || *it != coff) continue;
+        const size_t m = (size_t)(it - b->plan_hdr.begin());
+        const int64_t isize = (int64_t)((uint64_t)b->plan_table[4 * m + 3] >> 32);
+        if (uoff >= isize) continue;
+        const int64_t a = b->plan_table[4 * m + 2] + uoff;
+        if (a <= last) continue;
+        b->plan_anchors.push_back(a);
+        last = a;
+    }
+    info[4] = (int64_t)b->plan_anchors.size();
+    *comp = b->map + b->plan_table[0];
+    *table = b->plan_table.data();
+    *anchors = b->plan_anchors.data();
+    b->plan_coff = p;
+    b->plan_first = false;
+    return 0;
+}
+
+// member m of the slab handed out last, inflated and CRC-checked on the host (what inflate_block does for the host route)
+extern "C" int cv_bam_plan_inflate_host(cv_bam *b, int64_t m, uint8_t *dst)
+{
+    if (!b || !dst || m < 0 || m >= (int64_t)b->plan_hdr.size()) { cv_set_error("cv_bam_plan_inflate_host: bad argument"); return 1; }
+    const int64_t isize = (int64_t)((uint64_t)b->plan_table[4 * (size_t)m + 3] >> 32);
+    const int64_t s = b->plan_table[4 * (size_t)m] + b->plan_table[4 * (size_t)m + 1] + 8 - b->plan_hdr[(size_t)m];
+    z_stream zs;
+    memset(&zs, 0, sizeof(zs));
+    int dlen = 0;
+    bool ok = inflateInit2(&zs, -15) == Z_OK;
+    if (ok) {
+        ok = inflate_block(zs, b->map + b->plan_hdr[(size_t)m], (int)s, dst, &dlen) && (int64_t)dlen == isize;
+        inflateEnd(&zs);
+    }
+    if (!ok) { cv_set_error("bam: corrupt BGZF block at offset %lld", (long long)b->plan_hdr[(size_t)m]); return 1; }
+    return 0;
+}
+
+extern "C" int cv_bam_view_params(const cv_bam *b, int64_t out[4])
+{
+    if (!b || !out) { cv_set_error("cv_bam_view_params: null argument"); return 1; }
+    out[0] = b->tid; out[1] = b->exclude; out[2] = b->beg0; out[3] = b->end0;
     return 0;
 }
 

@@ -391,6 +391,8 @@ struct cv_pileup {
     int64_t pending_cols = 0;
     dev_batch work;                     // reused staging batch (retain == 0)
     std::vector<dev_batch> kept;        // resident batches / views (retain == 1)
+    dev_batch reserved;                 // room handed out by cv_pileup_reserve_bam_dev under retain, not yet a batch
+    bool has_reserved = false;
     int64_t prev_pos = 0, depth_cap = 0;   // CreateTensor.py:139,165-172
     int64_t evc_prev_pos = INT64_MIN;      // POS of the last read the candidate pass took
     int64_t evc_reads = 0;                 // processedReads (:150)
@@ -464,6 +466,7 @@ extern "C" void cv_pileup_destroy(cv_pileup *p)
     hipFree(p->ref_dev); hipFree(p->cand_dev); hipFree(p->bucket_dev); hipFree(p->cnt_dev);
     hipFree(p->touched_dev); hipFree(p->pos_cnt);
     free_batch(p->work);
+    if (p->has_reserved && p->retain) free_batch(p->reserved);
     for (auto &b : p->kept) free_batch(b);
     delete p;
 }
@@ -957,6 +960,117 @@ extern "C" int cv_pileup_flush(cv_pileup *p, void *stream)
     PL_HIP(hipStreamSynchronize(st));
     p->cols += p->pending_cols;
     p->queue.clear(); p->pending_cols = 0;
+    return 0;
+}
+
+// ---- a batch made on the device (cv_bam_dev.hip) ---------------------------------------------------------------
+// what the device BAM reader needs of the handle: out[0..4] = min_mq, dcov, evc, evc_min_mq, a contig is set;
+// out[5..8] = the running state prev_pos, depth_cap, evc_prev_pos, evc_reads
+extern "C" int cv_pileup_bam_params(const cv_pileup *p, int64_t out[9])
+{
+    if (!p || !out) { cv_set_error("cv_pileup_bam_params: null argument"); return 1; }
+    out[0] = p->min_mq; out[1] = p->dcov; out[2] = p->evc; out[3] = p->evc_min_mq; out[4] = p->contig.empty() ? 0 : 1;
+    out[5] = p->prev_pos; out[6] = p->depth_cap; out[7] = p->evc_prev_pos; out[8] = p->evc_reads;
+    return 0;
+}
+
+// room for a batch of ns segments and nqq SEQ bytes in b (the staging batch, or a fresh one under `retain`)
+static int batch_room(cv_pileup *p, dev_batch &b, size_t ns, size_t nqq, hipStream_t st)
+{
+    if (ns > b.segs_cap) {
+        PL_HIP(hipStreamSynchronize(st));
+        hipFree(b.segs); b.segs = nullptr;
+        b.segs_cap = p->retain ? ns : ns + ns / 4;
+        PL_HIP(hipMalloc(&b.segs, b.segs_cap * sizeof(seg_t)));
+    }
+    if (nqq > b.seq_cap) {
+        PL_HIP(hipStreamSynchronize(st));
+        hipFree(b.seq); b.seq = nullptr;
+        b.seq_cap = p->retain ? nqq : nqq + nqq / 4;
+        PL_HIP(hipMalloc(&b.seq, b.seq_cap));
+    }
+    return 0;
+}
+
+static int bam_dev_args(cv_pileup *p, int64_t nseg, int64_t nq, const char *who)
+{
+    if (!p || nseg < 0 || nq < 0) { cv_set_error("%s: bad argument", who); return 1; }
+    if ((uint64_t)nq >= 0xffffff00ull) { cv_set_error("%s: more than 4 Gi query bases in one batch", who); return 1; }
+    if (nseg > 0 && (!p->ref_dev || (!p->cand_dev && !p->evc))) {
+        cv_set_error("cv_pileup_flush: set the reference and the candidates first");
+        return 1;
+    }
+    return 0;
+}
+
+// The place of the next device-made batch, so that it is written where the kernels will read it: parts queued on the host
+// are flushed first (they use the same staging batch), then *segs_dev / *seq_dev have room for nseg segments and nq + 64
+// SEQ bytes.  cv_pileup_add_bam_dev with these pointers takes the batch without a copy.
+extern "C" int cv_pileup_reserve_bam_dev(cv_pileup *p, int64_t nseg, int64_t nq, void **segs_dev, uint8_t **seq_dev, void *stream)
+{
+    if (!segs_dev || !seq_dev || nseg < 1) { cv_set_error("cv_pileup_reserve_bam_dev: bad argument"); return 1; }
+    if (bam_dev_args(p, nseg, nq, "cv_pileup_reserve_bam_dev")) return 1;
+    if (cv_pileup_flush(p, stream)) return 1;
+    PL_HIP(hipSetDevice(p->device));
+    if (p->has_reserved && p->retain) free_batch(p->reserved);             // reserved and never handed over
+    p->has_reserved = false;
+    if (p->retain) p->reserved = dev_batch();
+    dev_batch &b = p->retain ? p->reserved : p->work;
+    if (batch_room(p, b, (size_t)nseg, (size_t)nq + 64, (hipStream_t)stream)) return 1;
+    p->has_reserved = true;
+    *segs_dev = b.segs; *seq_dev = b.seq;
+    return 0;
+}
+
+// segs_dev[0, nseg) / seq_dev[0, nq): segments in read order and their SEQ bytes (q0 absolute in seq_dev), flags already
+// as absorb_parts leaves them; cols their alignment columns; state[4] the running state behind the last read.  The
+// batch goes where cv_pileup_flush puts an upload -- in place when it was written to cv_pileup_reserve_bam_dev's
+// pointers, copied on `stream` otherwise; parts queued on the host go first.
+extern "C" int cv_pileup_add_bam_dev(cv_pileup *p, const void *segs_dev, int64_t nseg, const uint8_t *seq_dev, int64_t nq,
+                                     int64_t cols, const int64_t state[4], void *stream)
+{
+    if (!p || !state || cols < 0 || (nseg > 0 && !segs_dev) || (nq > 0 && !seq_dev)) {
+        cv_set_error("cv_pileup_add_bam_dev: bad argument");
+        return 1;
+    }
+    if (bam_dev_args(p, nseg, nq, "cv_pileup_add_bam_dev")) return 1;
+    const bool in_place = p->has_reserved && nseg > 0 && segs_dev == (p->retain ? p->reserved.segs : p->work.segs) &&
+                          seq_dev == (p->retain ? p->reserved.seq : p->work.seq);
+    if (!in_place && cv_pileup_flush(p, stream)) return 1;                // (in place: flushed when the room was reserved)
+    p->prev_pos = state[0]; p->depth_cap = state[1]; p->evc_prev_pos = state[2]; p->evc_reads = state[3];
+    p->cols += cols;
+    if (nseg == 0) return 0;
+    PL_HIP(hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ns = (size_t)nseg;
+    dev_batch fresh;
+    dev_batch &b = in_place ? (p->retain ? p->reserved : p->work) : (p->retain ? fresh : p->work);
+    if (!in_place) {
+        if (batch_room(p, b, ns, (size_t)nq + 64, st)) return 1;
+        PL_HIP(hipMemcpyAsync(b.segs, segs_dev, ns * sizeof(seg_t), hipMemcpyDeviceToDevice, st));
+        if (nq > 0) PL_HIP(hipMemcpyAsync(b.seq, seq_dev, (size_t)nq, hipMemcpyDeviceToDevice, st));
+    }
+    b.nseg = ns;
+    if (p->evc && !p->pos_cnt) {
+        const size_t bytes = (size_t)(p->ref_len > 0 ? p->ref_len : 1) * NPOS * sizeof(int32_t);
+        PL_HIP(hipMalloc(&p->pos_cnt, bytes));
+        PL_HIP(hipMemsetAsync(p->pos_cnt, 0, bytes, st));
+    }
+    PL_HIP(hipMemsetAsync(b.seq + nq, 0, 64, st));
+    if (p->evc) {
+        if (p->eve.size() >= 128 && drain(p->eve, p->ms_evc)) return 1;
+        {
+            timed t(p->eve, st);
+            evc_count<<<(unsigned)((ns + EVC_SEGS - 1) / EVC_SEGS), 1024, 0, st>>>(b.segs, (int64_t)ns, b.seq, p->ref_first,
+                                                                                   p->ref_len, p->pos_cnt);
+        }
+        PL_HIP(hipGetLastError());
+    }
+    if (p->cand_dev && launch_scatter(p, b, st)) return 1;
+    if (p->retain) p->kept.push_back(b);
+    if (in_place) { p->has_reserved = false; p->reserved = dev_batch(); }
+    p->nsegs += (int64_t)ns;
+    PL_HIP(hipStreamSynchronize(st));
     return 0;
 }
 

@@ -3,6 +3,7 @@
 (OutputAlnTensor :93-246, GenerateTensor :23-54); see csrc/cv_pileup.hip for the decomposition.
 """
 import ctypes
+import os
 
 import numpy as np
 
@@ -11,6 +12,40 @@ from . import _lib
 FLANK = 16
 WIDTH = 2 * FLANK + 1
 FLUSH_COLUMNS = 1 << 26         # queue at most this many alignment columns on the host before a scatter launch
+
+# BAM records on the device (csrc/cv_bam_dev.hip): `route` of Pileup.add_bam, else CV_BAM_DECODE=host|device, else the
+# device from BAM_DEVICE_MIN_BYTES of file size on.  None: no measured size from which the device route wins in every
+# run, so the route is opt-in and the default is the host.
+BAM_DEVICE_MIN_BYTES = None
+BAM_SLAB_BYTES = 64 << 20       # compressed bytes per slab; CV_BAM_SLAB_BYTES overrides (tests set it small)
+_BAM_KEYS = ("host_views", "device_views", "device_slabs", "device_records", "device_members", "host_members",
+             "handed_over_slabs", "handed_over_records", "walkers", "members")
+_bam_counts = dict.fromkeys(_BAM_KEYS, 0)
+
+
+def bam_decode_counts(reset=False):
+    """what Pileup.add_bam did since the start (or the last reset), per side: views by route, slabs / records / BGZF
+    members the device took, members the host had to inflate for it, slabs (and their records) handed over to the host
+    because the device did not vouch for them, walkers that ran"""
+    out = dict(_bam_counts)
+    if reset:
+        for k in _BAM_KEYS:
+            _bam_counts[k] = 0
+    return out
+
+
+def _bam_route(route, bam_path):
+    r = route if route is not None else os.environ.get("CV_BAM_DECODE")
+    if r is None or r == "":
+        if BAM_DEVICE_MIN_BYTES is None:
+            return "host"
+        try:
+            return "device" if os.path.getsize(bam_path) >= BAM_DEVICE_MIN_BYTES else "host"
+        except OSError:
+            return "host"
+    if r not in ("host", "device"):
+        raise ValueError("BAM decode route %r: host or device" % (r,))
+    return r
 
 
 class Pileup(object):
@@ -40,6 +75,9 @@ class Pileup(object):
         self.reads_kept = 0
 
     def close(self):
+        if getattr(self, "_bam_dev", None):
+            self.lib.cv_bam_dev_destroy(self._bam_dev)
+            self._bam_dev = None
         if getattr(self, "h", None):
             self.lib.cv_pileup_destroy(self.h)
             self.h = None
@@ -96,12 +134,22 @@ class Pileup(object):
             _lib.check(self.lib.cv_pileup_flush(self.h, self._stream()))
         return self._kept_now
 
-    def add_bam(self, bam, ref, start=None, end=None, exclude_flags=2308, contig_ok=True, window=64 << 20):
+    def add_bam(self, bam, ref, start=None, end=None, exclude_flags=2308, contig_ok=True, window=64 << 20, route=None):
         """feed the records `samtools view -F exclude_flags BAM ref[:start-end]` would print, straight from the
-        BAM (bam: clairvoyante_amd.bam.BamFile) -- no SAM text in between; same result as add_sam on that text"""
+        BAM (bam: clairvoyante_amd.bam.BamFile) -- no SAM text in between; same result as add_sam on that text.
+        route: "host" (records walked and cut into segments by host threads), "device" (the compressed blocks go to
+        the GPU, csrc/cv_bam_dev.hip; needs the .bai, a view without one takes the host route), None: CV_BAM_DECODE,
+        else BAM_DEVICE_MIN_BYTES.  Same result either way; bam_decode_counts() tells which one ran."""
         self._kept_now = 0
         if self._tail:
             self.add_sam(b"", final=True)
+        if _bam_route(route, bam.path) == "device":
+            usable = ctypes.c_int(0)
+            _lib.check(self.lib.cv_bam_view_plan_begin(bam.h, ref.encode(), int(start or 0), int(end or 0), int(exclude_flags),
+                                                       ctypes.byref(usable)))
+            if usable.value:
+                return self._add_bam_device(bam, contig_ok)
+        _bam_counts["host_views"] += 1
         _lib.check(self.lib.cv_bam_view_begin(bam.h, ref.encode(), int(start or 0), int(end or 0), int(exclude_flags), 0))
         base = ctypes.c_void_p(); offs = ctypes.c_void_p(); done = ctypes.c_int(0); kept = ctypes.c_int64(0)
         total = 0
@@ -116,6 +164,31 @@ class Pileup(object):
                 if self.lib.cv_pileup_pending(self.h) >= FLUSH_COLUMNS:
                     _lib.check(self.lib.cv_pileup_flush(self.h, self._stream()))
         return total
+
+    def _add_bam_device(self, bam, contig_ok):
+        if getattr(self, "_bam_dev", None) is None:
+            self._bam_dev = ctypes.c_void_p()
+            _lib.check(self.lib.cv_bam_dev_create(self.device.index, ctypes.byref(self._bam_dev)))
+        slab = int(os.environ.get("CV_BAM_SLAB_BYTES") or BAM_SLAB_BYTES)
+        kept = ctypes.c_int64(0)
+        cnt = (ctypes.c_int64 * 8)()
+        rc = self.lib.cv_bam_dev_view(self._bam_dev, bam.h, self.h, slab, int(bool(contig_ok)), self._stream(), ctypes.byref(kept), cnt)
+        _bam_counts["device_views"] += 1
+        for k, i in (("device_slabs", 0), ("device_records", 1), ("device_members", 2), ("host_members", 3),
+                     ("handed_over_slabs", 4), ("walkers", 5), ("handed_over_records", 6), ("members", 7)):
+            _bam_counts[k] += cnt[i]
+        self.reads_kept += kept.value
+        _lib.check(rc)
+        return kept.value
+
+    def bam_device_ms(self):
+        """time (ms) of the device BAM route on this handle: host wall time between its synchronisations by phase (copies,
+        launches and, in emit_handover, the pileup's own kernels included), and the HIP-event time of the inflate and the
+        walk kernel alone"""
+        ms = (ctypes.c_double * 7)()
+        if getattr(self, "_bam_dev", None):
+            _lib.check(self.lib.cv_bam_dev_times(self._bam_dev, ms))
+        return dict(zip(("inflate", "walk", "count_scan", "emit_handover", "host_slabs", "inflate_kernel", "walk_kernel"), ms))
 
     def finish(self, subtract=False, want_tensors=True):
         """-> (tensors [n,33,4,4] fp32 on the device, depth [n] int32, touched [n] bool)"""

@@ -625,6 +625,56 @@ int64_t cv_bam_view_records(cv_bam *b, int64_t max_bytes, const uint8_t **base, 
 /* CIGAR words of a record handed out by cv_bam_view_records (rec at refID): the inline ones, or the CG:B,I array
  * behind the long-read placeholder <l_seq>S<span>N (more than 65535 operations, SAMv1 4.2.2).  0 ok.      */
 int cv_bam_record_cigar(const uint8_t *rec, const uint8_t **ops, int64_t *n);
+/* ---- the BAM front end on the device (csrc/cv_bam_dev.hip, cv_bam_core.hpp; optional route of `--samtools native`) ----
+ * The compressed BGZF members of a view go to the GPU; segments, SEQ bytes and flags are made in HBM and handed to the
+ * pileup handle where cv_pileup_flush puts its uploads.  The host route (cv_bam_view_records + cv_pileup_add_bam) stays
+ * the definition: same counters, same running state, same exception texts.  Needs the .bai.
+ * cv_bam_view_plan_begin: cv_bam_view_begin without inflating anything; *usable = 0 when the file has no (intact)
+ *   index or the index gives no start for the contig: the caller takes the host route.
+ * cv_bam_view_plan: the next slab of the view -- a run of WHOLE members of about slab_bytes compressed bytes.
+ *   info[0] members, [1] compressed bytes from *comp on (the first member's DEFLATE data to the last member's end),
+ *   [2] inflated bytes, [3] offset in them of the first record to look at (first slab: voff & 0xffff of the start; 0
+ *   afterwards, where the caller's carried tail goes in front), [4] anchors, [5] 1 = the file ends behind this slab,
+ *   [6] file offset of the first member, [7] 1 = first slab of the view.  *table: rows as cv_bgzf_scan writes them
+ *   (file offsets; cv_inflate_bgzf_dev takes them relative to the first row).  *anchors: the linear-index entries of the
+ *   contig inside the slab and behind the start, distinct, ascending, as offsets in the slab's inflated bytes;
+ *   duplicates, zeros, entries out of order or not at a member start of the slab are dropped (fewer walkers, never
+ *   another result).  The pointers hold until the next call.  info[0] = 0: nothing left.
+ * cv_bam_plan_inflate_host: member m of that slab inflated and CRC-checked on the host into dst (ISIZE bytes, <= 64 KiB);
+ *   failure is the host route's "bam: corrupt BGZF block at offset N".
+ * cv_bam_view_params: tid, exclude mask, beg0, end0 of the current view.
+ * cv_bam_dev_view: the whole view through the device, slab by slab, into pileup handle p on `stream` (synchronises).
+ *   A slab the device does not vouch for (a walker that misses its anchor, a placeholder CIGAR, a record that fails
+ *   the layout checks, POS / CIGAR demands out of range) is refused before anything of p changes and goes to
+ *   cv_pileup_add_bam from the same inflated bytes.  *kept = reads kept; counts[0] slabs, [1] records taken on the
+ *   device, [2] members inflated on the device, [3] members inflated on the host, [4] slabs handed over to the host,
+ *   [5] walkers that ran, [6] records of the slabs handed over, [7] members read.
+ * cv_bam_dev_times: host wall time (ms, since creation) between the synchronisations of cv_bam_dev_view: [0] copy +
+ *   inflate, [1] walk, [2] count + scans + running state, [3] emit + hand-over (with the pileup's own kernels), [4] slabs
+ *   taken by the host; HIP-event time of [5] the inflate kernel and [6] the walk kernel alone.
+ * cv_pileup_bam_params: out[0..4] = min_mq, dcov, evc, evc_min_mq, 1 if a contig is set; out[5..8] = prev_pos, depth_cap,
+ *   evc_prev_pos, evc_reads (the running state of the depth cap and the late mark).
+ * cv_pileup_add_bam_dev: a batch made on the device -- segs_dev[0, nseg) (20-byte segments in READ order, flags final,
+ *   q0 absolute in seq_dev[0, nq)), `cols` alignment columns, state[4] the running state behind its last read.  Parts
+ *   queued on the host are flushed first; then evc_count / pileup_scatter / retention exactly as cv_pileup_flush.
+ * cv_pileup_reserve_bam_dev: the place of that batch in the handle (room for nseg >= 1 segments, nq + 64 SEQ bytes; the
+ *   host queue is flushed here), so that it is written where the kernels read it: cv_pileup_add_bam_dev with these
+ *   pointers takes it without a copy, with other pointers it copies device to device.                               */
+typedef struct cv_bam_dev cv_bam_dev;
+int cv_bam_view_plan_begin(cv_bam *b, const char *ref, int64_t beg1, int64_t end1, int exclude_flags, int *usable);
+int cv_bam_view_plan(cv_bam *b, int64_t slab_bytes, int64_t info[8], const uint8_t **comp, const int64_t **table,
+                     const int64_t **anchors);
+int cv_bam_plan_inflate_host(cv_bam *b, int64_t m, uint8_t *dst);
+int cv_bam_view_params(const cv_bam *b, int64_t out[4]);
+int cv_bam_dev_create(int device, cv_bam_dev **out);
+void cv_bam_dev_destroy(cv_bam_dev *d);
+int cv_bam_dev_view(cv_bam_dev *d, cv_bam *b, cv_pileup *p, int64_t slab_bytes, int contig_ok, void *stream, int64_t *kept,
+                    int64_t counts[8]);
+int cv_bam_dev_times(const cv_bam_dev *d, double ms[7]);
+int cv_pileup_bam_params(const cv_pileup *p, int64_t out[9]);
+int cv_pileup_reserve_bam_dev(cv_pileup *p, int64_t nseg, int64_t nq, void **segs_dev, uint8_t **seq_dev, void *stream);
+int cv_pileup_add_bam_dev(cv_pileup *p, const void *segs_dev, int64_t nseg, const uint8_t *seq_dev, int64_t nq, int64_t cols,
+                          const int64_t state[4], void *stream);
 /* The block decoder behind the BGZF reader (raw DEFLATE, RFC 1951, whole block in memory): src[0, n) must be
  * followed by 8 readable bytes, the stream must produce exactly cap bytes; returns cap or -1.  And the CRC-32 of
  * the gzip trailer (start with crc = 0).                                                                 */

@@ -1,0 +1,453 @@
+"""The BAM front end on the device (csrc/cv_bam_dev.hip through Pileup.add_bam(route="device")) against the host route,
+which stays the definition: centres, tensors, depths, touched, reads_kept, the extracted candidates (pos0, late, counts,
+reads) and stats() columns / segments, all with np.array_equal -- the counters are integers.  On every clean input the
+device must have taken all of it: no slab handed over, no member inflated on the host, records counted."""
+import gzip
+import os
+import shutil
+import struct
+import sys
+import types
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE); sys.path.insert(0, os.path.join(HERE, ".."))
+import bam_device_cases as C  # noqa: E402
+from test_gpu_pileup import _same  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+G = os.path.join(HERE, "golden", "pileup")
+
+
+def counts():
+    from clairvoyante_amd import pileup
+    return pileup.bam_decode_counts(reset=True)
+
+
+def feed(bam, route, region=(None, None), centers=None, ref=None, ctg="ctgA", halves=None, **kw):
+    """one view (or, halves = [(route, region), ...], several on ONE handle) -> (results as _both_feeds gives them,
+    (columns, segments), bam_decode_counts of the run)"""
+    from clairvoyante_amd.bam import BamFile
+    from clairvoyante_amd.pileup import Pileup
+    counts()
+    pl = Pileup(contig="ctgA", **kw)
+    pl.set_reference(ref, 0)
+    if centers is not None:
+        pl.set_candidates(centers)
+    bf = BamFile(bam, threads=3)
+    for r, reg in (halves or [(route, region)]):
+        pl.add_bam(bf, ctg, reg[0], reg[1], window=1 << 20, route=r)
+    bf.close()
+    res = None
+    if kw.get("evc"):
+        res = pl.extract_candidates(0.1, 3)
+        if kw.get("retain"):
+            pl.adopt_candidates()
+    t, d, u = pl.finish()
+    st = pl.stats()
+    out = (pl.centers.copy(), t.cpu().numpy(), d.cpu().numpy(), u.cpu().numpy(), pl.reads_kept,
+           None if res is None else (res["pos0"], res["late"], res["counts"], res["reads"]))
+    pl.close()
+    return out, (st["columns"], st["segments"]), counts()
+
+
+def clean(cnt, views=1):
+    """the device took everything it was asked to take"""
+    assert cnt["device_views"] == views and cnt["host_views"] == 0, cnt
+    assert cnt["handed_over_slabs"] == 0 and cnt["host_members"] == 0 and cnt["device_records"] > 0, cnt
+    assert cnt["device_members"] == cnt["members"] > 0, cnt
+
+
+def both(bam, ref, centers=None, region=(None, None), **kw):
+    h, hs, hc = feed(bam, "host", region, centers, ref, **kw)
+    d, ds, dc = feed(bam, "device", region, centers, ref, **kw)
+    assert hc["host_views"] == 1 and hc["device_views"] == 0
+    _same(h, d)
+    assert hs == ds, (hs, ds)
+    return h, d, dc
+
+
+SETTINGS = [dict(dcov=1), dict(dcov=250, considerleftedge=False), dict(dcov=250, minMQ=10),
+            dict(evc=True, retain=True, evc_minMQ=5, dcov=2)]
+
+
+@pytest.mark.parametrize("payload", [60000, 311, 777, 303])
+def test_corner_case_records(tmp_path, payload):
+    """cases 1 and 2: every kind of record, whole and straddling BGZF members (neither 311 nor 777 happens to split a
+    4-byte block_size field of these records across two members; 303 does, and the test asserts that from the layout)"""
+    bam = str(tmp_path / "c.bam")
+    where = C.write_bam(bam, C.corner_records(), C.corner_refs(), block_payload=payload)
+    if payload == 303:
+        ends = {m[2] + m[3] for m in C.members(bam)}
+        assert any(e in ends for o, _n in where for e in (o + 1, o + 2, o + 3)), "no block_size field is split: choose another payload"
+    for kw in SETTINGS:
+        h, d, cnt = both(bam, C.CORNER_REF, None if kw.get("evc") else C.CORNER_CENTERS, **kw)
+        clean(cnt)
+        assert h[4] > 0
+    h, d, cnt = both(bam, C.CORNER_REF, C.CORNER_CENTERS, region=(10, 45))
+    clean(cnt)
+    assert h[3].any()
+    # the text feed of the same file (the record `op9` has no SAM spelling: compare without candidates near it)
+    from clairvoyante_amd.bam import BamFile
+    from clairvoyante_amd.pileup import Pileup
+    pl = Pileup(contig="ctgA", dcov=250)
+    pl.set_reference(C.CORNER_REF, 0)
+    far = C.CORNER_CENTERS[(C.CORNER_CENTERS < 40) | (C.CORNER_CENTERS > 90)]
+    pl.set_candidates(far)
+    bf = BamFile(bam, threads=2)
+    for chunk in bf.view("ctgA"):
+        pl.add_sam(chunk)
+    bf.close()
+    t, _d, u = pl.finish()
+    pl.close()
+    dev, _s, cnt = feed(bam, "device", centers=far, ref=C.CORNER_REF, dcov=250)
+    clean(cnt)
+    assert np.array_equal(t.cpu().numpy(), dev[1]) and np.array_equal(u.cpu().numpy(), dev[3])
+
+
+@pytest.fixture(scope="module")
+def noisy():
+    return C.random_alignments()
+
+
+EVC = dict(evc=True, retain=True, dcov=3, minMQ=3, evc_minMQ=5)
+
+
+@pytest.mark.parametrize("region", [(None, None), (9000, 21000)])
+def test_several_anchors(tmp_path, noisy, region):
+    """case 3: three 16 kbp windows, a walker per window"""
+    ref, lines = noisy
+    bam = str(tmp_path / "r.bam")
+    C.write_bam(bam, lines, [("ctgA", len(ref)), ("zzz", 50)])
+    h, d, cnt = both(bam, ref, region=region, **EVC)
+    clean(cnt)
+    assert cnt["walkers"] > 1 and cnt["device_slabs"] == 1
+    assert len(h[0]) > 300 and h[5][1].sum() > 0
+
+
+def _slab_bounds(bam, first, slab_bytes):
+    """inflated offsets where cv_bam_view_plan ends its slabs, for a view that starts at inflated offset `first`"""
+    mem = C.members(bam)
+    k = max(i for i, m in enumerate(mem) if m[2] <= first)
+    out, run = [], 0
+    for m in mem[k:]:
+        if m[3] == 0 and m is mem[-1]:
+            break
+        run += m[1]
+        if run >= slab_bytes:
+            out.append(m[2] + m[3]); run = 0
+    return out
+
+
+def test_several_slabs(tmp_path, noisy, monkeypatch):
+    """case 4: a record and a run of more than dcov reads of one POS straddle a slab boundary; same results as one slab
+    and as the host route"""
+    ref, lines = noisy
+    dcov = 3
+    k = len(lines) // 6
+    f = lines[k].split("\t")
+    f[4] = "60"
+    planted = lines[:k] + ["\t".join(["planted%d" % i] + f[1:]) for i in range(70)] + lines[k:]
+    bam = str(tmp_path / "s.bam")
+    where = C.write_bam(bam, planted, [("ctgA", len(ref))], block_payload=4093)
+    mem = C.members(bam)
+    # the first slab is to end inside the planted run, behind more than dcov of its reads
+    run0, run1 = where[k + dcov + 2][0], where[k + 60][0]
+    m = next(i for i, x in enumerate(mem) if run0 < x[2] + x[3] < run1)
+    m0 = max(i for i, x in enumerate(mem) if x[2] <= where[0][0])
+    slab = sum(x[1] for x in mem[m0:m + 1])
+    bounds = _slab_bounds(bam, where[0][0], slab)
+    assert len(bounds) >= 5 and bounds[0] == mem[m][2] + mem[m][3], "choose another place for the planted run"
+    assert any(o < b < o + n for b in bounds for o, n in where), "no record straddles a slab boundary"
+    inside = [i for i, (o, n) in enumerate(where) if o + n > bounds[0]][0]
+    assert k + dcov < inside <= k + 60, "the planted run does not straddle the first slab boundary"
+    one_h, one_d, cnt = both(bam, ref, **dict(EVC, dcov=dcov))
+    clean(cnt)
+    assert cnt["device_slabs"] == 1
+    monkeypatch.setenv("CV_BAM_SLAB_BYTES", str(slab))
+    many, _st, cnt = feed(bam, "device", ref=ref, **dict(EVC, dcov=dcov))
+    clean(cnt)
+    assert cnt["device_slabs"] == len(bounds) + (1 if bounds[-1] < where[-1][0] + where[-1][1] else 0) >= 5, cnt
+    _same(one_h, many)
+    # and the tensor pass with set centres, where the depth cap is what the planted run is about
+    centers = np.arange(20, len(ref) - 20, 37, dtype=np.int64)
+    hh, _s, _c = feed(bam, "host", centers=centers, ref=ref, dcov=dcov)
+    dd, _s, cnt = feed(bam, "device", centers=centers, ref=ref, dcov=dcov)
+    clean(cnt)
+    _same(hh, dd)
+
+
+def _expected_fetch(bam, start, end_rec, slab_bytes):
+    """(slabs, members) a view that starts at inflated offset `start` reads when the record (offset, length) end_rec ends
+    it -- the slab in which that record is complete is the last one: no prefetch, so not one slab is read in vain --
+    or, end_rec None, when it runs to the end of the file"""
+    mem = C.members(bam)
+    k = max(i for i, m in enumerate(mem) if m[2] <= start)
+    bounds = _slab_bounds(bam, start, slab_bytes)
+    if end_rec is None:
+        return len(bounds) + 1, len(mem) - k                  # (the end-of-file marker closes, or is, the last slab)
+    last = sum(1 for b in bounds if b < end_rec[0] + end_rec[1])
+    upto = bounds[last] if last < len(bounds) else None
+    return last + 1, sum(1 for m in mem[k:] if upto is None or m[2] + m[3] <= upto)
+
+
+def test_end_of_view(tmp_path, noisy, monkeypatch):
+    """case 5: a region that ends mid-file, and a contig followed by another: the device stops where the host stops, and
+    reads exactly the slabs up to the one that holds the first record behind the view (at most one fetched past the end
+    is what is asked; this loop fetches none)"""
+    ref, lines = noisy
+    other = [l.replace("\tctgA\t", "\tctgB\t", 1) for l in lines[:3000]]
+    bam = str(tmp_path / "e.bam")
+    where = C.write_bam(bam, lines + other, [("ctgA", len(ref)), ("ctgB", len(ref))], block_payload=20000)
+    pos = [int(l.split("\t")[3]) - 1 for l in lines]
+    slab = os.path.getsize(bam) // 12
+    monkeypatch.setenv("CV_BAM_SLAB_BYTES", str(slab))
+    for region, end_index in (((2000, 9000), next(i for i, p in enumerate(pos) if p >= 9000)), ((None, None), len(lines))):
+        h, d, cnt = both(bam, ref, region=region, **EVC)
+        clean(cnt)
+        assert h[4] == d[4] > 0
+        slabs, members = _expected_fetch(bam, where[0][0], where[end_index], slab)
+        assert 1 < slabs < 12 and (cnt["device_slabs"], cnt["members"]) == (slabs, members), (cnt, slabs, members)
+    # the second contig, whose reads sit behind all of the first one's: to the end of the file
+    h, d, cnt = both(bam, ref, centers=np.arange(100, 5000, 53, dtype=np.int64), region=(None, None), ctg="ctgB", dcov=3)
+    clean(cnt)
+    slabs, members = _expected_fetch(bam, where[len(lines)][0], None, slab)
+    assert (cnt["device_slabs"], cnt["members"]) == (slabs, members), (cnt, slabs, members)
+
+
+@pytest.mark.parametrize("handed_over", ["second", "first"])
+def test_state_across_a_handed_over_slab(tmp_path, noisy, monkeypatch, handed_over):
+    """case 6, where it bites: a run of more than dcov reads of one POS straddles the first slab boundary, and one of the
+    two slabs holds a placeholder-CIGAR record, so it goes to the host route: the depth cap and the late mark of the run's
+    second part depend on prev_pos / depth_cap / evc_prev_pos handed from one route to the other through the handle"""
+    ref, lines = noisy
+    dcov = 3
+    k = len(lines) // 6
+    f = lines[k].split("\t")
+    f[4] = "60"
+    run = ["\t".join(["planted%d" % i] + f[1:]) for i in range(70)]
+    if handed_over == "second":
+        planted = lines[:k] + run + ["\t".join(["ph"] + f[1:])] + lines[k:]
+    else:
+        planted = lines[:5] + ["\t".join(["ph"] + lines[5].split("\t")[1:])] + lines[5:k] + run + lines[k:]
+    r0 = next(i for i, l in enumerate(planted) if l.startswith("planted0\t"))
+    ph = next(i for i, l in enumerate(planted) if l.startswith("ph\t"))
+    bam = str(tmp_path / "x.bam")
+    where = C.write_bam(bam, planted, [("ctgA", len(ref))], block_payload=4093)
+    mem = C.members(bam)
+    m = next(i for i, x in enumerate(mem) if where[r0 + dcov + 2][0] < x[2] + x[3] < where[r0 + 60][0])
+    m0 = max(i for i, x in enumerate(mem) if x[2] <= where[0][0])
+    slab = sum(x[1] for x in mem[m0:m + 1])
+    bounds = _slab_bounds(bam, where[0][0], slab)
+    assert len(bounds) >= 5 and bounds[0] == mem[m][2] + mem[m][3]
+    inside = [i for i, (o, n) in enumerate(where) if o + n > bounds[0]][0]
+    assert r0 + dcov < inside <= r0 + 60, "the planted run does not straddle the first slab boundary"
+    assert (bounds[0] <= where[ph][0] and where[ph][0] + where[ph][1] <= bounds[1]) if handed_over == "second" else where[ph][0] + where[ph][1] < bounds[0]
+    monkeypatch.setenv("CV_BAM_SLAB_BYTES", str(slab))
+    centers = np.arange(20, len(ref) - 20, 37, dtype=np.int64)
+    for kw in (dict(centers=centers, dcov=dcov), dict(EVC, dcov=dcov)):
+        h, hs, _c = feed(bam, "host", ref=ref, **kw)
+        d, ds, cnt = feed(bam, "device", ref=ref, **kw)
+        _same(h, d)
+        assert hs == ds
+        assert cnt["handed_over_slabs"] == 1 and cnt["device_slabs"] >= 5 and cnt["host_members"] == 0, cnt
+        assert cnt["device_records"] + cnt["handed_over_records"] == len(planted)
+
+
+def test_state_across_routes(tmp_path, noisy, monkeypatch):
+    """case 6: one handle, the first half of a view through one route and the second through the other"""
+    ref, lines = noisy
+    bam = str(tmp_path / "h.bam")
+    C.write_bam(bam, lines, [("ctgA", len(ref))])
+    # two views that meet at 20000 / 20001 take some reads twice; what matters is that every order of routes gives the
+    # same counters, late marks and depth caps as one route alone
+    halves = [(None, 20000), (20001, None)]
+    want = feed(bam, None, ref=ref, halves=[("host", halves[0]), ("host", halves[1])], **EVC)
+    for a, b in (("host", "device"), ("device", "host"), ("device", "device")):
+        got = feed(bam, None, ref=ref, halves=[(a, halves[0]), (b, halves[1])], **EVC)
+        _same(want[0], got[0])
+        assert want[1] == got[1]
+        assert got[2]["device_views"] == (a == "device") + (b == "device") and got[2]["handed_over_slabs"] == 0
+    # and split by slab: a tiny slab size hands the running state from slab to slab many times
+    monkeypatch.setenv("CV_BAM_SLAB_BYTES", "70000")
+    got = feed(bam, None, ref=ref, halves=[("device", halves[0]), ("host", halves[1])], **EVC)
+    _same(want[0], got[0])
+    assert got[2]["device_slabs"] > 3
+
+
+def _raises(bam, route, ref="x" * 300, ctg="ctgA", **kw):
+    from clairvoyante_amd import _lib
+    with pytest.raises(_lib.CvError) as e:
+        feed(bam, route, ref=ref, centers=np.asarray([50], dtype=np.int64), ctg=ctg, **kw)
+    return str(e.value)
+
+
+def test_hand_overs(tmp_path, noisy):
+    """case 7: what the device does not vouch for goes to the host from the same bytes, same result or same exception"""
+    from test_bam_native import long_cigar_records, _rewrite_with_patched_stream, _first_record_offset
+    # a placeholder CIGAR whose operations sit in the CG:B,I tag
+    recs = long_cigar_records()
+    rng = np.random.RandomState(8)
+    ref = "".join("ACGT"[i] for i in rng.randint(0, 4, 200000))
+    centers = np.asarray([90, 100, 101, 117, 5000, 50000, 52600, 52700, 60000, 199990], dtype=np.int64)
+    bam = str(tmp_path / "long.bam")
+    C.write_bam(bam, recs, [("ctgA", 200000)])
+    h, _s, _c = feed(bam, "host", centers=centers, ref=ref, dcov=250)
+    d, _s, cnt = feed(bam, "device", centers=centers, ref=ref, dcov=250)
+    _same(h, d)
+    assert cnt["device_views"] == 1 and cnt["handed_over_slabs"] > 0 and cnt["handed_over_records"] == 3 and h[1].sum() > 0
+    # a flipped payload bit, in a member behind the ones the reader inflates when it opens the file: the device gives
+    # the member to the host, whose CRC check fails
+    nref, nlines = noisy
+    good = str(tmp_path / "good.bam")
+    C.write_bam(good, nlines, [("ctgA", len(nref))], block_payload=4093)
+    blob = bytearray(open(good, "rb").read())
+    m = C.members(good)[500]
+    blob[m[0] + 18 + (m[1] - 26) // 2] ^= 0x10
+    flipped = str(tmp_path / "flipped.bam")
+    open(flipped, "wb").write(bytes(blob))
+    shutil.copy(good + ".bai", flipped + ".bai")
+    texts = [_raises(flipped, r, ref=nref) for r in ("host", "device")]
+    assert texts[0] == texts[1] and "corrupt BGZF block at offset %d" % m[0] in texts[0], texts
+    # records behind intact block checksums: block_size 16, l_seq -1
+    plain = str(tmp_path / "plain.bam")
+    C.write_bam(plain, C.corner_records(), C.corner_refs())
+    for name, field, value in (("bs16", 0, 16), ("lseq", 4 + 16, -1)):
+        def patch(stream):
+            p = _first_record_offset(stream)
+            p += 4 + struct.unpack_from("<i", stream, p)[0]           # the second record
+            stream[p + field:p + field + 4] = struct.pack("<i", value)
+        bad = str(tmp_path / (name + ".bam"))
+        _rewrite_with_patched_stream(plain, bad, patch)
+        shutil.copy(plain + ".bai", bad + ".bai")
+        texts = [_raises(bad, r) for r in ("host", "device")]
+        assert texts[0] == texts[1] and "corrupt record" in texts[0], texts
+    # a .bai with an entry that points into the middle of a record
+    ref, lines = noisy
+    mid = str(tmp_path / "mid.bam")
+    C.write_bam(mid, lines, [("ctgA", len(ref))])
+    bai = bytearray(open(mid + ".bai", "rb").read())
+    n_intv = struct.unpack_from("<i", bai, len(bai) - 8 * 3 - 4)[0]
+    assert n_intv == 3
+    v = struct.unpack_from("<Q", bai, len(bai) - 16)[0]
+    bai[len(bai) - 16:len(bai) - 8] = struct.pack("<Q", v + 9)
+    open(mid + ".bai", "wb").write(bytes(bai))
+    h, _s, _c = feed(mid, "host", ref=ref, **EVC)
+    d, _s, cnt = feed(mid, "device", ref=ref, **EVC)
+    _same(h, d)
+    assert cnt["handed_over_slabs"] == 1 and cnt["device_slabs"] == 1 and cnt["handed_over_records"] == len(lines)
+    # no .bai: the host route, counted
+    os.remove(mid + ".bai")
+    d2, _s, cnt = feed(mid, "device", ref=ref, **EVC)
+    _same(h, d2)
+    assert cnt["host_views"] == 1 and cnt["device_views"] == 0
+
+
+def _fasta_with_index(name, tmp_path):
+    fa = str(tmp_path / (name + ".fa"))
+    shutil.copy(os.path.join(G, name + ".fa"), fa)
+    raw = open(fa, "rb").read().split(b"\n")
+    hdr, line = raw[0], raw[1]
+    length = 0
+    for l in raw[1:]:
+        if l.startswith(b">"):
+            break
+        length += len(l)
+    with open(fa + ".fai", "w") as fh:
+        fh.write("%s\t%d\t%d\t%d\t%d\n" % (hdr[1:].split()[0].decode(), length, len(hdr) + 1, len(line), len(line) + 1))
+    return fa, length
+
+
+def _golden_bam(name, tmp_path):
+    recs = [l.rstrip("\n") for l in open(os.path.join(G, name + ".sam")) if not l.startswith("@")]
+    fa, length = _fasta_with_index(name, tmp_path)
+    bam = str(tmp_path / (name + ".bam"))
+    C.write_bam(bam, recs, [("ctgA", length), ("other", 10)], block_payload=9001)
+    return bam, fa
+
+
+@pytest.mark.parametrize("name", ["plain", "region", "noleftedge", "noisy", "eqx", "handmade", "handmade_dcov1"])
+def test_createtensor_rows_equal_reference_rows_through_the_device(name, tmp_path, monkeypatch):
+    """case 8: the CreateTensor drop-in with --samtools native and CV_BAM_DECODE=device reproduces the committed rows"""
+    from clairvoyante_amd import CreateTensor
+    from test_pileup_oracle import load_case, norm_opts
+    _, _, _, opts, want = load_case(name)
+    bam, fa = _golden_bam(name, tmp_path)
+    a = dict(bam_fn=bam, ref_fn=fa, can_fn=os.path.join(G, name + ".can"), tensor_fn=str(tmp_path / "out.gz"), minMQ=0,
+             ctgName="ctgA", ctgStart=None, ctgEnd=None, samtools="native", dcov=250, minCoverage=0, considerleftedge=True)
+    a.update(norm_opts(opts))
+    monkeypatch.setenv("CV_BAM_DECODE", "device")
+    counts()
+    CreateTensor.OutputAlnTensor(types.SimpleNamespace(**a))
+    clean(counts())
+    assert sorted(gzip.open(a["tensor_fn"], "rt").read().splitlines()) == sorted(want)
+
+
+@pytest.mark.parametrize("name", ["plain", "region_bed", "noisy", "lowcov"])
+def test_extract_candidates_rows_equal_reference_rows_through_the_device(name, tmp_path, monkeypatch):
+    from clairvoyante_amd import ExtractVariantCandidates as evc
+    from test_pileup_oracle import load_evc_case
+    import json
+    aln, _, _, opts, _, want = load_evc_case(name)
+    opts = dict(opts)
+    meta = json.load(open(os.path.join(G, name + ".evc.args.json")))["options"]
+    if "bed_fn" in meta:
+        opts["bed_fn"] = os.path.join(G, meta["bed_fn"])
+    bam, fa = _golden_bam(aln, tmp_path)
+    a = dict(bam_fn=bam, ref_fn=fa, bed_fn=None, can_fn=str(tmp_path / "can.gz"), threshold=0.125, minCoverage=4, minMQ=0,
+             gen4Training=False, candidates=7000000, genomeSize=3000000000, ctgName="ctgA", ctgStart=None, ctgEnd=None,
+             samtools="native")
+    a.update(opts)
+    monkeypatch.setenv("CV_BAM_DECODE", "device")
+    counts()
+    evc.MakeCandidates(types.SimpleNamespace(**a))
+    clean(counts())
+    assert gzip.open(a["can_fn"], "rt").read().splitlines() == want
+
+
+def test_callvarbam_end_to_end(tmp_path, oracle, monkeypatch):
+    """case 9: callVarBam --samtools native writes the same VCF bytes with CV_BAM_DECODE=host and =device"""
+    from clairvoyante_amd import callVarBam
+    from test_gpu_pileup import _checkpoint
+    chk = _checkpoint(oracle, tmp_path)
+    for name, extra in (("plain", []), ("noisy", ["--ctgStart", "300", "--ctgEnd", "1900", "--dcov", "3"])):
+        bam, fa = _golden_bam(name, tmp_path)
+        vcf = {}
+        for route in ("host", "device"):
+            monkeypatch.setenv("CV_BAM_DECODE", route)
+            counts()
+            args = callVarBam.build_parser().parse_args(
+                ["--chkpnt_fn", chk, "--ref_fn", fa, "--ctgName", "ctgA", "--threshold", "0.125", "--minCoverage", "2", "--bam_fn", bam,
+                 "--samtools", "native", "--call_fn", str(tmp_path / (name + route + ".vcf"))] + extra)
+            callVarBam.Run(args)
+            cnt = counts()
+            vcf[route] = open(args.call_fn, "rb").read()
+            if route == "device":
+                assert cnt["device_views"] > 0
+                clean(cnt, views=cnt["device_views"])
+            else:
+                assert cnt["device_views"] == 0 and cnt["host_views"] > 0
+        assert vcf["host"] == vcf["device"] and vcf["host"].count(b"\n") > 10
+
+
+def test_empty_inputs_and_null_arguments(tmp_path):
+    """case 10"""
+    import ctypes
+    from clairvoyante_amd import _lib
+    bam = str(tmp_path / "c.bam")
+    C.write_bam(bam, C.corner_records()[:-1], C.corner_refs() + [("empty", 77)])
+    for ctg, region in (("zzz", (None, None)), ("empty", (None, None)), ("nope", (None, None)), ("ctgA", (312, 318))):
+        h, d, cnt = both(bam, C.CORNER_REF, C.CORNER_CENTERS, region=region, ctg=ctg, dcov=250)
+        assert h[4] == d[4] == 0 and cnt["device_views"] == 1 and cnt["handed_over_slabs"] == 0 and cnt["device_records"] == 0
+    lib = _lib.load()
+    i8 = (ctypes.c_int64 * 9)()
+    p = ctypes.c_void_p()
+    for rc in (lib.cv_bam_view_plan_begin(None, b"ctgA", 0, 0, 0, None), lib.cv_bam_view_plan(None, 1, None, None, None, None),
+               lib.cv_bam_plan_inflate_host(None, 0, None), lib.cv_bam_view_params(None, i8), lib.cv_bam_dev_create(0, None),
+               lib.cv_bam_dev_view(None, None, None, 1, 1, None, None, None), lib.cv_pileup_bam_params(None, i8),
+               lib.cv_pileup_add_bam_dev(None, None, 0, None, 0, 0, None, None)):
+        assert rc == 1 and (b"null" in lib.cv_last_error() or b"bad argument" in lib.cv_last_error())
+    lib.cv_bam_dev_destroy(None)
+    assert p.value is None
