@@ -540,13 +540,17 @@ __global__ __launch_bounds__(256, 2) void conv_tm(const f4 *__restrict__ in_tm, 
     CV_STAMP_END(MODE == 1 && KH == 2 && CINB == 1 && FRONT == 0, 6);
 }
 
+// front2_tm: first-layer output column j (0 / 1) of wave nt of a pair -- {1, 2} and {0, 3}: 7 and 5 MFMAs per raw row
+__device__ constexpr int f2col(int nt, int j) { return nt == 0 ? 1 + j : 3 * j; }
+
 // ---------------------------------------------------------------------------
 // conv1 k(1,4) + pool(5) + conv2 k(2,4) + pool(4) of the full topology with the FIRST LAYER SHARED between the two
 // waves of a group (variant bit 6).  conv_tm<2,1,2,4,29,5> gives each of the two output tiles of conv2 its own wave,
 // and both waves push the whole first layer through their registers: its 33 MFMA rows, pooling windows and -- the
 // expensive part -- 29 rows of SELU are computed twice.  Here a workgroup (4 waves = 2 groups x 2 tiles) walks the 29
-// pooled first-layer rows in chunks of CH: in phase A the two waves of a group each produce HALF of the chunk's rows
-// (pre-activations of CH/2 + 4 input rows, running maxima, one SELU per pooled row) into an LDS row buffer laid out
+// pooled first-layer rows in chunks of CH: in phase A the two waves of a group each produce TWO OF THE FOUR COLUMNS of
+// the chunk's rows (pre-activations of CH new input rows behind the four carried from the chunk before, block maxima,
+// one SELU per pooled value: every raw row is computed once per group) into an LDS row buffer laid out
 // as B fragments; after a barrier both waves run conv2 over the chunk from LDS (phase B: 96 MFMA steps per
 // position, kh-row and pooling state kept in registers across chunks), second barrier, next chunk.  Per position a
 // wave now evaluates 8 + 16 SELU'd values x lanes instead of 16 + 16.  Arithmetic and order per output value are
@@ -656,57 +660,90 @@ __global__ __launch_bounds__(FLAT ? 128 : 256, 2) void front2_tm(const float *__
         }
     };
 
+    // ---- the first layer: wave nt makes the output columns f2col(nt, 0 / 1) of EVERY row of the segment (7 and 5 MFMAs
+    // per raw row), so each raw row is computed once: the last P1 - 1 pre-activation rows (+ b1) of its columns stay in
+    // tc across chunks and a chunk of CH pooled rows needs CH new raw rows.  Their X rows are fetched a chunk ahead.
+    static_assert(CH == 6, "the block pooling below is written for six rows per chunk");
+    f4 tc[P1 - 1][2];
+    float xn[CH][4];                                     // raw rows c0 + 4 .. c0 + 9 of the chunk to come
+    const bool first = __builtin_amdgcn_readfirstlane(nt) == 0;      // (wave-uniform: the column code is picked by a scalar branch)
+    auto load_raw = [&](int row0) {
+#pragma unroll
+        for (int r = 0; r < CH; r++) {
+            const int rr = row0 + r < CV_INPUT_H ? row0 + r : CV_INPUT_H - 1;   // rows past the input feed unused outputs
+#pragma unroll
+            for (int w = 0; w < 4; w++) xn[r][w] = xp[rr * 16 + w * 4];
+        }
+    };
+    // one raw row of this wave's two columns: per value the MFMAs in ascending kw into a zero accumulator, then + b1
+    auto conv1_row = [&](auto NTc, const float (&xr)[4], f4 (&t)[2]) {
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            constexpr int N = decltype(NTc)::value;
+            const int wo = f2col(N, j);
+            f4 acc = zero;
+#pragma unroll
+            for (int kw = 0; kw < 4; kw++) {
+                const int wi = wo + kw - 1;
+                if (wi < 0 || wi > 3) continue;
+                acc = mfma4(A1[kw], xr[wi], acc);
+            }
+            t[j] = acc + b1;
+        }
+    };
+    // CH new rows behind the four carried ones: t0 .. t9 give the pooled rows o_i = max(t_i .. t_i+4) with shared
+    // middles c1 = max3(t2,t3,t4), c2 = max3(t5,t6,t7) -- eight v_max3 per value for six rows -- and one SELU per pooled row
+    auto phase_a = [&](auto NTc, int cn) {
+        constexpr int N = decltype(NTc)::value;
+        f4 t[CH + P1 - 1][2];
+#pragma unroll
+        for (int r = 0; r < P1 - 1; r++)
+#pragma unroll
+            for (int j = 0; j < 2; j++) t[r][j] = tc[r][j];
+#pragma unroll
+        for (int r = 0; r < CH; r++) conv1_row(NTc, xn[r], t[P1 - 1 + r]);
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int w = f2col(N, j);
+            const f4 c1 = max3_4(t[2][j], t[3][j], t[4][j]);
+            const f4 c2 = max3_4(t[5][j], t[6][j], t[7][j]);
+            const f4 o[CH] = {max3_4(t[0][j], t[1][j], c1), max3_4(t[1][j], c1, t[5][j]), max3_4(c1, t[5][j], t[6][j]),
+                              max3_4(t[3][j], t[4][j], c2), max3_4(t[4][j], c2, t[8][j]), max3_4(c2, t[8][j], t[9][j])};
+#pragma unroll
+            for (int i = 0; i < CH; i++)
+                if (i < cn) myrows[(size_t)(i * 4 + w) * 64] = selu4(o[i]);
+        }
+#pragma unroll
+        for (int r = 0; r < P1 - 1; r++)
+#pragma unroll
+            for (int j = 0; j < 2; j++) tc[r][j] = t[CH + r][j];
+    };
+    {   // priming: the first window's four rows (what a segment pays for starting), and the first chunk's raw rows
+        float xw[P1 - 1][4];
+#pragma unroll
+        for (int r = 0; r < P1 - 1; r++)
+#pragma unroll
+            for (int w = 0; w < 4; w++) xw[r][w] = xp[(oa + r) * 16 + w * 4];
+        load_raw(oa + P1 - 1);
+        if (first) {
+#pragma unroll
+            for (int r = 0; r < P1 - 1; r++) conv1_row(std::integral_constant<int, 0>{}, xw[r], tc[r]);
+        } else {
+#pragma unroll
+            for (int r = 0; r < P1 - 1; r++) conv1_row(std::integral_constant<int, 1>{}, xw[r], tc[r]);
+        }
+    }
+
 #pragma unroll 1
     for (int c0 = oa; c0 < pend; c0 += CH) {
         const int cn = pend - c0 < CH ? pend - c0 : CH;
-        // ---- phase A: this wave's half of the chunk's first-layer rows
-        const int half = (cn + 1) >> 1;
-        const int a0 = c0 + nt * half;
-        const int a1 = a0 + half < c0 + cn ? a0 + half : c0 + cn;
-        if (a0 < a1) {
-            // HALF pooled rows need HALF + 4 pre-activation rows; all of them are kept in registers so that the 5-row
-            // windows share their middle: c = max3(t2,t3,t4), rows = max3(t0,t1,c), max3(t1,c,t5), max3(c,t5,t6) --
-            // four v_max3 per value for three rows, where a running-maximum walk takes four v_max per value and ROW
-            static_assert(CH == 6, "the block pooling below is written for three rows per wave");
-            constexpr int HALF = CH / 2, NRAW = HALF + P1 - 1;
-            float xr[NRAW][4];
-#pragma unroll
-            for (int r = 0; r < NRAW; r++) {
-                const int rr = a0 + r < CV_INPUT_H ? a0 + r : CV_INPUT_H - 1;   // rows past the input feed unused outputs
-#pragma unroll
-                for (int w = 0; w < 4; w++) xr[r][w] = xp[rr * 16 + w * 4];
-            }
-            CV_PHASE(0);
-            CV_PHASE_DRAIN();                            // (development probe: the raw rows' round trip on its own)
-            CV_PHASE(3);
-            f4 t[NRAW][4];
-#pragma unroll
-            for (int r = 0; r < NRAW; r++) {
-                f4 acc[4];
-#pragma unroll
-                for (int w = 0; w < 4; w++) acc[w] = zero;
-#pragma unroll
-                for (int kw = 0; kw < 4; kw++)
-#pragma unroll
-                    for (int wo = 0; wo < 4; wo++) {
-                        const int wi = wo + kw - 1;
-                        if (wi < 0 || wi > 3) continue;
-                        acc[wo] = mfma4(A1[kw], xr[r][wi], acc[wo]);
-                    }
-#pragma unroll
-                for (int w = 0; w < 4; w++) t[r][w] = acc[w] + b1;
-            }
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-                const f4 c = max3_4(t[2][w], t[3][w], t[4][w]);
-                const f4 o0 = max3_4(t[0][w], t[1][w], c);
-                const f4 o1 = max3_4(t[1][w], c, t[5][w]);
-                const f4 o2 = max3_4(c, t[5][w], t[6][w]);
-                myrows[(size_t)((a0 - c0 + 0) * 4 + w) * 64] = selu4(o0);
-                if (a0 + 1 < a1) myrows[(size_t)((a0 - c0 + 1) * 4 + w) * 64] = selu4(o1);
-                if (a0 + 2 < a1) myrows[(size_t)((a0 - c0 + 2) * 4 + w) * 64] = selu4(o2);
-            }
-        }
+        // ---- phase A: this wave's two columns of the chunk's first-layer rows
+        CV_PHASE(0);
+        CV_PHASE_DRAIN();                                // (development probe: what is left of the raw rows' round trip)
+        CV_PHASE(3);
+        if (first) phase_a(std::integral_constant<int, 0>{}, cn);
+        else phase_a(std::integral_constant<int, 1>{}, cn);
+        if (c0 + CH < pend) load_raw(c0 + CH + P1 - 1);  // the next chunk's raw rows travel under phase B
         CV_PHASE(0);
         __syncthreads();
         CV_PHASE(2);

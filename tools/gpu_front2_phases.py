@@ -21,8 +21,8 @@ ph = np.stack([r[:, 0], r[:, 1], r[:, 2], r[:, 3] >> np.uint64(8)], 1).astype(np
 tot = ph.sum(1)
 print("batch %d: %d wave records of front2_tm<6> (newest 4096 of %d)" % (n, len(r), int(cnt[7])))
 print("  cycles per wave (s_memtime): median %.0f  p10 %.0f  p90 %.0f" % (np.median(tot), np.percentile(tot, 10), np.percentile(tot, 90)))
-names = ("producer half (3 first-layer rows: 84 MFMA + pool + 48 SELU + LDS writes)", "conv2 over the chunk (6 x 96 MFMA + pool + 96 SELU + stores)",
-         "the two barriers of a chunk", "raw X rows: wait for the strided loads")
+names = ("producer half (2 columns of 6 first-layer rows: 42 / 30 MFMA + pool + 48 SELU + LDS writes)", "conv2 over the chunk (6 x 96 MFMA + pool + 96 SELU + stores)",
+         "the two barriers of a chunk", "raw X rows: what is left of the prefetched loads' round trip")
 for i, nm in enumerate(names):
     print("  %-82s %6.3f of the wave's cycles   (median %.0f cycles)" % (nm, (ph[:, i] / tot).mean(), np.median(ph[:, i])))
 for w in range(4):
@@ -30,6 +30,6 @@ for w in range(4):
     if sel.any():
         print("  wave %d (group %d, tile %d): producer %.3f  conv2 %.3f  barriers %.3f  X wait %.3f" % (
             w, w >> 1, w & 1, *[(ph[sel, i] / tot[sel]).mean() for i in range(4)]))
-# the ideal: MFMA issue of one wave (5 chunks x 84 + 28 x 96 + 48 first + 48 last-row MFMAs ~ 3 200) x 32 cycles x 2 waves per SIMD
-print("  MFMA issue of the two waves of a SIMD: ~%.0f cycles (3 156 MFMAs x 32 x 2)" % (3156 * 32 * 2))
+# the ideal: MFMA issue of one wave (33 x 12 / 2 first-layer + 28 x 96 + 48 last-row MFMAs = 2 934) x 32 cycles x 2 waves per SIMD
+print("  MFMA issue of the two waves of a SIMD: ~%.0f cycles (2 934 MFMAs x 32 x 2)" % (2934 * 32 * 2))
 m.close()
