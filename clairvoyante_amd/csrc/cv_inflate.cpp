@@ -44,10 +44,11 @@ inline uint32_t reverse_bits(uint32_t code, int len)
 }
 
 // canonical Huffman code of `lens` -> decode tables.  make(sym, len) gives the entry of a symbol.
-// Returns false for an over-subscribed code; an incomplete code leaves invalid (zero) entries behind, which
-// the decoder reports when it meets one (a single distance code of one bit is legal and ends up that way).
+// Returns false for an over-subscribed code and, as zlib does, for an incomplete one -- unless it is no code at all or
+// (single_ok: the literal/length and the distance code, not the code-length code) a single code of one bit, whose
+// other half stays an invalid (zero) entry that the decoder reports when it meets it.
 template <typename MAKE>
-bool build(const uint8_t *lens, int n, uint32_t *first, int fbits, uint32_t *sub, int subsize, int max_sub, MAKE make)
+bool build(const uint8_t *lens, int n, uint32_t *first, int fbits, uint32_t *sub, int subsize, int max_sub, bool single_ok, MAKE make)
 {
     int count[MAXBITS + 1] = {0};
     for (int i = 0; i < n; i++) count[lens[i]]++;
@@ -55,12 +56,15 @@ bool build(const uint8_t *lens, int n, uint32_t *first, int fbits, uint32_t *sub
     uint32_t next[MAXBITS + 2];
     uint32_t code = 0;
     int64_t left = 1;
+    int max = 0;
     for (int l = 1; l <= MAXBITS; l++) {
         left = left * 2 - count[l];
         if (left < 0) return false;
+        if (count[l]) max = l;
         code = (code + (uint32_t)count[l - 1]) << 1;
         next[l] = code;
     }
+    if (left > 0 && max > 0 && !(single_ok && max == 1)) return false;
     memset(first, 0, sizeof(uint32_t) << fbits);
     int nsub = 0;
     for (int s = 0; s < n; s++) {
@@ -170,8 +174,8 @@ static int64_t inflate_core(const uint8_t *src, int64_t n, uint8_t *dst, int64_t
             for (; i < 280; i++) lens[i] = 7;
             for (; i < 288; i++) lens[i] = 8;
             for (i = 0; i < 32; i++) lens[288 + i] = 5;
-            if (!build(lens, 288, T.lit, LBITS, T.lsub, LSUB, 288, make_litlen)) return -1;
-            if (!build(lens + 288, 32, T.dist, DBITS, T.dsub, DSUB, 32, make_dist)) return -1;
+            if (!build(lens, 288, T.lit, LBITS, T.lsub, LSUB, 288, true, make_litlen)) return -1;
+            if (!build(lens + 288, 32, T.dist, DBITS, T.dsub, DSUB, 32, true, make_dist)) return -1;
         } else {                                                     // dynamic code
             const int hlit = (int)(buf & 31) + 257, hdist = (int)((buf >> 5) & 31) + 1, hclen = (int)((buf >> 10) & 15) + 4;
             DROP(14);
@@ -186,7 +190,7 @@ static int64_t inflate_core(const uint8_t *src, int64_t n, uint8_t *dst, int64_t
             }
             uint32_t cltab[128];
             uint32_t nosub[1];
-            if (!build(cl, 19, cltab, 7, nosub, 1, 0, [](int s, int l) { return entry((uint32_t)s, K_LIT, 0, (uint32_t)l); }))
+            if (!build(cl, 19, cltab, 7, nosub, 1, 0, false, [](int s, int l) { return entry((uint32_t)s, K_LIT, 0, (uint32_t)l); }))
                 return -1;
             uint8_t lens[288 + 32];
             memset(lens, 0, sizeof(lens));
@@ -212,8 +216,8 @@ static int64_t inflate_core(const uint8_t *src, int64_t n, uint8_t *dst, int64_t
             if (all[256] == 0) return -1;                            // no end-of-block code
             memcpy(lens, all, (size_t)hlit);
             memcpy(lens + 288, all + hlit, (size_t)hdist);
-            if (!build(lens, 288, T.lit, LBITS, T.lsub, LSUB, 288, make_litlen)) return -1;
-            if (!build(lens + 288, 32, T.dist, DBITS, T.dsub, DSUB, 32, make_dist)) return -1;
+            if (!build(lens, 288, T.lit, LBITS, T.lsub, LSUB, 288, true, make_litlen)) return -1;
+            if (!build(lens + 288, 32, T.dist, DBITS, T.dsub, DSUB, 32, true, make_dist)) return -1;
         }
         // ---- the symbols of this block.  FAST: input left to load and room for three literals plus the longest
         // match with its copy slop -- no per-symbol bounds checks on the output, no bit-count checks.

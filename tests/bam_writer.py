@@ -21,9 +21,12 @@ def reg2bin(beg, end):
     return 0
 
 
-def _bgzf_block(data):
-    co = zlib.compressobj(6, zlib.DEFLATED, -15)
-    comp = co.compress(data) + co.flush()
+def _bgzf_block(data, compress=None):
+    if compress is None:
+        co = zlib.compressobj(6, zlib.DEFLATED, -15)
+        comp = co.compress(data) + co.flush()
+    else:
+        comp = compress(data)
     bsize = len(comp) + 25
     return (b"\x1f\x8b\x08\x04" + b"\0\0\0\0" + b"\0\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, bsize)
             + comp + struct.pack("<II", zlib.crc32(data) & 0xffffffff, len(data)))
@@ -60,8 +63,9 @@ def encode_record(fields, tid_of):
     return struct.pack("<i", len(out)) + out, tid, pos, pos + span
 
 
-def write_bam(path, sam_lines, refs, block_payload=60000, index=True, header_text=None):
-    """sam_lines: records (header lines ignored) sorted by (contig order, POS); refs: [(name, length)]."""
+def write_bam(path, sam_lines, refs, block_payload=60000, index=True, header_text=None, compress=None):
+    """sam_lines: records (header lines ignored) sorted by (contig order, POS); refs: [(name, length)].
+    compress: raw bytes -> raw DEFLATE bytes of one BGZF member (default: zlib, level 6)."""
     tid_of = {n: i for i, (n, _l) in enumerate(refs)}
     text = (header_text if header_text is not None else
             "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % r for r in refs)).encode()
@@ -82,7 +86,7 @@ def write_bam(path, sam_lines, refs, block_payload=60000, index=True, header_tex
     for off in range(0, len(stream), block_payload):
         chunk = bytes(stream[off:off + block_payload])
         blocks.append((len(out), off, len(chunk)))
-        out += _bgzf_block(chunk)
+        out += _bgzf_block(chunk, compress)
     out += _EOF
     with open(path, "wb") as fh:
         fh.write(out)
