@@ -1,0 +1,150 @@
+"""Pairs the truth-variant tensors with a share of the non-variant tensors: command line, inputs, output rows and log
+lines of /root/reference/dataPrepScripts/PairWithNonVariants.py (Pair :33-128), plus --seed.
+
+    python -m clairvoyante_amd.PairWithNonVariants --tensor_can_fn CAN.gz --tensor_var_fn VAR.gz --bed_fn B.bed \
+           --output_fn MIX.gz --amp 2 [--seed N]
+
+All rows of --tensor_var_fn are written; a row of --tensor_can_fn is usable when the BED covers it (when there is one)
+and no truth row has its contig and position; of the usable ones the share r = min(1, amp * v / c) is written.  The
+reference picks them with Python's unseeded generator in file order (:119); here a row is kept when its keyed draw
+(clairvoyante_amd/draws.py, stream PAIR: a function of seed, contig and position alone) is below r, so the same seed
+gives the same file and the device route of utils_v2.GetTrainingSetFromBam, which is held to this loop, the same set.
+Deliberate deviation: with no usable non-variant (c == 0) r is 1, where the reference divides by zero (:88).
+"""
+import argparse
+import logging
+import shlex
+import subprocess
+import sys
+
+if __package__ in (None, ""):      # run as `python <dir>/PairWithNonVariants.py` (the reference's way): make the package importable
+    import os as _os, sys as _sys
+    _sys.path[0] = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
+    import clairvoyante_amd  # noqa: F401
+    __package__ = "clairvoyante_amd"
+from . import draws
+
+logging.basicConfig(format='%(message)s', level=logging.INFO)
+
+
+def _rows(fn):
+    f = subprocess.Popen(shlex.split("gzip -fdc %s" % fn), stdout=subprocess.PIPE, bufsize=8388608)
+    for row in f.stdout:
+        yield row.strip()
+    f.stdout.close()
+    f.wait()
+
+
+def _usable(args, tree, truth):
+    """(raw row, contig, position) of the rows of --tensor_can_fn the pairing may pick (:106-118)"""
+    for raw in _rows(args.tensor_can_fn):
+        row = raw.split()
+        if not row:
+            continue
+        ctg, pos = row[0].decode(), int(row[1])
+        if args.bed_fn is not None and (ctg not in tree or not tree[ctg].hit(pos)):
+            continue
+        if (ctg, pos) in truth:
+            continue
+        yield raw, ctg, pos
+
+
+def Pair(args):
+    from .utils_v2 import _Intervals
+    seed = draws.resolve_seed(getattr(args, "seed", None), "PairWithNonVariants")
+    tree = {}
+    if args.bed_fn is not None:
+        logging.info("Loading BED file ...")
+        for row in _rows(args.bed_fn):
+            row = row.split()
+            if not row:
+                continue
+            begin, end = int(row[1]), int(row[2]) - 1
+            if end == begin:
+                end += 1
+            tree.setdefault(row[0].decode(), _Intervals()).addi(begin, end)
+
+    logging.info("Counting the number of Truth Variants in %s ..." % args.tensor_var_fn)
+    v = 0
+    truth = set()
+    for row in _rows(args.tensor_var_fn):
+        row = row.split()
+        if not row:
+            continue
+        v += 1
+        truth.add((row[0].decode(), int(row[1])))
+    logging.info("%d Truth Variants" % v)
+    t = v * args.amp
+    logging.info("%d non-variants to be picked" % t)
+
+    logging.info("Counting the number of usable non-variants in %s ..." % args.tensor_can_fn)
+    c = sum(1 for _ in _usable(args, tree, truth))
+    logging.info("%d usable non-variant" % c)
+    r = float(t) / c if c else 1.0
+    r = r if r <= 1 else 1
+    logging.info("%.2f of all non-variants are selected" % r)
+
+    o1 = o2 = 0
+    fpo = open(args.output_fn, "wb")
+    fh = subprocess.Popen(shlex.split("gzip -c"), stdin=subprocess.PIPE, stdout=fpo, stderr=sys.stderr, bufsize=8388608)
+    for row in _rows(args.tensor_var_fn):
+        fh.stdin.write(row)
+        fh.stdin.write(b"\n")
+        o1 += 1
+    batch = []
+
+    def drain():
+        n = 0
+        by_ctg = {}
+        for k, (_raw, ctg, pos) in enumerate(batch):
+            by_ctg.setdefault(ctg, []).append(k)
+        keep = [False] * len(batch)
+        for ctg, ks in by_ctg.items():
+            u = draws.draws(seed, draws.PAIR, ctg, [batch[k][2] for k in ks])
+            for k, uk in zip(ks, u):
+                keep[k] = uk < r
+        for k, (raw, _ctg, _pos) in enumerate(batch):
+            if keep[k]:
+                fh.stdin.write(raw)
+                fh.stdin.write(b"\n")
+                n += 1
+        del batch[:]
+        return n
+
+    for item in _usable(args, tree, truth):
+        batch.append(item)
+        if len(batch) >= 65536:
+            o2 += drain()
+    o2 += drain()
+    fh.stdin.close()
+    fh.wait()
+    fpo.close()
+    logging.info("%.2f/%.2f Truth Variants/Non-variants outputed" % (o1, o2))
+    return {"v": v, "c": c, "r": r, "o1": o1, "o2": o2, "seed": seed}
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description="Pair the truth variants with non-variants")
+    parser.add_argument('--tensor_can_fn', type=str, default=None,
+                        help="Tensors generated at randome genome positions by ExtractVariantCandidates.py+CreateTensor.py")
+    parser.add_argument('--tensor_var_fn', type=str, default=None, help="Variant tensors generated by GetTruth.py+CreateTensor.py")
+    parser.add_argument('--bed_fn', type=str, default=None, help="Usable genome regions input in BED format")
+    parser.add_argument('--output_fn', type=str, default=None, help="Tensors output filename")
+    parser.add_argument('--amp', type=float, default=2,
+                        help="Pick ((# of the Truth Variants)*amp) non-variants to pair with the Truth Variants, default: 2")
+    parser.add_argument('--seed', type=int, default=None,
+                        help="Seed of the keyed draws (repeatable output); default: 64 bits taken from Python's generator once")
+    return parser
+
+
+def main():
+    parser = build_parser()
+    args = parser.parse_args()
+    if len(sys.argv[1:]) == 0:
+        parser.print_help()
+        sys.exit(1)
+    Pair(args)
+
+
+if __name__ == "__main__":
+    main()

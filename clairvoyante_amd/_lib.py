@@ -173,6 +173,20 @@ _SIGS = {
     "cv_pileup_recount": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "cv_pileup_get_candidates": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                 ctypes.POINTER(ctypes.c_int64)]),
+    # the labelled training set straight from the pileup (csrc/cv_bamtrain.hip)
+    "cv_draws_host": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_int64, ctypes.c_void_p]),
+    "cv_pileup_sample_candidates": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_double, ctypes.c_int,
+                                                   ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    "cv_pileup_adopt_union": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    "cv_bamtrain_columns": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
+    "cv_bamtrain_pair": (ctypes.c_int, [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_double, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "cv_bam_open": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     "cv_bam_close": (None, [ctypes.c_void_p]),
     "cv_bam_nref": (ctypes.c_int, [ctypes.c_void_p]),

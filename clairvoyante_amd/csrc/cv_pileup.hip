@@ -48,6 +48,7 @@
 #include <vector>
 
 #include "../../include/clairvoyante_amd.h"
+#include "cv_draw_core.hpp"
 
 void cv_set_error(const char *fmt, ...);
 
@@ -398,6 +399,10 @@ struct cv_pileup {
     int64_t evc_reads = 0;                 // processedReads (:150)
     std::vector<int64_t> sel_host;         // extracted entries: position << 1 | kind
     std::vector<int32_t> sel_counts;       // [n,7]
+    int64_t *sel_dev = nullptr;            // the same entries in HBM (cv_pileup_sample_candidates leaves them there)
+    int64_t nsel_dev = 0;
+    bool sel_host_stale = false;           // sel_host / sel_counts not yet fetched from sel_dev
+    uint8_t *cflag_dev = nullptr;          // [n] CV_CENTRE_* of the centres cv_pileup_adopt_union installed
     std::vector<hipEvent_t> ev;            // pairs, scatter launches not yet accumulated
     std::vector<hipEvent_t> evf;           // pairs, finalize launches
     std::vector<hipEvent_t> eve;           // pairs, candidate-pass launches
@@ -464,7 +469,7 @@ extern "C" void cv_pileup_destroy(cv_pileup *p)
     float sink = 0.f;
     drain(p->ev, sink); drain(p->evf, sink); drain(p->eve, sink);
     hipFree(p->ref_dev); hipFree(p->cand_dev); hipFree(p->bucket_dev); hipFree(p->cnt_dev);
-    hipFree(p->touched_dev); hipFree(p->pos_cnt);
+    hipFree(p->touched_dev); hipFree(p->pos_cnt); hipFree(p->sel_dev); hipFree(p->cflag_dev);
     free_batch(p->work);
     if (p->has_reserved && p->retain) free_batch(p->reserved);
     for (auto &b : p->kept) free_batch(b);
@@ -505,11 +510,11 @@ extern "C" int cv_pileup_set_reference(cv_pileup *p, const char *seq, int64_t le
     return 0;
 }
 
-static int install_candidates(cv_pileup *p, const std::vector<int32_t> &c32)
+// room for n centres: the centre list (to be filled by the caller), zeroed counters and "touched" marks
+static int install_alloc(cv_pileup *p, int64_t n)
 {
-    const int64_t n = (int64_t)c32.size();
-    hipFree(p->cand_dev); hipFree(p->bucket_dev); hipFree(p->cnt_dev); hipFree(p->touched_dev);
-    p->cand_dev = nullptr; p->bucket_dev = nullptr; p->cnt_dev = nullptr; p->touched_dev = nullptr;
+    hipFree(p->cand_dev); hipFree(p->bucket_dev); hipFree(p->cnt_dev); hipFree(p->touched_dev); hipFree(p->cflag_dev);
+    p->cand_dev = nullptr; p->bucket_dev = nullptr; p->cnt_dev = nullptr; p->touched_dev = nullptr; p->cflag_dev = nullptr;
     p->n = n;
     size_t n1 = (size_t)(n > 0 ? n : 1);
     PL_HIP(hipMalloc(&p->cand_dev, n1 * sizeof(int32_t)));
@@ -517,10 +522,16 @@ static int install_candidates(cv_pileup *p, const std::vector<int32_t> &c32)
     PL_HIP(hipMalloc(&p->touched_dev, n1));
     PL_HIP(hipMemset(p->cnt_dev, 0, n1 * WIDTH * NCNT * sizeof(int32_t)));
     PL_HIP(hipMemset(p->touched_dev, 0, n1));
+    return 0;
+}
+
+// the lookup table over the centres in cand_dev[0, n); first / last: the smallest and the largest of them
+static int install_buckets(cv_pileup *p, int32_t first, int32_t last)
+{
+    const int64_t n = p->n;
     if (n > 0) {
-        PL_HIP(hipMemcpy(p->cand_dev, c32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-        p->bucket_lo = c32[0] - (FLANK + 1);
-        p->nb = (((int64_t)c32[(size_t)n - 1] + FLANK + 2 - p->bucket_lo) >> BUCKET_SHIFT) + 1;
+        p->bucket_lo = first - (FLANK + 1);
+        p->nb = (((int64_t)last + FLANK + 2 - p->bucket_lo) >> BUCKET_SHIFT) + 1;
     } else {
         p->bucket_lo = 0; p->nb = 1;
     }
@@ -531,6 +542,14 @@ static int install_candidates(cv_pileup *p, const std::vector<int32_t> &c32)
     PL_HIP(hipGetLastError());
     PL_HIP(hipDeviceSynchronize());
     return 0;
+}
+
+static int install_candidates(cv_pileup *p, const std::vector<int32_t> &c32)
+{
+    const int64_t n = (int64_t)c32.size();
+    if (install_alloc(p, n)) return 1;
+    if (n > 0) PL_HIP(hipMemcpy(p->cand_dev, c32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    return install_buckets(p, n > 0 ? c32[0] : 0, n > 0 ? c32[(size_t)n - 1] : 0);
 }
 
 extern "C" int cv_pileup_set_candidates(cv_pileup *p, const int64_t *centers, int64_t n)
@@ -1074,19 +1093,16 @@ extern "C" int cv_pileup_add_bam_dev(cv_pileup *p, const void *segs_dev, int64_t
     return 0;
 }
 
-extern "C" int cv_pileup_extract_candidates(cv_pileup *p, double threshold, double min_coverage, int has_region,
-                                            int64_t ctg_start, int64_t ctg_end, const int64_t *bed_begin,
-                                            const int64_t *bed_end, int64_t nbed, void *stream, int64_t *n_out)
+// BED intervals: sorted, merged -> disjoint (membership is all the reference asks of its interval tree), in HBM
+struct bed_dev {
+    int64_t *bb = nullptr, *be = nullptr;
+    int n = -1;                                            // -1: no BED file
+    ~bed_dev() { hipFree(bb); hipFree(be); }
+};
+
+static int bed_upload(bed_dev &d, const int64_t *bed_begin, const int64_t *bed_end, int64_t nbed)
 {
-    if (!p || !n_out) { cv_set_error("cv_pileup_extract_candidates: null argument"); return 1; }
-    if (!p->evc) { cv_set_error("cv_pileup_extract_candidates: option 'evc' was not set"); return 1; }
-    if (cv_pileup_flush(p, stream)) return 1;
-    PL_HIP(hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    p->sel_host.clear(); p->sel_counts.clear();
-    *n_out = 0;
-    if (!p->pos_cnt || p->ref_len <= 0) return 0;         // no read reached the candidate pass
-    // BED intervals: sorted, merged -> disjoint (membership is all the reference asks of its interval tree)
+    if (nbed < 0) return 0;
     std::vector<std::pair<int64_t, int64_t>> iv;
     for (int64_t i = 0; i < nbed; ++i) if (bed_end[i] > bed_begin[i]) iv.emplace_back(bed_begin[i], bed_end[i]);
     std::sort(iv.begin(), iv.end());
@@ -1095,22 +1111,41 @@ extern "C" int cv_pileup_extract_candidates(cv_pileup *p, double threshold, doub
         if (!bb.empty() && x.first <= be.back()) be.back() = std::max(be.back(), x.second);
         else { bb.push_back(x.first); be.push_back(x.second); }
     }
-    int64_t *bb_dev = nullptr, *be_dev = nullptr;
-    if (nbed >= 0) {
-        const size_t nb1 = bb.size() ? bb.size() : 1;
-        PL_HIP(hipMalloc(&bb_dev, nb1 * sizeof(int64_t)));
-        PL_HIP(hipMalloc(&be_dev, nb1 * sizeof(int64_t)));
-        if (!bb.empty()) {
-            PL_HIP(hipMemcpy(bb_dev, bb.data(), bb.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-            PL_HIP(hipMemcpy(be_dev, be.data(), be.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        }
+    const size_t nb1 = bb.size() ? bb.size() : 1;
+    PL_HIP(hipMalloc(&d.bb, nb1 * sizeof(int64_t)));
+    PL_HIP(hipMalloc(&d.be, nb1 * sizeof(int64_t)));
+    if (!bb.empty()) {
+        PL_HIP(hipMemcpy(d.bb, bb.data(), bb.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        PL_HIP(hipMemcpy(d.be, be.data(), be.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     }
-    evc_pred pred{p->pos_cnt, p->ref_dev, p->ref_first, threshold, min_coverage, has_region, ctg_start, ctg_end,
-                  bb_dev, be_dev, nbed >= 0 ? (int)bb.size() : -1};
+    d.n = (int)bb.size();
+    return 0;
+}
+
+// the gen4Training sample (ExtractVariantCandidates.py:203-205) on top of the select: an entry the select keeps stays
+// unless its stream-0 draw (cv_draw_core.hpp) exceeds outputProb
+struct sample_pred {
+    evc_pred base;
+    uint64_t seed;
+    uint32_t h;
+    double prob;
+
+    __device__ bool operator()(const int64_t &j) const
+    {
+        if (!base(j)) return false;
+        return !(cv_draw(seed, CV_DRAW_SAMPLE, h, base.ref_first + (j >> 1) + 1, (int)(j & 1)) > prob);
+    }
+};
+
+// entries j = position << 1 | kind of the loaded window that pred keeps, ascending, into p->sel_dev / p->nsel_dev
+template <class Pred>
+static int select_entries(cv_pileup *p, const Pred &pred, hipStream_t st)
+{
+    hipFree(p->sel_dev); p->sel_dev = nullptr; p->nsel_dev = 0;
     const int64_t items = p->ref_len * 2;
-    int64_t *sel_dev = nullptr, *nsel_dev = nullptr;
-    PL_HIP(hipMalloc(&sel_dev, (size_t)items * sizeof(int64_t)));
-    PL_HIP(hipMalloc(&nsel_dev, sizeof(int64_t)));
+    int64_t *count_dev = nullptr;
+    PL_HIP(hipMalloc(&p->sel_dev, (size_t)items * sizeof(int64_t)));
+    PL_HIP(hipMalloc(&count_dev, sizeof(int64_t)));
     int64_t nsel = 0;
     void *tmp = nullptr;
     size_t tmp_bytes = 0;
@@ -1121,30 +1156,94 @@ extern "C" int cv_pileup_extract_candidates(cv_pileup *p, double threshold, doub
         const int cnt = (int)std::min<int64_t>(SLICE, items - off);
         hipcub::CountingInputIterator<int64_t> it(off);
         size_t need = 0;
-        PL_HIP(hipcub::DeviceSelect::If(nullptr, need, it, sel_dev + written, nsel_dev, cnt, pred, st));
+        PL_HIP(hipcub::DeviceSelect::If(nullptr, need, it, p->sel_dev + written, count_dev, cnt, pred, st));
         if (need > tmp_bytes) { hipFree(tmp); tmp = nullptr; PL_HIP(hipMalloc(&tmp, need)); tmp_bytes = need; }
         {
             timed t(p->eve, st);
-            PL_HIP(hipcub::DeviceSelect::If(tmp, need, it, sel_dev + written, nsel_dev, cnt, pred, st));
+            PL_HIP(hipcub::DeviceSelect::If(tmp, need, it, p->sel_dev + written, count_dev, cnt, pred, st));
         }
-        PL_HIP(hipMemcpyAsync(&nsel, nsel_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        PL_HIP(hipMemcpyAsync(&nsel, count_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
         PL_HIP(hipStreamSynchronize(st));
         written += nsel;
     }
+    hipFree(tmp); hipFree(count_dev);
+    // the select needed room for every entry of the window; what stays resident is the selected ones only
+    int64_t *fit = nullptr;
+    PL_HIP(hipMalloc(&fit, (size_t)(written > 0 ? written : 1) * sizeof(int64_t)));
+    if (written) PL_HIP(hipMemcpyAsync(fit, p->sel_dev, (size_t)written * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    PL_HIP(hipStreamSynchronize(st));
+    hipFree(p->sel_dev);
+    p->sel_dev = fit;
+    p->nsel_dev = written;
+    return 0;
+}
+
+// sel_host / sel_counts from sel_dev
+static int fetch_selected(cv_pileup *p, hipStream_t st)
+{
+    const int64_t written = p->nsel_dev;
     p->sel_host.resize((size_t)written);
     p->sel_counts.resize((size_t)written * 7);
     if (written) {
         int32_t *c7 = nullptr;
         PL_HIP(hipMalloc(&c7, (size_t)written * 7 * sizeof(int32_t)));
-        evc_gather<<<(unsigned)((written + 255) / 256), 256, 0, st>>>(sel_dev, written, p->pos_cnt, c7);
+        evc_gather<<<(unsigned)((written + 255) / 256), 256, 0, st>>>(p->sel_dev, written, p->pos_cnt, c7);
         PL_HIP(hipGetLastError());
-        PL_HIP(hipMemcpyAsync(p->sel_host.data(), sel_dev, (size_t)written * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        PL_HIP(hipMemcpyAsync(p->sel_host.data(), p->sel_dev, (size_t)written * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         PL_HIP(hipMemcpyAsync(p->sel_counts.data(), c7, (size_t)written * 7 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         PL_HIP(hipStreamSynchronize(st));
         hipFree(c7);
     }
-    hipFree(tmp); hipFree(sel_dev); hipFree(nsel_dev); hipFree(bb_dev); hipFree(be_dev);
-    *n_out = written;
+    p->sel_host_stale = false;
+    return 0;
+}
+
+extern "C" int cv_pileup_extract_candidates(cv_pileup *p, double threshold, double min_coverage, int has_region,
+                                            int64_t ctg_start, int64_t ctg_end, const int64_t *bed_begin,
+                                            const int64_t *bed_end, int64_t nbed, void *stream, int64_t *n_out)
+{
+    if (!p || !n_out) { cv_set_error("cv_pileup_extract_candidates: null argument"); return 1; }
+    if (!p->evc) { cv_set_error("cv_pileup_extract_candidates: option 'evc' was not set"); return 1; }
+    if (cv_pileup_flush(p, stream)) return 1;
+    PL_HIP(hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    p->sel_host.clear(); p->sel_counts.clear();
+    hipFree(p->sel_dev); p->sel_dev = nullptr; p->nsel_dev = 0; p->sel_host_stale = false;
+    *n_out = 0;
+    if (!p->pos_cnt || p->ref_len <= 0) return 0;         // no read reached the candidate pass
+    bed_dev bed;
+    if (bed_upload(bed, bed_begin, bed_end, nbed)) return 1;
+    evc_pred pred{p->pos_cnt, p->ref_dev, p->ref_first, threshold, min_coverage, has_region, ctg_start, ctg_end,
+                  bed.bb, bed.be, bed.n};
+    if (select_entries(p, pred, st) || fetch_selected(p, st)) return 1;
+    hipFree(p->sel_dev); p->sel_dev = nullptr;             // (this route works from the host copy)
+    *n_out = p->nsel_dev;
+    p->nsel_dev = 0;
+    return 0;
+}
+
+extern "C" int cv_pileup_sample_candidates(cv_pileup *p, uint64_t seed, double output_prob, int has_region,
+                                           int64_t ctg_start, int64_t ctg_end, const int64_t *bed_begin,
+                                           const int64_t *bed_end, int64_t nbed, void *stream, int64_t *n_out)
+{
+    if (!p || !n_out) { cv_set_error("cv_pileup_sample_candidates: null argument"); return 1; }
+    if (!p->evc) { cv_set_error("cv_pileup_sample_candidates: option 'evc' was not set"); return 1; }
+    if (p->contig.empty()) { cv_set_error("cv_pileup_sample_candidates: no contig set (the draws are keyed by its name)"); return 1; }
+    if (cv_pileup_flush(p, stream)) return 1;
+    PL_HIP(hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    p->sel_host.clear(); p->sel_counts.clear();
+    hipFree(p->sel_dev); p->sel_dev = nullptr; p->nsel_dev = 0; p->sel_host_stale = false;
+    *n_out = 0;
+    if (!p->pos_cnt || p->ref_len <= 0) return 0;
+    bed_dev bed;
+    if (bed_upload(bed, bed_begin, bed_end, nbed)) return 1;
+    // threshold 0, minCoverage 0 (--gen4Training, :252-254): every booked position inside the region and the BED
+    sample_pred pred{{p->pos_cnt, p->ref_dev, p->ref_first, 0.0, 0.0, has_region, ctg_start, ctg_end, bed.bb, bed.be, bed.n},
+                     seed, cv_fnv1a32((const uint8_t *)p->contig.data(), (int64_t)p->contig.size()), output_prob};
+    if (select_entries(p, pred, st)) return 1;
+    p->sel_host_stale = true;
+    *n_out = p->nsel_dev;
     return 0;
 }
 
@@ -1152,6 +1251,10 @@ extern "C" int cv_pileup_get_extracted(cv_pileup *p, int64_t *pos0, int32_t *lat
                                        int64_t info[2])
 {
     if (!p) { cv_set_error("cv_pileup_get_extracted: null handle"); return 1; }
+    if (p->sel_host_stale) {
+        PL_HIP(hipSetDevice(p->device));
+        if (fetch_selected(p, (hipStream_t)0)) return 1;
+    }
     for (size_t i = 0; i < p->sel_host.size(); ++i) {
         if (pos0) pos0[i] = p->ref_first + (p->sel_host[i] >> 1);
         if (late) late[i] = (int32_t)(p->sel_host[i] & 1);
@@ -1168,6 +1271,7 @@ extern "C" int cv_pileup_adopt_candidates(cv_pileup *p, int has_range, int64_t l
     if (!p->retain) { cv_set_error("cv_pileup_adopt_candidates: option 'retain' was not set"); return 1; }
     if (cv_pileup_flush(p, stream)) return 1;
     PL_HIP(hipSetDevice(p->device));
+    if (p->sel_host_stale && fetch_selected(p, (hipStream_t)stream)) return 1;
     std::vector<int32_t> c32;
     for (size_t i = 0; i < p->sel_host.size(); ++i) {
         const int64_t c = p->ref_first + (p->sel_host[i] >> 1) + 1;          // the row prints pos+1 (:38)
@@ -1179,6 +1283,141 @@ extern "C" int cv_pileup_adopt_candidates(cv_pileup *p, int has_range, int64_t l
     hipStream_t st = (hipStream_t)stream;
     for (const auto &b : p->kept) if (launch_scatter(p, b, st)) return 1;
     if (n_out) *n_out = (int64_t)c32.size();
+    return 0;
+}
+
+// ---- centres = sampled positions UNION truth positions, made on the device ----------------------------------------
+namespace {
+
+constexpr int32_t UNION_OUT = INT32_MAX;                  // key of a sampled entry outside [lo1, hi1]: sorts last
+
+__global__ void union_fill(const int64_t *__restrict__ sel, int64_t ns, int64_t ref_first, int has_range, int64_t lo1,
+                           int64_t hi1, const int64_t *__restrict__ truth, int64_t nt, int32_t *__restrict__ key,
+                           uint8_t *__restrict__ val)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < ns) {
+        const int64_t c = ref_first + (sel[t] >> 1) + 1;                       // the row prints pos+1 (:38)
+        key[t] = (has_range && (c < lo1 || c > hi1)) ? UNION_OUT : (int32_t)c;   // CreateTensor.py:60-61
+        val[t] = CV_CENTRE_SAMPLED;
+    } else if (t < ns + nt) {
+        key[t] = (int32_t)truth[t - ns];
+        val[t] = CV_CENTRE_TRUTH;
+    }
+}
+
+__global__ void union_heads(const int32_t *__restrict__ key, int64_t m, int32_t *__restrict__ head)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j <= m) head[j] = j < m && key[j] != UNION_OUT && (j == 0 || key[j] != key[j - 1]) ? 1 : 0;   // (slot m: the total)
+}
+
+// one centre per distinct key; its flags = OR over the (at most three: regular, late, truth) items that share it
+__global__ void union_write(const int32_t *__restrict__ key, const uint8_t *__restrict__ val, const int32_t *__restrict__ head,
+                            const int32_t *__restrict__ before, int64_t m, int32_t *__restrict__ cands,
+                            uint8_t *__restrict__ flags)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m || !head[j]) return;
+    int f = 0;
+    for (int64_t k = j; k < m && key[k] == key[j]; ++k) f |= val[k];
+    cands[before[j]] = key[j];
+    flags[before[j]] = (uint8_t)f;
+}
+
+struct dev_free {                  // frees its pointers when the function leaves
+    std::vector<void *> v;
+    ~dev_free() { for (void *q : v) hipFree(q); }
+    template <class T> hipError_t alloc(T **out, size_t bytes) { hipError_t e = hipMalloc(out, bytes ? bytes : 1); if (e == hipSuccess) v.push_back(*out); return e; }
+};
+
+}  // namespace
+
+extern "C" int cv_pileup_adopt_union(cv_pileup *p, int has_range, int64_t lo1, int64_t hi1, const int64_t *truth,
+                                     int64_t ntruth, void *stream, int64_t *n_out)
+{
+    if (!p || ntruth < 0 || (ntruth > 0 && !truth)) { cv_set_error("cv_pileup_adopt_union: bad argument"); return 1; }
+    if (!p->retain) { cv_set_error("cv_pileup_adopt_union: option 'retain' was not set"); return 1; }
+    for (int64_t i = 0; i < ntruth; ++i)
+        if (truth[i] < -(1LL << 30) || truth[i] > (1LL << 31) - 64 || (i && truth[i] <= truth[i - 1])) {
+            cv_set_error("cv_pileup_adopt_union: truth positions must be strictly ascending 1-based positions below 2^31 "
+                         "(index %lld: %lld)", (long long)i, (long long)truth[i]);
+            return 1;
+        }
+    if (cv_pileup_flush(p, stream)) return 1;
+    PL_HIP(hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t ns = p->sel_dev ? p->nsel_dev : 0, m = ns + ntruth;
+    if (m >= (1LL << 31) - 1) { cv_set_error("cv_pileup_adopt_union: %lld entries, more than one sort takes", (long long)m); return 1; }
+    int64_t n = 0;
+    int32_t ends[2] = {0, 0};
+    dev_free tmp;
+    int32_t *cands = nullptr;
+    uint8_t *flags = nullptr;
+    if (m > 0) {
+        int64_t *truth_dev = nullptr;
+        int32_t *key_in = nullptr, *key_out = nullptr, *head = nullptr, *before = nullptr;
+        uint8_t *val_in = nullptr, *val_out = nullptr;
+        void *ws = nullptr;
+        size_t a = 0, b = 0;
+        PL_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, a, (const int32_t *)nullptr, (int32_t *)nullptr, (const uint8_t *)nullptr,
+                                                  (uint8_t *)nullptr, (int)m, 0, 32, st));
+        PL_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t *)nullptr, (int32_t *)nullptr, (int)(m + 1), st));
+        const size_t ws_bytes = a > b ? a : b;
+        PL_HIP(tmp.alloc(&truth_dev, (size_t)ntruth * 8));
+        PL_HIP(tmp.alloc(&key_in, (size_t)m * 4)); PL_HIP(tmp.alloc(&key_out, (size_t)m * 4));
+        PL_HIP(tmp.alloc(&val_in, (size_t)m)); PL_HIP(tmp.alloc(&val_out, (size_t)m));
+        PL_HIP(tmp.alloc(&head, (size_t)(m + 1) * 4)); PL_HIP(tmp.alloc(&before, (size_t)(m + 1) * 4));
+        PL_HIP(tmp.alloc(&cands, (size_t)m * 4)); PL_HIP(tmp.alloc(&flags, (size_t)m));
+        PL_HIP(tmp.alloc(&ws, ws_bytes));
+        if (ntruth) PL_HIP(hipMemcpyAsync(truth_dev, truth, (size_t)ntruth * 8, hipMemcpyHostToDevice, st));
+        const unsigned grid = (unsigned)((m + 1 + 255) / 256);
+        {
+            timed t(p->eve, st);
+            union_fill<<<grid, 256, 0, st>>>(p->sel_dev, ns, p->ref_first, has_range, lo1, hi1, truth_dev, ntruth, key_in, val_in);
+            size_t wb = ws_bytes;
+            PL_HIP(hipcub::DeviceRadixSort::SortPairs(ws, wb, (const int32_t *)key_in, key_out, (const uint8_t *)val_in, val_out, (int)m,
+                                                      0, 32, st));
+            union_heads<<<grid, 256, 0, st>>>(key_out, m, head);
+            wb = ws_bytes;
+            PL_HIP(hipcub::DeviceScan::ExclusiveSum(ws, wb, (const int32_t *)head, before, (int)(m + 1), st));
+            union_write<<<grid, 256, 0, st>>>(key_out, val_out, head, before, m, cands, flags);
+        }
+        PL_HIP(hipGetLastError());
+        int32_t n32 = 0;
+        PL_HIP(hipMemcpyAsync(&n32, before + m, 4, hipMemcpyDeviceToHost, st));
+        PL_HIP(hipStreamSynchronize(st));                 // (also: `truth` may go after the call)
+        n = n32;
+        if (n > 0) {
+            PL_HIP(hipMemcpyAsync(&ends[0], cands, 4, hipMemcpyDeviceToHost, st));
+            PL_HIP(hipMemcpyAsync(&ends[1], cands + (n - 1), 4, hipMemcpyDeviceToHost, st));
+            PL_HIP(hipStreamSynchronize(st));
+        }
+    }
+    if (install_alloc(p, n)) return 1;
+    PL_HIP(hipMalloc(&p->cflag_dev, (size_t)(n > 0 ? n : 1)));
+    if (n > 0) {
+        PL_HIP(hipMemcpy(p->cand_dev, cands, (size_t)n * 4, hipMemcpyDeviceToDevice));
+        PL_HIP(hipMemcpy(p->cflag_dev, flags, (size_t)n, hipMemcpyDeviceToDevice));
+    }
+    if (install_buckets(p, ends[0], ends[1])) return 1;
+    for (const auto &b : p->kept) if (launch_scatter(p, b, st)) return 1;
+    if (n_out) *n_out = n;
+    return 0;
+}
+
+// what cv_bamtrain.hip reads of the handle (not part of the C ABI): the centres, their CV_CENTRE_* flags (null unless
+// cv_pileup_adopt_union made them) and the reference bytes, all in HBM and owned by the handle
+int cv_pileup_centres_dev(const cv_pileup *p, const int32_t **centres_dev, const uint8_t **flags_dev,
+                                     const uint8_t **ref_dev, int64_t *ref_first, int64_t *ref_len, int64_t *n)
+{
+    if (!p || !centres_dev || !flags_dev || !ref_dev || !ref_first || !ref_len || !n) {
+        cv_set_error("cv_pileup_centres_dev: null argument");
+        return 1;
+    }
+    if (!p->cand_dev || !p->ref_dev) { cv_set_error("cv_pileup_centres_dev: set the reference and the candidates first"); return 1; }
+    *centres_dev = p->cand_dev; *flags_dev = p->cflag_dev; *ref_dev = p->ref_dev;
+    *ref_first = p->ref_first; *ref_len = p->ref_len; *n = p->n;
     return 0;
 }
 

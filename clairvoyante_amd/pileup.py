@@ -73,6 +73,7 @@ class Pileup(object):
         self.centers = np.zeros(0, dtype=np.int64)
         self._tail = b""
         self.reads_kept = 0
+        self._nsel = 0                  # entries of the last sample_candidates()
 
     def close(self):
         if getattr(self, "_bam_dev", None):
@@ -223,13 +224,8 @@ class Pileup(object):
             self.h, float(threshold), float(minCoverage), int(region is not None), int(region[0]) if region else 0,
             int(region[1]) if region else 0, bb.ctypes.data_as(ctypes.c_void_p), be.ctypes.data_as(ctypes.c_void_p),
             nbed, self._stream(), ctypes.byref(n)))
-        k = n.value
-        pos0 = np.zeros(k, dtype=np.int64); late = np.zeros(k, dtype=np.int32); c7 = np.zeros((k, 7), dtype=np.int32)
-        info = (ctypes.c_int64 * 2)()
-        _lib.check(self.lib.cv_pileup_get_extracted(self.h, pos0.ctypes.data_as(ctypes.c_void_p),
-                                                    late.ctypes.data_as(ctypes.c_void_p),
-                                                    c7.ctypes.data_as(ctypes.c_void_p), info))
-        return {"pos0": pos0, "late": late, "counts": c7, "reads": info[0], "last_pos": info[1]}
+        self._nsel = n.value
+        return self.extracted()
 
     def adopt_candidates(self, lo1=None, hi1=None):
         """make the extracted positions (+1, optionally inside [lo1, hi1]) the candidate centres and scatter
@@ -242,6 +238,65 @@ class Pileup(object):
         _lib.check(self.lib.cv_pileup_get_candidates(self.h, self.centers.ctypes.data_as(ctypes.c_void_p), self.n,
                                                      ctypes.byref(n)))
         return self.centers
+
+    def _bed_arrays(self, bed):
+        if bed is None:
+            z = np.zeros(1, dtype=np.int64)
+            return z, z, -1
+        return (np.ascontiguousarray([b for b, _ in bed], dtype=np.int64),
+                np.ascontiguousarray([e for _, e in bed], dtype=np.int64), len(bed))
+
+    def sample_candidates(self, seed, outputProb, region=None, bed=None):
+        """ExtractVariantCandidates --gen4Training --seed on the device (needs evc=True and a contig): every position the
+        candidate pass booked, inside region / bed as extract_candidates tests them, kept unless its stream-0 draw exceeds
+        outputProb.  The entries stay in HBM -> their number; extracted() fetches them."""
+        if self._tail:
+            self.add_sam(b"", final=True)
+        n = ctypes.c_int64(0)
+        bb, be, nbed = self._bed_arrays(bed)
+        _lib.check(self.lib.cv_pileup_sample_candidates(
+            self.h, int(seed), float(outputProb), int(region is not None), int(region[0]) if region else 0,
+            int(region[1]) if region else 0, bb.ctypes.data_as(ctypes.c_void_p), be.ctypes.data_as(ctypes.c_void_p), nbed,
+            self._stream(), ctypes.byref(n)))
+        self._nsel = n.value
+        return n.value
+
+    def extracted(self):
+        """the entries of the last extract_candidates() / sample_candidates(): dict(pos0, late, counts [n,7] in
+        A,C,G,T,I,D,N order, reads, last_pos)"""
+        k = self._nsel
+        pos0 = np.zeros(k, dtype=np.int64); late = np.zeros(k, dtype=np.int32); c7 = np.zeros((k, 7), dtype=np.int32)
+        info = (ctypes.c_int64 * 2)()
+        _lib.check(self.lib.cv_pileup_get_extracted(self.h, pos0.ctypes.data_as(ctypes.c_void_p),
+                                                    late.ctypes.data_as(ctypes.c_void_p),
+                                                    c7.ctypes.data_as(ctypes.c_void_p), info))
+        return {"pos0": pos0, "late": late, "counts": c7, "reads": info[0], "last_pos": info[1]}
+
+    def adopt_union(self, truth, lo1=None, hi1=None):
+        """centres = sampled positions (+1, inside [lo1, hi1]) united with the ascending 1-based `truth` positions, made
+        and flagged on the device; the retained alignments are scattered for them (needs retain=True) -> their number"""
+        t = np.ascontiguousarray(truth, dtype=np.int64)
+        n = ctypes.c_int64(0)
+        _lib.check(self.lib.cv_pileup_adopt_union(self.h, int(lo1 is not None), int(lo1 or 0), int(hi1 or 0),
+                                                  t.ctypes.data_as(ctypes.c_void_p), len(t), self._stream(), ctypes.byref(n)))
+        self.n = n.value
+        self.centers = None                 # (they stay in HBM; cv_pileup_get_candidates fetches them)
+        return self.n
+
+    def columns(self, depth, touched, minCoverage=0):
+        """behind finish(): per centre the columns cv_trainset_finish sorts and labels by -> dict of device tensors
+        pos int64, digits / centre / acgt / cflag / row uint8 (csrc/cv_bamtrain.hip)"""
+        import torch
+        n = self.n
+        col = {"pos": torch.empty(n, dtype=torch.int64, device=self.device)}
+        for k in ("digits", "centre", "acgt", "cflag", "row"):
+            col[k] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        u8 = touched.to(torch.uint8)
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if n else None
+        _lib.check(self.lib.cv_bamtrain_columns(self.h, p(depth), p(u8), int(minCoverage), p(col["pos"]), p(col["digits"]),
+                                                p(col["centre"]), p(col["acgt"]), p(col["cflag"]), p(col["row"]),
+                                                self._stream()))
+        return col
 
     def stats(self):
         ms = (ctypes.c_float * 3)()

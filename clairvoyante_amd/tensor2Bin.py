@@ -3,6 +3,10 @@ blocks) of 500-item blosc chunks -- same command line and layout as
 /root/reference/clairvoyante/tensor2Bin.py (Convert :16-28).
 
     python -m clairvoyante_amd.tensor2Bin --tensor_fn T.gz --var_fn V.gz --bed_fn B.bed --bin_fn OUT.bin
+    python -m clairvoyante_amd.tensor2Bin --bam_fn A.bam,B.bam --ref_fn A.fa,B.fa --ctgName chr21,chr22 \
+           --ctgStart S1,S2 --ctgEnd E1,E2 --var_fn V.gz --bed_fn B.bed --seed N --bin_fn OUT.bin
+
+The second form (not in the reference) builds the set from the BAMs on the GPU, utils_v2.GetTrainingSetFromBam.
 """
 import argparse
 import logging
@@ -21,7 +25,13 @@ logging.basicConfig(format='%(message)s', level=logging.INFO)
 
 def Convert(args, utils):
     logging.info("Loading the dataset ...")
-    total, XC, YC, PC = utils.GetTrainingArray(args.tensor_fn, args.var_fn, args.bed_fn)
+    sources = utils.bam_sources(args) if hasattr(utils, "bam_sources") else None
+    if sources is not None:
+        total, XC, YC, PC = utils.GetTrainingSetFromBam(
+            sources, args.var_fn, args.bed_fn, amp=args.amp, candidates=args.candidates, genomeSize=args.genomeSize,
+            seed=args.seed, samtools=args.samtools, minMQ=args.minMQ, dcov=args.dcov).blocks()
+    else:
+        total, XC, YC, PC = utils.GetTrainingArray(args.tensor_fn, args.var_fn, args.bed_fn)
     logging.info("Writing to binary ...")
     with open(args.bin_fn, "wb") as fh:
         for obj in (total, XC, YC, PC):
@@ -36,7 +46,7 @@ def Run(args):
     Convert(args, utils)
 
 
-def main():
+def build_parser():
     parser = argparse.ArgumentParser(description="Generate a binary format input tensor")
     for flag, default, text in (("--tensor_fn", "vartensors", "Tensor input"), ("--var_fn", "truthvars", "Truth variants list input"),
                                 ("--bed_fn", None, "High confident genome regions input in the BED format"),
@@ -47,7 +57,20 @@ def main():
     parser.add_argument("--blosc_blocksize", type=int, default=None,
                         help="Write c-blosc's multi-block layout with blocks of this many bytes (e.g. 65536: many short "
                              "streams per chunk, what the device decoder likes); default: one stream per chunk")
+    from .utils_v2 import BAM_FLAGS
+    for flag, typ, default, text in BAM_FLAGS:
+        parser.add_argument(flag, type=typ, default=default, help=text)
+    return parser
+
+
+def main():
+    parser = build_parser()
     args = parser.parse_args()
+    from .utils_v2 import bam_sources
+    try:
+        bam_sources(args)
+    except ValueError as e:
+        parser.error(str(e))
     if not sys.argv[1:]:
         parser.print_help()
         sys.exit(1)

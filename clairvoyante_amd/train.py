@@ -292,7 +292,8 @@ class _Job(Thread):
 
 
 def load_dataset(args, utils, m=None):
-    """(total, XC, YC, posC) from --bin_fn or from --tensor_fn/--var_fn/--bed_fn (train.py:39-49).
+    """(total, XC, YC, posC) from --bin_fn or from --tensor_fn/--var_fn/--bed_fn (train.py:39-49), or -- with --bam_fn --
+    from the BAMs through utils.GetTrainingSetFromBam (resident with one rank and a real model, packed otherwise).
     With one rank, a real model `m` (it takes batches that lie in HBM) and a tensor file whose training set is built on
     the device (utils.trains_on_device), the set stays there: XC / YC are stand-ins for the block lists which
     DecompressArray hands out slices of (posC is None: training does not read it)."""
@@ -303,6 +304,15 @@ def load_dataset(args, utils, m=None):
             except TypeError:                                    # a foreign utils module with the plain signature
                 return utils.LoadBin(args.bin_fn)
         return _load_bin(args.bin_fn)
+    sources = utils.bam_sources(args) if hasattr(utils, "bam_sources") else None
+    if sources is not None:
+        from . import parallel
+        ts = utils.GetTrainingSetFromBam(
+            sources, args.var_fn, args.bed_fn, amp=args.amp, candidates=args.candidates, genomeSize=args.genomeSize,
+            seed=args.seed, device=getattr(m, "device", None), samtools=args.samtools, minMQ=args.minMQ, dcov=args.dcov)
+        if m is not None and getattr(m, "accepts_device_batches", False) and parallel.world()[1] == 1:
+            return ts.resident() + (None,)
+        return ts.blocks()
     if m is not None and getattr(m, "accepts_device_batches", False) and hasattr(utils, "GetTrainingSetDevice") \
             and utils.trains_on_device(args.tensor_fn):
         from . import parallel
@@ -565,14 +575,29 @@ _SWITCHES = (("--v3", True, "Use Clairvoyante version 3"), ("--v2", False, "Use 
              ("--slim", False, "Train using the slim version of Clairvoyante, optional"))
 
 
-def build_parser(description, cli=_CLI, switches=_SWITCHES):
+def build_parser(description, cli=_CLI, switches=_SWITCHES, bam=False):
     parser = argparse.ArgumentParser(description=description)
     for spec in cli:
         flag, typ, default, text = spec[:4]
         parser.add_argument(flag, type=typ, default=default, help=text, **(spec[4] if len(spec) > 4 else {}))
     for flag, default, text in switches:
         parser.add_argument(flag, type=param.str2bool, nargs='?', const=True, default=default, help=text)
+    if bam:                                                    # the training set straight from BAMs (utils_v2.BAM_FLAGS)
+        from .utils_v2 import BAM_FLAGS
+        for flag, typ, default, text in BAM_FLAGS:
+            parser.add_argument(flag, type=typ, default=default, help=text)
     return parser
+
+
+def parse_args(parser):
+    """parse_args() + the checks of the --bam_fn family (lists of equal length, not together with --tensor_fn)"""
+    args = parser.parse_args()
+    from .utils_v2 import bam_sources
+    try:
+        bam_sources(args)
+    except ValueError as e:
+        parser.error(str(e))
+    return args
 
 
 def pick_model(args):
@@ -587,8 +612,8 @@ def pick_model(args):
 
 
 def main():
-    parser = build_parser("Train Clairvoyante")
-    args = parser.parse_args()
+    parser = build_parser("Train Clairvoyante", bam=True)
+    args = parse_args(parser)
     if not sys.argv[1:]:
         parser.print_help()
         sys.exit(1)

@@ -26,7 +26,7 @@ if __package__ in (None, ""):      # run as `python <dir>/trainNonstop.py` (the 
     import clairvoyante_amd  # noqa: F401
     __package__ = "clairvoyante_amd"
 from . import param
-from .train import _BatchStream, _Job, build_parser, load_dataset, pick_model, run_epoch
+from .train import _BatchStream, _Job, build_parser, load_dataset, parse_args, pick_model, run_epoch
 
 logging.basicConfig(format='%(message)s', level=logging.INFO)
 
@@ -106,8 +106,8 @@ def TrainAll(args, m, utils, validate=True):
 
 
 def main(validate=True):
-    parser = build_parser("Train Clairvoyante Nonstop")
-    args = parser.parse_args()
+    parser = build_parser("Train Clairvoyante Nonstop", bam=True)
+    args = parse_args(parser)
     if not sys.argv[1:]:
         parser.print_help()
         sys.exit(1)

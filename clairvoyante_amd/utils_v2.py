@@ -10,6 +10,7 @@ import ctypes
 import gc
 import gzip
 import io
+import logging
 import os
 import pickle
 import random
@@ -1717,9 +1718,10 @@ def _gz_lines(fn):
     f.wait()
 
 
-def _read_bed_truth(var_fn, bed_fn):
+def _read_bed_truth(var_fn, bed_fn, every=None):
     """The BED and truth files as utils_v2.py:62-119 reads them -> (tree: contig -> _Intervals, Y: "ctg:pos" -> label of
-    the truth rows the BED keeps; the last row of a key wins).  A truth contig the BED file lacks raises KeyError, as there."""
+    the truth rows the BED keeps; the last row of a key wins).  A truth contig the BED file lacks raises KeyError, as there.
+    every: a dict that receives contig -> set of the positions of ALL truth rows, kept by the BED or not."""
     tree = {}
     if bed_fn is not None:
         for row in _gz_lines(bed_fn):
@@ -1738,6 +1740,8 @@ def _read_bed_truth(var_fn, bed_fn):
             if not row:
                 continue
             ctg = row[0]; pos = int(row[1])
+            if every is not None:
+                every.setdefault(ctg, set()).add(pos)
             if bed_fn is not None and not tree[ctg].hit(pos):
                 continue
             Y[ctg + ":" + str(pos)] = _label(row)
@@ -2189,6 +2193,220 @@ def GetTrainingSetDevice(tensor_fn, var_fn, bed_fn, shuffle=True, device=None, n
             batches.close()
     blocks = _training_array_host(tensor_fn, var_fn, bed_fn, shuffle)
     return TrainingSet(blocks[0], None, None, "host", reason=reason, blocks=blocks)
+
+
+# ---- the labelled training set straight from BAM files (csrc/cv_bamtrain.hip, csrc/cv_pileup.hip) -----------------------
+class _BamTrainsetBuilder(_TrainsetBuilder):
+    """_TrainsetBuilder whose rows come from the pileup, with their columns, instead of from parsed text: per source one
+    run of one contig; before the finish pass the pairing with non-variants over the rows of all sources"""
+
+    _COLS = _TrainsetBuilder._COLS + (("acgt", "uint8"), ("cflag", "uint8"))
+
+    def add_source(self, name, x, col):
+        """the c rows CreateTensor would print for one source (ascending position): x [c,33,4,4], col: their columns"""
+        torch, lib = self.torch, self.lib
+        c = int(x.shape[0])
+        if name not in self.ids:
+            if not contig_token_ok(name):
+                raise _lib.CvError("GetTrainingSetFromBam: contig name %r holds ':', NUL or a byte >= 0x80" % (name,))
+            if len(self.names) >= TRAINSET_MAX_CONTIGS:
+                raise _lib.CvError("GetTrainingSetFromBam: more than %d contigs" % TRAINSET_MAX_CONTIGS)
+            self.ids[name] = len(self.names)
+            self.names.append(name)
+        if c == 0:
+            return
+        if self.n + c > self.cap:
+            self._grow(max(2 * self.cap, self.n + c))
+        lo, hi = self.n, self.n + c
+        with torch.cuda.device(self.device):
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self.x[lo:hi].copy_(x.reshape(c, _NV))
+            for k in ("pos", "digits", "centre", "acgt", "cflag"):
+                self.cols[k][lo:hi].copy_(col[k])
+            mine = {k: v[lo:hi] for k, v in self.cols.items()}
+            run = torch.zeros(c, dtype=torch.int32, device=self.device)
+            run_ctg = torch.tensor([self.ids[name]], dtype=torch.int32, device=self.device)
+            t = self.tab
+            _lib.check(lib.cv_trainset_join(c, self._p(run), self._p(run_ctg), 1, self._p(mine["pos"]), self.ntab,
+                                            1 if self.has_bed else 0, self._p(t["bed_off"]), self._p(t["bed_begin"]), self._p(t["bed_emax"]),
+                                            self._p(t["truth_off"]) if t["truth_pos"].numel() else None, self._p(t["truth_pos"]),
+                                            self._p(mine["ctg"]), self._p(mine["keep"]), self._p(mine["truth"]), st))
+        self.n = hi
+
+    def pair(self, seed, amp):
+        """PairWithNonVariants over all rows: keep <- the final verdict -> dict(v, c, r, picked, kept); pair_ms: the event
+        time of the two launches"""
+        from . import draws
+        torch, lib, n = self.torch, self.lib, self.n
+        with torch.cuda.device(self.device):
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            h = np.array([draws.fnv1a32(nm) for nm in self.names] or [0], dtype=np.uint32).view(np.int32)
+            h_dev = torch.from_numpy(h).to(self.device)
+            counts = torch.zeros(4, dtype=torch.int64, device=self.device)
+            r = torch.zeros(1, dtype=torch.float64, device=self.device)
+            c = self.cols
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            _lib.check(lib.cv_bamtrain_pair(n, self._p(c["ctg"][:n]), self._p(c["pos"][:n]), self._p(c["cflag"][:n]),
+                                            self._p(c["acgt"][:n]), self._p(h_dev), max(len(self.names), 1), int(seed), float(amp),
+                                            self._p(c["keep"][:n]), self._p(counts), self._p(r), st))
+            ev[1].record()
+            v, cc, picked, kept = counts.cpu().tolist()
+            self.pair_ms = ev[0].elapsed_time(ev[1])
+            return {"v": v, "c": cc, "r": float(r.item()), "picked": picked, "kept": kept}
+
+
+def _split_list(value, n=None, typ=str):
+    """a comma-separated command-line list; an empty item is None"""
+    items = [None if v == "" else typ(v) for v in str(value).split(",")]
+    if n is not None and len(items) != n:
+        raise ValueError("expected %d comma-separated items, got %d in %r" % (n, len(items), value))
+    return items
+
+
+BAM_FLAGS = (   # flag, type, default, help: what tensor2Bin and train.py add for GetTrainingSetFromBam
+    ("--bam_fn", str, None, "Sorted BAM inputs, comma-separated, one per source: build the training set from them on the GPU "
+                            "(--tensor_fn must be left at its default)"),
+    ("--ref_fn", str, None, "Reference FASTA inputs, one per source"),
+    ("--ctgName", str, None, "Contig names, one per source"),
+    ("--ctgStart", str, None, "1-based starting positions, one per source; an empty item means no bound"),
+    ("--ctgEnd", str, None, "Inclusive ending positions, one per source; an empty item means no bound"),
+    ("--amp", float, 2, "Pick ((# of the Truth Variants)*amp) non-variants to pair with the Truth Variants, default: %(default)s"),
+    ("--candidates", int, 7000000, "Number of sampled positions over the genome, default: %(default)s"),
+    ("--genomeSize", int, 3000000000, "default: %(default)s"),
+    ("--seed", int, None, "Seed of the keyed draws; default: 64 bits taken from Python's generator once"),
+    ("--samtools", str, "samtools", "Path to the 'samtools', or 'native', default: %(default)s"),
+    ("--minMQ", int, 0, "Minimum Mapping Quality, default: %(default)d"),
+    ("--dcov", int, 250, "Cap depth per position at %(default)d"),
+)
+
+
+def bam_sources(args, tensor_default="vartensors"):
+    """the `sources` of GetTrainingSetFromBam from the --bam_fn family of flags, or None when --bam_fn is absent;
+    ValueError for lists of unequal length and for --bam_fn together with --tensor_fn"""
+    if getattr(args, "bam_fn", None) is None:
+        return None
+    if getattr(args, "tensor_fn", tensor_default) != tensor_default:
+        raise ValueError("--bam_fn and --tensor_fn are both given: the set is built from one or the other")
+    bams = _split_list(args.bam_fn)
+    n = len(bams)
+    cols = [bams]
+    for flag, typ in (("ref_fn", str), ("ctgName", str), ("ctgStart", int), ("ctgEnd", int)):
+        v = getattr(args, flag, None)
+        if v is None:
+            if flag in ("ref_fn", "ctgName"):
+                raise ValueError("--bam_fn needs --%s" % flag)
+            cols.append([None] * n)
+        else:
+            try:
+                cols.append(_split_list(v, n, typ))
+            except ValueError as e:
+                raise ValueError("--%s: %s" % (flag, e))
+    if any(v is None for v in cols[0] + cols[1] + cols[2]):
+        raise ValueError("--bam_fn, --ref_fn and --ctgName take no empty items")
+    return list(zip(*cols))
+
+
+def _fai_length(ref_fn, ctg):
+    try:
+        with open(ref_fn + ".fai") as fh:
+            for row in fh:
+                f = row.split("\t")
+                if f[0] == ctg:
+                    return int(f[1])
+    except (OSError, ValueError, IndexError):
+        pass
+    return None
+
+
+def GetTrainingSetFromBam(sources, var_fn, bed_fn, amp=2, candidates=7000000, genomeSize=3000000000, seed=None, shuffle=True,
+                          device=None, samtools="samtools", minMQ=0, dcov=250, considerleftedge=True):
+    """From (BAM, reference, truth list, BED) to the labelled, shuffled training set in HBM -> TrainingSet (route "device";
+    .pairing = dict(v, c, r, picked, kept)), without text tensors in between.  `sources`: (bam_fn, ref_fn, ctgName, ctgStart,
+    ctgEnd) each.  The result is the one the file recipe gives with the same seed: ExtractVariantCandidates
+    --gen4Training --seed, CreateTensor over the truth rows of var_fn inside [ctgStart+1, ctgEnd] and over the sampled
+    positions, the files of all sources concatenated, PairWithNonVariants --seed, GetTrainingArray.  Per source one Pileup
+    reads the BAM once (samtools pipe, or --samtools native on either BAM route): the candidate pass books every position,
+    cv_pileup_sample_candidates keeps the sampled ones by keyed draws, cv_pileup_adopt_union makes the centres (sampled
+    UNION truth) and scatters the retained alignments, cv_bamtrain_columns gives the columns; over all rows
+    cv_bamtrain_pair pairs, then cv_trainset_finish / _gather as for the text route.  Deliberate deviation from
+    PairWithNonVariants.py:88: with no usable non-variant (c == 0) r is 1, where the reference divides by zero.
+    There is no host builder behind this route (the pileup has none): without a GPU, or when twice the estimated set
+    would not fit into half of the free device memory, it raises CvError."""
+    import argparse
+    import time
+    from . import draws
+    from .CreateTensor import load_reference, region_of
+    from .ExtractVariantCandidates import stream_alignments
+    from .pileup import Pileup
+    if not _gpu_present():
+        raise _lib.CvError("GetTrainingSetFromBam needs an MI355X (no GPU visible); there is no CPU fallback")
+    import torch
+    device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+    seed = draws.resolve_seed(seed, "GetTrainingSetFromBam")
+    outputProb = (candidates * 2.) / genomeSize                      # ExtractVariantCandidates.py:254
+    t0 = time.time()
+    truth_all = {}                                                   # contig -> every truth position (not BED-filtered)
+    tree, Y = _read_bed_truth(var_fn, bed_fn, truth_all)
+    names, tables = _trainset_tables(tree, Y, bed_fn is not None)
+    plan, estimate = [], 0
+    for bam_fn, ref_fn, ctg, cs0, ce0 in sources:
+        a = argparse.Namespace(bam_fn=bam_fn, ref_fn=ref_fn, ctgName=ctg, ctgStart=cs0, ctgEnd=ce0, samtools=samtools)
+        cs, ce, rs, re_ = region_of(a)
+        truth = sorted(p for p in truth_all.get(ctg, ()) if cs is None or cs <= p <= ce)
+        span = (ce - cs + 1) if cs is not None else (_fai_length(ref_fn, ctg) or 0)
+        estimate += len(truth) + int(span * min(outputProb, 1.0)) + 1
+        plan.append((a, cs, ce, rs, re_, truth))
+    free = TRAINSET_FREE_BYTES
+    if free is None:
+        with torch.cuda.device(device):
+            free = torch.cuda.mem_get_info()[0]
+    if estimate * _ROW_BYTES * 2 > free // 2:
+        raise _lib.CvError("GetTrainingSetFromBam: the set would not fit into half of the free device memory: about %d rows, "
+                           "%d bytes twice over (the rows in arrival order and the set), against %d bytes free"
+                           % (estimate, estimate * _ROW_BYTES * 2, free))
+    t_tables = time.time() - t0
+    b = _BamTrainsetBuilder(device, names, tables, bed_fn is not None, estimate)
+    times = dict.fromkeys(("read", "sample", "scatter+finish", "columns"), 0.0)
+    sampled = 0
+    for a, cs, ce, rs, re_, truth in plan:
+        t0 = time.time()
+        ref_seq = load_reference(a, rs, re_)
+        pl = Pileup(device=device.index, minMQ=minMQ, dcov=dcov, considerleftedge=considerleftedge, evc=True, retain=True,
+                    evc_minMQ=minMQ, contig=a.ctgName)
+        try:
+            pl.set_reference(ref_seq, 0 if rs is None else rs - 1)
+            stream_alignments(a, pl, cs, ce)
+            t1 = time.time()
+            sampled += pl.sample_candidates(seed, outputProb, (cs, ce) if cs is not None else None, None)
+            t2 = time.time()
+            pl.adopt_union(truth, cs, ce)
+            x, depth, touched = pl.finish(subtract=True)
+            t3 = time.time()
+            col = pl.columns(depth, touched, 0)
+            idx = torch.nonzero(col["row"]).squeeze(1)
+            b.add_source(a.ctgName.encode("utf-8"), x.index_select(0, idx), {k: v.index_select(0, idx) for k, v in col.items()})
+            torch.cuda.current_stream(device).synchronize()
+            t4 = time.time()
+        finally:
+            pl.close()
+        for k, d in (("read", t1 - t0), ("sample", t2 - t1), ("scatter+finish", t3 - t2), ("columns", t4 - t3)):
+            times[k] += d
+    t0 = time.time()
+    pairing = b.pair(seed, amp)
+    pairing["sampled"] = sampled
+    t_pair = time.time() - t0
+    logging.info("%d Truth Variants" % pairing["v"])
+    logging.info("%d usable non-variant" % pairing["c"])
+    logging.info("%.2f of all non-variants are selected" % pairing["r"])
+    logging.info("%.2f/%.2f Truth Variants/Non-variants outputed" % (pairing["v"], pairing["picked"]))
+    t0 = time.time()
+    total, X, Yd, key_ctg, key_pos, t_shuffle = b.finish(shuffle)
+    ts = TrainingSet(total, X, Yd, "device", names=b.names, key_ctg=key_ctg, key_pos=key_pos)
+    ts.pairing, ts.seed = pairing, seed
+    times.update({"tables": t_tables, "pair": t_pair, "pair_kernels_ms": b.pair_ms, "finish+gather": time.time() - t0 - t_shuffle, "shuffle": t_shuffle})
+    ts.times.update(times)
+    return ts
 
 
 def GetTrainingArray(tensor_fn, var_fn, bed_fn, shuffle=True):

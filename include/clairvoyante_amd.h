@@ -596,6 +596,52 @@ int cv_pileup_recount(cv_pileup *p, void *stream);
 /* Current candidate centres (1-based); centers may be NULL to query the count.                  */
 int cv_pileup_get_candidates(cv_pileup *p, int64_t *centers, int64_t cap, int64_t *n_out);
 
+/* ---- the labelled training set straight from the pileup (csrc/cv_bamtrain.hip, csrc/cv_draw_core.hpp) ----------
+ * Replaces the middle of dataPrepScripts/PrepDataBeforeDemo.sh -- ExtractVariantCandidates.py --gen4Training, the two
+ * CreateTensor.py runs and PairWithNonVariants.py -- for utils_v2.GetTrainingSetFromBam; what follows them is the
+ * cv_trainset_* block above.  The reference draws from Python's unseeded generator in file order; here a draw is
+ * Philox4x32-10 keyed by what is drawn: key = the halves of `seed`, counter = (pos lo32, pos hi32, stream | late << 8,
+ * h), pos the 1-based coordinate, h = FNV-1a-32 of the contig name, stream CV_DRAW_SAMPLE (0) or CV_DRAW_PAIR (1);
+ * u = ((x0 << 32 | x1) >> 11) * 2^-53.
+ *
+ * cv_draws_host (host, no GPU): out_u[i] = that draw for (pos[i], late[i]); late may be NULL (all 0).
+ *
+ * cv_pileup_sample_candidates: cv_pileup_extract_candidates with threshold 0 and min_coverage 0 (every position the
+ *   "evc" pass booked, inside the region and the BED; a late second entry is its own entry) of which an entry stays
+ *   unless its stream-0 draw u > output_prob (:203).  Needs cv_pileup_set_contig (the name keys the draws).  The entries
+ *   stay in HBM, only *n_out comes back; cv_pileup_get_extracted fetches them when asked.
+ * cv_pileup_adopt_union (needs "retain"): centres = the sorted, unique union of the sampled positions (+1, inside
+ *   [lo1, hi1] when has_range) and truth[ntruth] (host, strictly ascending 1-based positions: the truth rows of the
+ *   contig the caller found inside the range, CreateTensor.py:59-61), with CV_CENTRE_TRUTH / CV_CENTRE_SAMPLED per
+ *   centre; then the scatter over the retained alignments as cv_pileup_adopt_candidates runs it.
+ * cv_bamtrain_columns, behind cv_pileup_finish(depth_dev, touched_dev), per centre i < n:
+ *   row_dev[i]     CreateTensor.py prints a row (:50-51): touched, the window starts inside the loaded reference,
+ *                  depth >= min_coverage
+ *   pos_dev[i] int64, digits_dev[i]  the centre and its decimal length (0 for a centre <= 0)
+ *   centre_dev[i]  the upper-cased reference base at the centre -> 0..3 (255: none of A, C, G, T), acgt_dev[i] = it is one
+ *   flags_dev[i]   the centre's CV_CENTRE_* flags
+ * cv_bamtrain_pair, once over the nrows rows of ALL sources (PairWithNonVariants.py pairs the concatenated files):
+ *   keep_dev[r] holds the BED verdict of cv_trainset_join on entry.  v = rows with CV_CENTRE_TRUTH (not BED-filtered,
+ *   :50-62), c = the other rows the BED keeps (:68-86), r = min(1, amp * v / c) in double, r = 1 when c == 0 (the
+ *   reference divides by zero); keep_dev[r] = truth ? BED verdict : (BED verdict and stream-1 draw of (ctg_hash_dev[
+ *   ctg_dev[r]], pos_dev[r]) < r), AND acgt_dev[r] -- a row whose centre is not ACGT is dropped only by the reader
+ *   behind the pairing, so it still counts in c.  counts_dev[4] = v, c, non-variants picked (before acgt), rows kept;
+ *   *r_dev = r: all the host fetches.                                                                              */
+#define CV_CENTRE_TRUTH 1
+#define CV_CENTRE_SAMPLED 2
+int cv_draws_host(uint64_t seed, int stream, uint32_t h, const int64_t *pos, const int32_t *late, int64_t n, double *out_u);
+int cv_pileup_sample_candidates(cv_pileup *p, uint64_t seed, double output_prob, int has_region, int64_t ctg_start,
+                                int64_t ctg_end, const int64_t *bed_begin, const int64_t *bed_end, int64_t nbed,
+                                void *stream, int64_t *n_out);
+int cv_pileup_adopt_union(cv_pileup *p, int has_range, int64_t lo1, int64_t hi1, const int64_t *truth, int64_t ntruth,
+                          void *stream, int64_t *n_out);
+int cv_bamtrain_columns(const cv_pileup *p, const int32_t *depth_dev, const uint8_t *touched_dev, int64_t min_coverage,
+                        int64_t *pos_dev, uint8_t *digits_dev, uint8_t *centre_dev, uint8_t *acgt_dev, uint8_t *flags_dev,
+                        uint8_t *row_dev, void *stream);
+int cv_bamtrain_pair(int64_t nrows, const int32_t *ctg_dev, const int64_t *pos_dev, const uint8_t *flags_dev,
+                     const uint8_t *acgt_dev, const uint32_t *ctg_hash_dev, int32_t nctg, uint64_t seed, double amp,
+                     uint8_t *keep_dev, int64_t *counts_dev, double *r_dev, void *stream);
+
 /* One text row of CreateTensor.py (:52): "<ctg> <center> <seq33> " + 528 x "%0.1f" (no newline).
  * counts: [33,4,4] fp32 raw counts (host).  Returns the length written, or -1 if cap is small.  */
 int64_t cv_format_tensor_row(const char *ctg, int64_t center, const char *seq, int64_t seqlen,
