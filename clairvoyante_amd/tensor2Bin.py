@@ -43,6 +43,8 @@ def Run(args):
     utils.SetupEnv()
     if getattr(args, "blosc_blocksize", None):
         utils.PACK_BLOCKSIZE = int(args.blosc_blocksize)
+    if getattr(args, "pack", None):
+        utils.PACK_ROUTE = args.pack
     Convert(args, utils)
 
 
@@ -57,6 +59,10 @@ def build_parser():
     parser.add_argument("--blosc_blocksize", type=int, default=None,
                         help="Write c-blosc's multi-block layout with blocks of this many bytes (e.g. 65536: many short "
                              "streams per chunk, what the device decoder likes); default: one stream per chunk")
+    parser.add_argument("--pack", type=str, default=None, choices=("host", "device"),
+                        help="Where the X blocks of a set built on the GPU are compressed: host (the default; the file is "
+                             "byte for byte what it has always been) or device (only the compressed form crosses to the host; "
+                             "c-blosc's multi-block layout, blocks of 65536 bytes unless --blosc_blocksize names another)")
     from .utils_v2 import BAM_FLAGS
     for flag, typ, default, text in BAM_FLAGS:
         parser.add_argument(flag, type=typ, default=default, help=text)

@@ -2005,6 +2005,19 @@ class TrainingSet(object):
         def block(a, s):
             return pack_array(np.ascontiguousarray(a[s:s + bs])) if s < len(a) else pack_array(empty)
 
+        if bin_pack_route() == "device" and getattr(self._X, "is_cuda", False):
+            # X is packed where it lies and only its compressed form crosses (pack_blocks_device); Y, the keys and the
+            # trailing empty block stay the host's, packed by the pool meanwhile
+            with ThreadPoolExecutor(min(self.PACK_THREADS, _lib.usable_cores())) as pool:
+                yj = [pool.submit(block, Y, b * bs) for b in range(nfull + 1)]
+                pj = [pool.submit(lambda b: pack_array(np.array(keys[b * bs:(b + 1) * bs])), b) for b in range(nfull + 1)]
+                XC = pack_blocks_device(self._X, PACK_BLOCKSIZE)
+                if total % bs == 0:
+                    XC.append(pack_array(empty))
+                YC, PC = [j.result() for j in yj], [j.result() for j in pj]
+            self.times["pack"] = time.time() - t0
+            self._blocks = (total, XC, YC, PC)
+            return self._blocks
         step = max(self.STAGE_ITEMS // bs, 1) * bs
         XC = []
         with ThreadPoolExecutor(min(self.PACK_THREADS, _lib.usable_cores())) as pool:
@@ -2781,3 +2794,148 @@ def resident_from_blocks(total, XC, YC, device=None):
         if pending is not None:
             pending[0].synchronize()
     return ResidentBlocks(X), ResidentBlocks(Y)
+
+
+# ---- the X blocks packed on the device (csrc/cv_blosc_pack_dev.hip) ----------------------
+bin_pack_chunk_counts = {"device": 0, "host": 0}
+PACK_ROUTE = None                 # tensor2Bin --pack: "host" / "device"; None = the CV_BIN_PACK environment variable decides
+DEVICE_PACK_BLOCKSIZE = 65536     # the device route's blocksize when tensor2Bin --blosc_blocksize names none
+PACK_PIECE_CHUNKS = 32            # chunks per call of the device packer: 34 MB of scratch and as much of output at most
+
+
+def bin_pack_counts():
+    """X chunks packed on the device / handed to the host packer by pack_blocks_device so far"""
+    return dict(bin_pack_chunk_counts)
+
+
+def bin_pack_route():
+    """-> "host" or "device" for the X blocks of TrainingSet.blocks().  The device packs only when asked -- tensor2Bin
+    --pack device, or CV_BIN_PACK=device -- and a GPU is present: the file's bytes differ between the routes (the same
+    arrays come back from both)."""
+    want = PACK_ROUTE if PACK_ROUTE is not None else os.environ.get("CV_BIN_PACK", "")
+    if want not in ("", "host", "device"):
+        raise _lib.CvError("CV_BIN_PACK / --pack must be host or device, not %r" % (want,))
+    return "device" if want == "device" and _gpu_present() else "host"
+
+
+def find_array_payload(stream):
+    """(offset, length) of the ndarray's raw data inside a pickled array, by the rule of cv_lz4_core.hpp's
+    find_array_payload (the bytes object found by opcode + length in the first 1 KiB that ends less than 256 bytes in
+    front of the end); None when there is none"""
+    n = len(stream)
+    for i in range(max(min(n, 1024) - 9, 0)):
+        op = stream[i]
+        if op in (0x42, 0x54):                         # BINBYTES 'B', BINSTRING 'T'
+            L, h = int.from_bytes(stream[i + 1:i + 5], "little"), 5
+        elif op in (0x8e, 0x96):                       # BINBYTES8, BYTEARRAY8
+            L, h = int.from_bytes(stream[i + 1:i + 9], "little"), 9
+            if L >= 1 << 40:
+                continue
+        else:
+            continue
+        end = i + h + L
+        if end <= n and n - end < 256 and L >= 16:
+            return i + h, L
+    return None
+
+
+def pickle_envelope(shape, dtype):
+    """-> (head, tail): what pickle.dumps(a, HIGHEST_PROTOCOL) puts around the raw data of a C-contiguous, writable array
+    `a` of this shape and dtype -- learnt from ONE stand-in array, nothing assumed about pickle's opcodes.  None when the
+    stand-in's data is not found in its pickle in one piece of the expected length (the caller then packs on the host)."""
+    dtype = np.dtype(dtype)
+    nbytes = int(np.prod(shape, dtype=np.int64)) * dtype.itemsize
+    if nbytes < 16:
+        return None
+    stand = np.empty(shape, dtype=dtype)
+    raw = stand.reshape(-1).view(np.uint8)
+    raw[:] = (np.arange(nbytes, dtype=np.uint64) * 2654435761 >> 7).astype(np.uint8)     # (no byte pattern of a pickle's own)
+    stream = pickle.dumps(stand, pickle.HIGHEST_PROTOCOL)
+    found = find_array_payload(stream)
+    if found is None or found[1] != nbytes or stream[found[0]:found[0] + nbytes] != raw.tobytes():
+        return None
+    return stream[:found[0]], stream[found[0] + nbytes:]
+
+
+_bin_pack_buffers = {}
+_bin_pack_told = set()
+
+
+def pack_blocks_device(X_dev, blocksize=None):
+    """The X blocks of a resident set packed in HBM (cv_blosc_pack_dev) -> [bytes]: one chunk per param.bloscBlockSize items
+    and one for the items left over, each what pack_array(X[s:s + 500], blocksize) decodes to, in c-blosc's multi-block
+    layout.  Works in pieces of PACK_PIECE_CHUNKS chunks; only the compressed bytes of a piece cross, into page-locked
+    memory.  A chunk the device hands back (it does not shrink), and a piece it does not take (the envelope is not
+    found, a stream is larger than the device's cap), is packed by the host from its rows; bin_pack_counts() counts both."""
+    import torch
+    lib = _lib.load()
+    bs = param.bloscBlockSize
+    blocksize = int(blocksize or DEVICE_PACK_BLOCKSIZE)
+    total = int(X_dev.shape[0])
+    ishape = tuple(int(d) for d in X_dev.shape[1:])
+    row = int(np.prod(ishape, dtype=np.int64)) * 4
+    out = []
+
+    def host_pack(lo, hi, reason=None):
+        if reason is not None and reason not in _bin_pack_told:
+            _bin_pack_told.add(reason)
+            logging.info("The host packs X blocks: %s" % reason)
+        a = X_dev[lo:hi].cpu().numpy()
+        for s in range(0, hi - lo, bs):
+            out.append(pack_array(np.ascontiguousarray(a[s:s + bs]), blocksize))
+            bin_pack_chunk_counts["host"] += 1
+
+    if total == 0:
+        return out
+    if not X_dev.is_cuda or X_dev.dtype != torch.float32 or not X_dev.is_contiguous() or row == 0:
+        host_pack(0, total, "the set is not a contiguous fp32 tensor in HBM")
+        return out
+    nfull = total // bs
+    pieces = [(c * bs, min(PACK_PIECE_CHUNKS, nfull - c), bs) for c in range(0, nfull, PACK_PIECE_CHUNKS)]
+    if total % bs:
+        pieces.append((nfull * bs, 1, total % bs))
+    with torch.cuda.device(X_dev.device):
+        dev = torch.device("cuda", torch.cuda.current_device())
+        bufs = _bin_pack_buffers.get(dev.index)
+        if bufs is None:
+            bufs = _bin_pack_buffers[dev.index] = _BinDecodeBuffers(dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        envelopes = {}                                  # per item count: the full chunks' and the partial one's
+        for lo, chunks, items in pieces:
+            hi = lo + chunks * items
+            if items not in envelopes:
+                envelopes[items] = pickle_envelope((items,) + ishape, np.float32)
+            env = envelopes[items]
+            if env is None:
+                host_pack(lo, hi, "the array's data was not found in a stand-in's pickle")
+                continue
+            head, tail = env
+            ws_bytes, bound = ctypes.c_int64(), ctypes.c_int64()
+            if lib.cv_blosc_pack_workspace(chunks, len(head) + items * row + len(tail), 4, blocksize, ctypes.byref(ws_bytes),
+                                           ctypes.byref(bound)) != 0:
+                msg = lib.cv_last_error()
+                host_pack(lo, hi, msg.decode("utf-8", "replace") if msg else "the device does not take these chunks")
+                continue
+            with bufs.lock:
+                ws = bufs.get("pack_ws", ws_bytes.value + 16)
+                slab = bufs.get("pack_out", bound.value + 16)
+                state = bufs.get("pack_state", 12 * chunks + 32)       # chunk_off int64[chunks + 1] | status int32[chunks]
+                st_at = 8 * (chunks + 1)
+                _lib.check(lib.cv_blosc_pack_dev(X_dev.data_ptr() + lo * row, chunks, items * row, head, len(head), tail, len(tail), 4,
+                                                 blocksize, slab.data_ptr(), bound.value, state.data_ptr(), state.data_ptr() + st_at,
+                                                 ws.data_ptr(), ws_bytes.value, stream))
+                got = state[:st_at + 4 * chunks].cpu().numpy()          # (waits for the piece)
+                off, status = got[:st_at].view(np.int64), got[st_at:].view(np.int32)
+                nb = int(off[chunks])
+                if not 0 <= nb <= bound.value or any(off[c] > off[c + 1] for c in range(chunks)):
+                    raise _lib.CvError("cv_blosc_pack_dev: chunk offsets outside the slab")
+                host = bufs.get("pack_host", nb + 16, pinned=True)
+                host[:nb].copy_(slab[:nb])
+                comp = host.numpy()
+                for c in range(chunks):
+                    if status[c] == 1 and off[c + 1] - off[c] >= 16:
+                        out.append(comp[off[c]:off[c + 1]].tobytes())
+                        bin_pack_chunk_counts["device"] += 1
+                    else:
+                        host_pack(lo + c * items, lo + (c + 1) * items)
+    return out

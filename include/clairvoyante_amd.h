@@ -495,6 +495,38 @@ int cv_blosc_unpack_dev(const int64_t *chunk_rows_dev, int64_t chunks, const uin
                         const uint8_t *scratch_dev, int64_t scratch_bytes, uint8_t *dst_dev, int64_t block_bytes,
                         int64_t *lens_dev, int32_t *status_dev, void *stream);
 
+/* The X blocks of a resident training set packed on the device (csrc/cv_blosc_pack_dev.hip; the encode core is
+ * csrc/cv_lz4enc_core.hpp).  A chunk is head | data_bytes_per_chunk bytes of rows | tail -- the pickle envelope of
+ * blosc.pack_array around the rows where they lie in HBM -- and is written in the layout of cv_blosc_compress_lz4_blocks
+ * (byte shuffle; blocks of `blocksize` bytes split into byte planes; one LZ4 block per plane, one wave each; a plane
+ * that does not shrink is stored).  All chunks of a call share one envelope (at most 2 048 bytes each of head and tail,
+ * host memory, copied once), so a partial last chunk is a call of its own.  Only typesize 4 is taken, and only chunks of
+ * at least 64 bytes whose streams hold at most cv_blosc_pack_stream_cap() bytes: anything else is an error, and the
+ * caller packs on the host.
+ * cv_blosc_pack_workspace -> the bytes of workspace_dev (16-byte aligned) and of out_dev a call over `chunks` (at most
+ * 65535) chunks of chunk_nbytes = head_len + data_bytes_per_chunk + tail_len bytes needs.
+ * cv_blosc_pack_dev enqueues the three phases on `stream`, allocates nothing and does not synchronise:
+ *   status_dev[c]    CV_BLOSC_OK: chunk c lies at out_dev[chunk_off_dev[c], chunk_off_dev[c + 1]);  CV_BLOSC_HOST: it
+ *                    would not be smaller than 16 + nbytes (the host writer memcpy's such a chunk) -- it takes no room,
+ *                    the caller packs it with cv_blosc_compress_lz4_blocks
+ *   chunk_off_dev    int64[chunks + 1], 8-byte aligned; only out_dev[0, chunk_off_dev[chunks]) needs to cross
+ * cv_blosc_pack_phase_dev launches one phase alone (0 encode, 1 layout, 2 assemble) on buffers a whole call has filled:
+ * for the probe's timing.
+ * cv_blosc_pack_host_form writes the same chunks with the host form of the core, from host memory into host memory
+ * (out_cap as cv_blosc_pack_workspace says): byte for byte what the device writes.                                    */
+int64_t cv_blosc_pack_stream_cap(void);
+int cv_blosc_pack_workspace(int64_t chunks, int64_t chunk_nbytes, int typesize, int64_t blocksize, int64_t *scratch_bytes,
+                            int64_t *out_bound);
+int cv_blosc_pack_dev(const uint8_t *data_dev, int64_t chunks, int64_t data_bytes_per_chunk, const uint8_t *head, int64_t head_len,
+                      const uint8_t *tail, int64_t tail_len, int typesize, int64_t blocksize, uint8_t *out_dev, int64_t out_cap,
+                      int64_t *chunk_off_dev, int32_t *status_dev, uint8_t *workspace_dev, int64_t workspace_bytes, void *stream);
+int cv_blosc_pack_phase_dev(int phase, const uint8_t *data_dev, int64_t chunks, int64_t data_bytes_per_chunk, int64_t head_len,
+                            int64_t tail_len, int typesize, int64_t blocksize, uint8_t *out_dev, int64_t out_cap,
+                            int64_t *chunk_off_dev, int32_t *status_dev, uint8_t *workspace_dev, int64_t workspace_bytes, void *stream);
+int cv_blosc_pack_host_form(const uint8_t *data, int64_t chunks, int64_t data_bytes_per_chunk, const uint8_t *head, int64_t head_len,
+                            const uint8_t *tail, int64_t tail_len, int typesize, int64_t blocksize, uint8_t *out, int64_t out_cap,
+                            int64_t *chunk_off, int32_t *status);
+
 /* CRC32C (Castagnoli) of the tensor bytes / table blocks of the TensorFlow V2 checkpoint
  * bundle written by saveParameters and read by restoreParameters (v3.py:243-251).        */
 uint32_t cv_crc32c(uint32_t crc, const void *data, int64_t n);
