@@ -28,7 +28,7 @@ if __package__ in (None, ""):      # run as `python <dir>/CreateTensor.py` (the 
     import clairvoyante_amd  # noqa: F401
     __package__ = "clairvoyante_amd"
 from . import param
-from .pileup import FLANK, Pileup, format_rows
+from .pileup import FLANK, Pileup, format_row_blocks
 
 EXPAND = 1000000          # dataPrepScripts/param.py:3 expandReferenceRegion
 READ_CHUNK = 8 << 20
@@ -135,13 +135,10 @@ def OutputAlnTensor(args):
     else:
         fpo = None
         fp = TensorStdout(sys.stdout.buffer)
-    step = 32768
-    centers, tensors = res["centers"], res["tensors"]
-    for s in range(0, len(centers), step):
-        host = tensors[s:s + step].cpu().numpy()
-        for row in format_rows(args.ctgName, centers[s:s + step], res["ref_seq"], res["shift"], host):
-            fp.stdin.write(row)
-            fp.stdin.write(b"\n")
+    # the rows are made on the device, one block and one write per 32 768 of them, or by format_rows on the host, row by
+    # row (pileup.format_row_blocks: CV_ROW_FORMAT, else pileup.ROWTEXT_DEVICE_MIN_ROWS) -- the same bytes either way
+    for block in format_row_blocks(args.ctgName, res["centers"], res["ref_seq"], res["shift"], res["tensors"]):
+        fp.stdin.write(block)
     if bgzf is not None:
         bgzf.close()
     elif fpo is not None:

@@ -323,3 +323,120 @@ def format_rows(ctg, centers, ref_seq, ref_shift, counts):
             raise _lib.CvError("cv_format_tensor_row: buffer too small")
         rows.append(buf.raw[:n])
     return rows
+
+
+# ---- the same rows written on the device (csrc/cv_rowtext_dev.hip) ---------------------------------------------------
+# CV_ROW_FORMAT=host|device forces a side; without it the device formats a call of at least ROWTEXT_DEVICE_MIN_ROWS rows
+# whose tensors lie on a GPU (None would make the route opt-in).  0: the device route won every run of every rung from
+# 16 384 rows on, 9-12 times faster than the host loop (profiles/r15/rowtext_device.txt).
+ROWTEXT_DEVICE_MIN_ROWS = 0
+ROWTEXT_BATCH = 32768           # rows per block of text
+_row_counts = {"host": 0, "device": 0}
+_pinned = None                  # the host end of the text's copy, grown on demand and kept
+
+
+def row_format_counts(reset=False):
+    """rows formatted since the start (or the last reset) per side: {"host": n, "device": n}"""
+    out = dict(_row_counts)
+    if reset:
+        _row_counts["host"] = _row_counts["device"] = 0
+    return out
+
+
+def _row_route(rows, on_gpu):
+    r = os.environ.get("CV_ROW_FORMAT")
+    if r is None or r == "":
+        return "device" if on_gpu and ROWTEXT_DEVICE_MIN_ROWS is not None and rows >= ROWTEXT_DEVICE_MIN_ROWS else "host"
+    if r not in ("host", "device"):
+        raise ValueError("row format route %r: host or device" % (r,))
+    return r
+
+
+def _host_block(ctg, centers, ref_seq, ref_shift, counts):
+    """one batch through format_rows -> its rows, each with its newline, as one block"""
+    rows = format_rows(ctg, centers, ref_seq, ref_shift, counts.cpu().numpy() if hasattr(counts, "cpu") else counts)
+    _row_counts["host"] += len(rows)
+    rows.append(b"")
+    return b"\n".join(rows)
+
+
+def _pinned_bytes(n):
+    import torch
+    global _pinned
+    if _pinned is None or _pinned.numel() < n:
+        _pinned = torch.empty(max(n, 1 << 20), dtype=torch.uint8).pin_memory()
+    return _pinned
+
+
+def format_rows_device(ctg, centers, ref_seq, ref_shift, tensors_dev, batch=ROWTEXT_BATCH):
+    """format_rows on the device: yields, per batch of at most 32 768 rows, ONE block of bytes -- the rows format_rows
+    gives for it, each followed by "\\n".  tensors_dev [k,33,4,4] fp32 on a GPU; ref_seq bytes / str (uploaded once here)
+    or a uint8 tensor already on that GPU.  A batch with a row the device does not vouch for (cv_tensor_rows_text_dev:
+    status CV_ROWTEXT_HOST) is formatted whole by format_rows, so is one with a centre less than 17 bytes into the
+    reference; row_format_counts() tells which side took what."""
+    import torch
+    if not tensors_dev.is_cuda:
+        raise _lib.CvError("format_rows_device: the tensors are not on a GPU; there is no CPU form of the kernel")
+    lib = _lib.load()
+    dev = tensors_dev.device
+    centers = np.ascontiguousarray(centers, dtype=np.int64)
+    k = len(centers)
+    if tensors_dev.dtype != torch.float32 or tuple(tensors_dev.shape) != (k, WIDTH, 4, 4):
+        raise _lib.CvError("format_rows_device: tensors of shape %r for %d centres" % (tuple(tensors_dev.shape), k))
+    cb = ctg.encode()
+    host_ref = None if isinstance(ref_seq, torch.Tensor) else (ref_seq.encode() if isinstance(ref_seq, str) else bytes(ref_seq))
+    with torch.cuda.device(dev):
+        if host_ref is None:
+            ref_dev = ref_seq
+        else:
+            ref_dev = torch.frombuffer(bytearray(host_ref) or bytearray(1), dtype=torch.uint8).to(dev)[:len(host_ref)]
+        ref_len = int(ref_dev.numel())
+        need = ctypes.c_int64(0)
+        _lib.check(lib.cv_tensor_rows_text_workspace(min(batch, max(k, 1)), ctypes.byref(need)))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+        for s in range(0, k, batch):
+            n = min(batch, k - s)
+            cen = torch.from_numpy(centers[s:s + n]).to(dev)
+            cnt = tensors_dev[s:s + n].contiguous()
+            off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            status = torch.empty(n, dtype=torch.uint8, device=dev)
+
+            def call(text, cap):
+                _lib.check(lib.cv_tensor_rows_text_dev(cb, len(cb), ptr(cen), n, ptr(ref_dev) if ref_len else None, int(ref_shift),
+                                                       ref_len, ptr(cnt), ptr(off), ptr(status), text, cap, ptr(ws), need.value,
+                                                       stream))
+            call(None, 0)                                   # lengths and status: the text is sized exactly
+            total, host_rows = (int(v) for v in torch.stack((off[n], status.sum(dtype=torch.int64))).tolist())
+            # (a window that starts in front of the reference: the kernel takes what lies inside, format_rows what Python's
+            # negative slice index selects -- CreateTensor drops such a candidate, anyone else gets format_rows' bytes)
+            if host_rows or int(centers[s:s + n].min()) - int(ref_shift) - (FLANK + 1) < 0:
+                if host_ref is None:
+                    host_ref = ref_dev.cpu().numpy().tobytes()
+                yield _host_block(ctg, centers[s:s + n], host_ref, ref_shift, cnt)
+                continue
+            text = torch.empty(total, dtype=torch.uint8, device=dev)
+            call(ptr(text), total)
+            pin = _pinned_bytes(total)
+            pin[:total].copy_(text, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+            _row_counts["device"] += n
+            yield pin.numpy()[:total].tobytes()
+
+
+def format_row_blocks(ctg, centers, ref_seq, ref_shift, tensors, batch=ROWTEXT_BATCH):
+    """the text of the rows as pieces to write one after the other, by the route CV_ROW_FORMAT / ROWTEXT_DEVICE_MIN_ROWS
+    choose: one block per `batch` rows from the device, row by row from the host (joining them first costs more than the
+    writes it saves); the same bytes either way.  tensors: [k,33,4,4] fp32, a torch tensor (on a GPU for the device route)."""
+    if _row_route(len(centers), bool(getattr(tensors, "is_cuda", False))) == "device":
+        for block in format_rows_device(ctg, centers, ref_seq, ref_shift, tensors, batch):
+            yield block
+        return
+    for s in range(0, len(centers), batch):                 # the host's loop as it always ran: a row, its newline, nothing joined
+        part = tensors[s:s + batch]
+        rows = format_rows(ctg, centers[s:s + batch], ref_seq, ref_shift, part.cpu().numpy() if hasattr(part, "cpu") else part)
+        _row_counts["host"] += len(rows)
+        for row in rows:
+            yield row
+            yield b"\n"

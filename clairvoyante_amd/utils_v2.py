@@ -6,6 +6,7 @@ With a GPU, large text tensor files are parsed on the device (GetTensorDevice, c
 training set of GetTrainingArray is built there (GetTrainingSetDevice, csrc/cv_trainset.hip); the host loops stay as
 the definition of both results.
 """
+import collections
 import ctypes
 import gc
 import gzip
@@ -575,15 +576,20 @@ def GetTensor(tensor_fn, num, log=True):
 class BgzfWriter(object):
     """write() / close() over a new BGZF file: every BLOCK input bytes become one gzip member -- raw DEFLATE from zlib
     between a header whose "BC" extra subfield states the member's size and the CRC-32 / ISIZE trailer --, the 28-byte
-    empty member that marks the end follows the last.  Any gzip reads the file as ordinary multi-member gzip."""
+    empty member that marks the end follows the last.  Any gzip reads the file as ordinary multi-member gzip.
+    threads: members compressed at a time (None: min(16, usable cores)); the file does not depend on it."""
     BLOCK = 65280
     EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
-    def __init__(self, fn, level=6, block=None, strategy=0):
+    def __init__(self, fn, level=6, block=None, strategy=0, threads=None):
         self.fh = open(fn, "wb") if isinstance(fn, str) else fn
         self.owned = isinstance(fn, str)
         self.level, self.block, self.strategy = level, min(block or self.BLOCK, self.BLOCK), strategy
         self.parts, self.have = [], 0
+        # members are independent: a pool compresses them side by side (zlib releases the GIL) and they are written in
+        # order, at most 2 x threads of them in flight.  threads=1: one member after the other on the caller's thread
+        self.threads = max(1, min(16, _lib.usable_cores()) if threads is None else int(threads))
+        self.pool, self.inflight = None, collections.deque()
 
     @staticmethod
     def member(data, level=6, strategy=0):
@@ -598,14 +604,30 @@ class BgzfWriter(object):
         return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(body) + 25) + body +
                 struct.pack("<II", zlib.crc32(data), len(data)))
 
+    def _put(self, data):
+        """the member of `data` goes to the file behind every member put before it"""
+        if self.threads == 1:
+            self.fh.write(self.member(data, self.level, self.strategy))
+            return
+        if self.pool is None:
+            from concurrent.futures import ThreadPoolExecutor
+            self.pool = ThreadPoolExecutor(max_workers=self.threads)
+        while len(self.inflight) >= 2 * self.threads:
+            self.fh.write(self.inflight.popleft().result())
+        self.inflight.append(self.pool.submit(self.member, data, self.level, self.strategy))
+
+    def _drain(self):
+        while self.inflight:
+            self.fh.write(self.inflight.popleft().result())          # (a worker's exception is raised here)
+
     def write(self, data):
         self.parts.append(bytes(data)); self.have += len(data)
         if self.have >= self.block:
             buf = b"".join(self.parts)
             cut = len(buf) - len(buf) % self.block
-            for at in range(0, cut, self.block):
-                self.fh.write(self.member(buf[at:at + self.block], self.level, self.strategy))
             self.parts, self.have = ([buf[cut:]], len(buf) - cut) if cut < len(buf) else ([], 0)
+            for at in range(0, cut, self.block):
+                self._put(buf[at:at + self.block])
         return len(data)
 
     def flush(self):
@@ -614,14 +636,24 @@ class BgzfWriter(object):
     def close(self):
         if self.fh is None:
             return
-        if self.have:
-            self.fh.write(self.member(b"".join(self.parts), self.level, self.strategy))
-        self.fh.write(self.EOF)
-        if self.owned:
-            self.fh.close()
-        else:
-            self.fh.flush()
-        self.fh = None
+        try:
+            if self.have:
+                self._put(b"".join(self.parts))
+                self.parts, self.have = [], 0
+            self._drain()
+            self.fh.write(self.EOF)
+        finally:
+            fh, self.fh = self.fh, None
+            if self.pool is not None:
+                for f in self.inflight:
+                    f.cancel()
+                self.inflight.clear()
+                self.pool.shutdown(wait=True)
+                self.pool = None
+            if self.owned:
+                fh.close()
+            else:
+                fh.flush()
 
     def __enter__(self):
         return self

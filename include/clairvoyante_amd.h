@@ -678,6 +678,24 @@ int cv_bamtrain_pair(int64_t nrows, const int32_t *ctg_dev, const int64_t *pos_d
  * counts: [33,4,4] fp32 raw counts (host).  Returns the length written, or -1 if cap is small.  */
 int64_t cv_format_tensor_row(const char *ctg, int64_t center, const char *seq, int64_t seqlen,
                              const float *counts, char *dst, int64_t cap);
+/* The same rows written in HBM (csrc/cv_rowtext_dev.hip, cv_rowtext_core.hpp): row r is cv_format_tensor_row + "\n" of
+ * centres_dev[r], counts_dev[r] ([rows,33,4,4] fp32) and the reference bytes [new_pos - 17, new_pos + 16) of the window
+ * ref_dev[0, ref_len) whose first byte is 0-based position ref_first0 (new_pos = centre - ref_first0; the bytes as they
+ * are, fewer than 33 where the window ends on either side), at text_dev + off_dev[r]; off_dev[rows + 1] int64, off_dev[rows] = bytes in all.
+ * The device vouches only for what the host prints through its integer branch: a row with a value that is negative,
+ * fractional, 2^24 or more, NaN or infinite, or with a centre < 1 gets
+ * status_dev[r] = CV_ROWTEXT_HOST and length 0 (the caller formats it with cv_format_tensor_row); a contig name of more
+ * than 255 bytes makes every row CV_ROWTEXT_HOST.  text_dev = NULL: lengths and status only, so that the caller can size
+ * the text exactly and call again.  A row that would end behind text_cap is not written; nothing behind off_dev[rows]
+ * is.  ctg is host memory; centres / off 8-byte, counts 16-byte, the workspace 256-byte aligned.  Asynchronous on
+ * `stream`.                                                                                                          */
+#define CV_ROWTEXT_DEVICE 0
+#define CV_ROWTEXT_HOST 1
+int cv_tensor_rows_text_workspace(int64_t rows, int64_t *bytes);
+int cv_tensor_rows_text_dev(const char *ctg, int64_t ctg_len, const int64_t *centres_dev, int64_t rows,
+                            const uint8_t *ref_dev, int64_t ref_first0, int64_t ref_len, const float *counts_dev,
+                            int64_t *off_dev, uint8_t *status_dev, char *text_dev, int64_t text_cap,
+                            void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---- native `samtools view` (optional producer, host only) ------------------------------------
  * The text of `samtools view -F <exclude_flags> BAM CTG[:S-E]` (CreateTensor.py:128-130,
