@@ -25,10 +25,12 @@ _CIGAR = re.compile(r"(\d+)([MIDNSHP=X])")
 BASE2NUM = dict(zip("ACGT", (0, 1, 2, 3)))
 
 
-def make_source(d, tag, ctg, seed, ref_len=6000, n_reads=900, region=(None, None)):
-    """one source on disk: SAM text (the stand-in's "BAM"), FASTA + .fai -> dict"""
+def make_source(d, tag, ctg, seed, ref_len=6000, n_reads=900, region=(None, None), read_len=None, profile=None):
+    """one source on disk: SAM text (the stand-in's "BAM"), FASTA + .fai -> dict; read_len / profile: those of
+    synth_pileup.make_alignments (default: its own)"""
     from clairvoyante_amd import synth_pileup as sp
-    ref, lines = sp.make_alignments(seed, ref_len=ref_len, n_reads=n_reads, ctg=ctg, start_hi=ref_len - 600)
+    kw = {} if read_len is None else {"read_len": read_len}
+    ref, lines = sp.make_alignments(seed, ref_len=ref_len, n_reads=n_reads, ctg=ctg, start_hi=ref_len - 600, profile=profile, **kw)
     sam, fa = os.path.join(d, tag + ".sam"), os.path.join(d, tag + ".fa")
     with open(sam, "w") as fh:
         fh.write("@SQ\tSN:%s\tLN:%d\n" % (ctg, ref_len) + "\n".join(lines) + "\n")

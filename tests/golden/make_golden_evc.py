@@ -6,7 +6,7 @@ make_golden_pileup.py (same .fa / .sam files) through fake_samtools.py.
 
   pileup/<case>.evc.args.json    options of the run
   pileup/<case>.evc.gz           the candidate rows it wrote
-  pileup/<case>.bed              (region_bed only) the BED file given to --bed_fn
+  pileup/<case>.bed              (region_bed, long_region) the BED file given to --bed_fn
 
 Ties between equal counts are ordered by the interpreter's dict order: this recording (CPython 3.9) and
 PyPy -- which the reference recommends for this script, README.md:101 -- keep insertion order
@@ -32,6 +32,15 @@ CASES = {
                               "bed_fn": "BED"}),
     "noisy": ("noisy", {"ctgStart": 0, "ctgEnd": 2000, "minCoverage": 1, "threshold": 0.05}),
     "lowcov": ("eqx", {"minCoverage": 0, "threshold": 0.3}),
+    "long": ("long", {"minCoverage": 1, "threshold": 0.05}),
+    "sparse": ("sparse", {"minCoverage": 1, "threshold": 0.05}),
+    # reads of thousands of bases hang over both ends of the region; the BED intervals cut through them
+    "long_region": ("long", {"ctgStart": 3000, "ctgEnd": 7000, "minCoverage": 1, "threshold": 0.05, "bed_fn": "BED"}),
+}
+
+BEDS = {
+    "region_bed": "ctgA\t650\t900\nctgA\t1200\t1201\nctgA\t1500\t2400\nother\t1\t50\nctgA\t2600\t2950\n",
+    "long_region": "ctgA\t2500\t3400\nctgA\t4000\t4001\nctgA\t4500\t5200\nother\t1\t50\nctgA\t6100\t6101\nctgA\t6800\t7500\n",
 }
 
 SHIM = '''
@@ -69,7 +78,7 @@ def main():
             if opts.get("bed_fn") == "BED":
                 bed = os.path.join(OUT, name + ".bed")
                 with open(bed, "w") as fh:
-                    fh.write("ctgA\t650\t900\nctgA\t1200\t1201\nctgA\t1500\t2400\nother\t1\t50\nctgA\t2600\t2950\n")
+                    fh.write(BEDS[name])
                 opts["bed_fn"] = bed
             out = os.path.join(OUT, name + ".evc.gz")
             cmd = [sys.executable, os.path.join(tmp, "ExtractVariantCandidates.py"), "--bam_fn", base + ".sam", "--ref_fn",

@@ -39,6 +39,11 @@ CASES = {
             {"minCoverage": 9}),
     "handmade_dcov1": ("handmade", None, {"dcov": 1}),
     "handmade": ("handmade", None, {}),
+    # reads of thousands of bases, and short reads spread thin: a tile of 512 segments spans far more than the 1 536
+    # positions / 40 candidates the column kernels keep in LDS (tests/pileup_tile_cases.py)
+    "long": (dict(seed=16, ref_len=10000, n_reads=24, read_len=(2500, 7000), profile=sp.NOISY_PROFILE, stack=3), dict(n=150),
+             {}),
+    "sparse": (dict(seed=17, ref_len=40000, n_reads=110), dict(n=150), {}),
 }
 
 

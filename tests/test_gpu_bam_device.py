@@ -368,7 +368,7 @@ def _golden_bam(name, tmp_path):
     return bam, fa
 
 
-@pytest.mark.parametrize("name", ["plain", "region", "noleftedge", "noisy", "eqx", "handmade", "handmade_dcov1"])
+@pytest.mark.parametrize("name", ["plain", "region", "noleftedge", "noisy", "eqx", "handmade", "handmade_dcov1", "long", "sparse"])
 def test_createtensor_rows_equal_reference_rows_through_the_device(name, tmp_path, monkeypatch):
     """case 8: the CreateTensor drop-in with --samtools native and CV_BAM_DECODE=device reproduces the committed rows"""
     from clairvoyante_amd import CreateTensor
@@ -385,7 +385,7 @@ def test_createtensor_rows_equal_reference_rows_through_the_device(name, tmp_pat
     assert sorted(gzip.open(a["tensor_fn"], "rt").read().splitlines()) == sorted(want)
 
 
-@pytest.mark.parametrize("name", ["plain", "region_bed", "noisy", "lowcov"])
+@pytest.mark.parametrize("name", ["plain", "region_bed", "noisy", "lowcov", "long", "sparse", "long_region"])
 def test_extract_candidates_rows_equal_reference_rows_through_the_device(name, tmp_path, monkeypatch):
     from clairvoyante_amd import ExtractVariantCandidates as evc
     from test_pileup_oracle import load_evc_case

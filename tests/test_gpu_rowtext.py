@@ -237,7 +237,8 @@ def run_ct(monkeypatch, side, args):
     return out.getvalue(), pileup.row_format_counts(), len(res["centers"])
 
 
-@pytest.mark.parametrize("name,over", [("plain", {}), ("noisy", {"ctgStart": 0, "ctgEnd": 2000, "minCoverage": 2, "dcov": 3})])
+@pytest.mark.parametrize("name,over", [("plain", {}), ("noisy", {"ctgStart": 0, "ctgEnd": 2000, "minCoverage": 2, "dcov": 3}),
+                                       ("long", {}), ("sparse", {})])
 def test_createtensor_writes_the_same_bytes_on_either_side(name, over, tmp_path, monkeypatch):
     texts = {}
     for side in ("host", "device"):

@@ -10,7 +10,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, ".."))
 G = os.path.join(HERE, "golden", "pileup")
-CASES = ["plain", "region", "noleftedge", "noisy", "eqx", "handmade", "handmade_dcov1"]
+CASES = ["plain", "region", "noleftedge", "noisy", "eqx", "handmade", "handmade_dcov1", "long", "sparse"]
 
 
 def load_case(name):
@@ -49,7 +49,7 @@ def test_oracle_rows_equal_reference_rows(name):
     assert pos == sorted(pos) and len(set(pos)) == len(pos)
 
 
-EVC_CASES = ["plain", "region_bed", "noisy", "lowcov"]
+EVC_CASES = ["plain", "region_bed", "noisy", "lowcov", "long", "sparse", "long_region"]
 
 
 def load_evc_case(name):
