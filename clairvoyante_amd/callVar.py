@@ -8,7 +8,8 @@ Pipeline (one process per GPU): a reader thread parses text tensors into pinned 
 (native parser), the GPU runs the network and the per-candidate arg-max / quality / depth
 reductions (cv_call_postproc), and the host formats VCF lines only for the candidates
 that produce one.  `Output()` keeps the reference's signature (host arrays in, text out)
-and is the formatter both paths share.
+and is the formatter both paths share.  CV_VCF_FORMAT=device (opt-in) writes the lines on the GPU instead
+(cv_vcf_records_dev, csrc/cv_vcf_dev.hip): the same bytes, and what returns per batch is the text alone.
 """
 import argparse
 import ctypes
@@ -254,6 +255,58 @@ def OutputFromDevice(args, call_fh, num, XBatch, posBatch, call, qual, xrow=None
         call_fh.write(text.decode("ascii"))
 
 
+# ---- the same records written on the device (csrc/cv_vcf_dev.hip) ----------------------------------------------------
+# CV_VCF_FORMAT=host|device chooses who writes the records of called_batches; unset means the host (cv_format_vcf), as
+# before: measured, the device route wins with --showRef and ties without it, and no default was chosen from that.
+_vcf_counts = {"host": 0, "device": 0, "handed_over": 0}
+_vcf_counts_lock = __import__("threading").Lock()      # called_batches may run on one thread per GPU
+
+
+def _count_batch(*sides):
+    with _vcf_counts_lock:
+        for side in sides:
+            _vcf_counts[side] += 1
+
+
+def vcf_format_route():
+    """"host" or "device": CV_VCF_FORMAT, "host" when it is not set"""
+    forced = os.environ.get("CV_VCF_FORMAT")
+    if forced in ("host", "device"):
+        return forced
+    if forced:
+        raise ValueError("CV_VCF_FORMAT must be 'host' or 'device', got %r" % forced)
+    return "host"
+
+
+def vcf_format_counts():
+    """batches of called_batches whose records the host / the device wrote, and how many of the host's the device
+    handed over (a batch with a candidate cv_vcf_records_dev does not vouch for goes to cv_format_vcf whole)"""
+    with _vcf_counts_lock:
+        return dict(_vcf_counts)
+
+
+def _packed_tokens(buf, meta):
+    """-> (bytes, meta): the tokens `meta` names inside `buf`, packed end to end when `buf` holds much more than them (a
+    host-parsed batch's pieces are views of the input text, ~2.3 KB per row for ~40 bytes of tokens)"""
+    b = buf if isinstance(buf, np.ndarray) else np.frombuffer(buf, dtype=np.uint8)
+    lens = meta[:, 1::2].reshape(-1)
+    total = int(lens.sum())
+    if len(b) <= 2 * total + 4096:
+        return b, meta
+    new = np.cumsum(lens) - lens
+    idx = np.repeat(meta[:, 0::2].reshape(-1) - new, lens) + np.arange(total, dtype=np.int64)
+    packed = meta.copy()
+    packed[:, 0::2] = new.reshape(-1, 3)
+    return b[idx], packed
+
+
+def device_tokens(text, meta, first=0):
+    """what a PosBatch carries as `.device` when its tokens lie in HBM: the address of the bytes, of the [rows,6] meta
+    from row `first` on, no row index, nothing parsed on the host"""
+    return {"text_ptr": text.data_ptr(), "meta_ptr": meta.data_ptr() + first * 48, "keep": None, "merged": False,
+            "hold": (text, meta)}
+
+
 def predict_and_reduce(m, xd):
     """network + per-candidate reductions on the device: x [n,33,4,4] -> (call [n,8] int32, qual [n,4] fp32)"""
     import torch
@@ -310,6 +363,96 @@ class ResultFetcher(object):
             self.side.synchronize()
             return call, qual, rows_h.numpy(), xrow
 
+    def upload(self, arrays):
+        """host arrays (8-byte aligned sizes first) as ONE block of HBM, copied on the side stream from a page-locked
+        buffer so that it does not queue behind the kernels of the batch before; the current stream waits for it.
+        -> (uint8 tensor, byte offset of each array in it, the page-locked buffer: to be held until the copy has run)"""
+        import torch
+        offs = np.cumsum([0] + [(a.nbytes + 7) & ~7 for a in arrays])
+        stage = torch.empty(int(offs[-1]), dtype=torch.uint8, pin_memory=True)
+        h = stage.numpy()
+        for a, o in zip(arrays, offs):
+            h[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+        with torch.cuda.stream(self.side):
+            block = stage.to(self.m.device, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.side)
+        torch.cuda.current_stream(self.m.device).wait_event(ev)
+        return block, [int(o) for o in offs[:-1]], stage
+
+    def fetch_text(self, ev, parts):
+        """the records cv_vcf_records_dev wrote for a batch (enqueue_records): the 32 bytes of info per call, then exactly
+        info[0] bytes of text -> bytes, or None when a candidate was left to the host (info[2] > 0)"""
+        import torch
+        with torch.cuda.stream(self.side):
+            self.side.wait_event(ev)
+            info_h = torch.empty((len(parts), 4), dtype=torch.int64, pin_memory=True)
+            for k, p in enumerate(parts):
+                info_h[k].copy_(p["info"], non_blocking=True)
+            self.side.synchronize()
+            info = info_h.numpy()
+            if int(info[:, 2].sum()) > 0:
+                return None
+            total = int(info[:, 0].sum())
+            if total == 0:
+                return b""
+            text_h = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            at = 0
+            for k, p in enumerate(parts):
+                nb = int(info[k, 0])
+                if nb:
+                    text_h[at:at + nb].copy_(p["text"][:nb], non_blocking=True)
+                at += nb
+            self.side.synchronize()
+            return text_h.numpy().tobytes()
+
+
+def enqueue_records(args, m, fetcher, num, xd, pos, call, qual):
+    """cv_vcf_records_dev for one batch on the current stream, right behind its cv_call_postproc: one call per piece of
+    `pos`.  The tokens are read where they lie in HBM when the batch says so (pos.device: GetTensorDevice with
+    keep_device, CallFromDevice); otherwise the piece's tokens and meta are uploaded, ~90 bytes per row.  text_cap is
+    the host's own bound, n (longest contig token + 160).  -> [{"info": [4] int64, "text": uint8, ...}] in HBM, for
+    ResultFetcher.fetch_text; `call`, `qual` and the rows of xd stay where they are."""
+    import torch
+    from . import _lib
+    from .utils_v2 import PosBatch
+    lib, dev = _lib.load(), m.device
+    if not isinstance(pos, PosBatch):
+        pos = PosBatch.from_strings([pos[i] for i in range(num)])
+    d = getattr(pos, "device", None)
+    pieces = pos.pieces()
+    calls = []                               # (first candidate, n, text address, meta address, row index tensor or None, longest contig, held)
+    if d is not None and not d["merged"] and d.get("text_ptr") and d.get("meta_ptr"):
+        longest = max([int(meta[:, 1].max()) for _s, rows, _b, meta in pieces if rows] or [0])
+        keep = None if d["keep"] is None else fetcher.upload([np.ascontiguousarray(d["keep"], dtype=np.int64)])
+        calls.append((0, num, d["text_ptr"], d["meta_ptr"], keep[0] if keep else None, longest, (d, keep)))
+    else:
+        for start, rows, buf, meta in pieces:
+            n = min(start + rows, num) - start
+            if n <= 0:
+                continue
+            tok, tmeta = _packed_tokens(buf, np.ascontiguousarray(meta[:n], dtype=np.int64))
+            block, offs, stage = fetcher.upload([tmeta, tok])
+            calls.append((start, n, block.data_ptr() + offs[1], block.data_ptr() + offs[0], None, int(tmeta[:, 1].max()), (block, stage)))
+    need = ctypes.c_int64()
+    parts = []
+    for start, n, text_ptr, meta_ptr, keep, longest, held in calls:
+        _lib.check(lib.cv_vcf_records_workspace(n, ctypes.byref(need)))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        small = torch.empty(4 + n + 1, dtype=torch.int64, device=dev)            # info | off
+        status = torch.empty(n, dtype=torch.uint8, device=dev)
+        cap = n * (longest + 160)
+        text = torch.empty(cap, dtype=torch.uint8, device=dev)
+        _lib.check(lib.cv_vcf_records_dev(
+            ctypes.c_void_p(call.data_ptr() + start * 32), ctypes.c_void_p(qual.data_ptr() + start * 16), n,
+            ctypes.c_void_p(xd.data_ptr() + start * 2112), None, ctypes.c_void_p(text_ptr), ctypes.c_void_p(meta_ptr),
+            ctypes.c_void_p(keep.data_ptr()) if keep is not None else None, 1 if args.showRef else 0, 0 if args.qual is None else 1,
+            0 if args.qual is None else int(args.qual), ctypes.c_void_p(small.data_ptr() + 32), ctypes.c_void_p(status.data_ptr()),
+            ctypes.c_void_p(small.data_ptr()), ctypes.c_void_p(text.data_ptr()), cap, ctypes.c_void_p(ws.data_ptr()), need.value,
+            m._stream()))
+        parts.append({"info": small[:4], "text": text, "held": (ws, small, status, held)})
+    return parts
+
 
 def called_batches(args, m, items):
     """The call loop: `items` are (key, num, X, pos) batches -- X a host array ([num,33,4,4] fp32, copied to the
@@ -322,9 +465,17 @@ def called_batches(args, m, items):
     try:
         with torch.cuda.device(m.device):
             fetcher = ResultFetcher(m)
-            pending = None                   # (key, num, X, pos, call_dev, qual_dev, event) of the batch the GPU works on
+            pending = None                   # (key, num, X, pos, call_dev, qual_dev, records, event) of the batch the GPU works on
+            on_device = vcf_format_route() == "device"
 
-            def finish(key, num, X, pos, call, qual, ev):
+            def finish(key, num, X, pos, call, qual, records, ev):
+                if records is not None:      # the records were written in HBM: 32 bytes of info, then the text itself
+                    text = fetcher.fetch_text(ev, records)
+                    if text is not None:
+                        _count_batch("device")
+                        return key, text
+                    _count_batch("handed_over")            # a candidate the device does not vouch for: the batch goes the host's way
+                _count_batch("host")
                 if torch.is_tensor(X):       # rows on the device: only those that give a record come to the host
                     hcall, hqual, rows, xrow = fetcher.fetch(ev, call, qual, X, bool(args.showRef))
                     return key, format_records(args, num, rows, pos, hcall, hqual, xrow)
@@ -336,7 +487,8 @@ def called_batches(args, m, items):
                 if num:
                     xd = X if torch.is_tensor(X) else torch.from_numpy(X).to(m.device, non_blocking=True)
                     call, qual = predict_and_reduce(m, xd)
-                    nxt = (key, num, X, pos, call, qual, fetcher.mark())
+                    records = enqueue_records(args, m, fetcher, num, xd, pos, call, qual) if on_device else None
+                    nxt = (key, num, X, pos, call, qual, records, fetcher.mark())
                 if pending is not None:      # format batch k while the GPU works on batch k + 1
                     yield finish(*pending)
                 pending = nxt
@@ -362,7 +514,20 @@ def CallFromDevice(args, m, call_fh, X_dev, pos, batch=65536):
         pos = PosBatch.from_strings(list(pos))
         pieces = pos.pieces()
     _start, _rows, buf, meta = pieces[0]
-    slices = ((0, min(batch, n - s), X_dev[s:s + batch].contiguous(), PosBatch(buf, meta[s:s + batch])) for s in range(0, n, batch))
+    tokens = None
+    if n and vcf_format_route() == "device":         # the records are written in HBM: the tokens go there once, not per slice
+        import torch
+        b = buf if isinstance(buf, np.ndarray) else np.frombuffer(buf, dtype=np.uint8)
+        tokens = (torch.from_numpy(np.ascontiguousarray(b).copy()).to(X_dev.device),
+                  torch.from_numpy(np.ascontiguousarray(meta[:n], dtype=np.int64).copy()).to(X_dev.device))
+
+    def piece(s):
+        p = PosBatch(buf, meta[s:s + batch])
+        if tokens is not None:
+            p.device = device_tokens(tokens[0], tokens[1], s)
+        return p
+
+    slices = ((0, min(batch, n - s), X_dev[s:s + batch].contiguous(), piece(s)) for s in range(0, n, batch))
     for _key, text in called_batches(args, m, slices):
         call_fh.write(text.decode("ascii"))
 
@@ -627,7 +792,9 @@ def Test(args, m, utils):
             side = "device" if on_device else "host"
             utils.text_parse_counts[side] += 1
             logging.info("Text tensors are parsed on the %s" % side)
-            for _end, c, X, pos in (utils.GetTensorDevice(files[0], batch, m.device) if on_device else utils.GetTensor(files[0], batch)):
+            # (records written on the device read the tokens where the parser left them: keep_device)
+            for _end, c, X, pos in (utils.GetTensorDevice(files[0], batch, m.device, keep_device=vcf_format_route() == "device")
+                                    if on_device else utils.GetTensor(files[0], batch)):
                 yield 0, c, X, pos
             yield 0, None, None, None
 

@@ -129,6 +129,32 @@ int cv_eval_counts(const float *out16_dev, const void *y_dev, int y_is_f64, int6
 int cv_format_vcf(const int32_t *call, const float *qual, int64_t n, const float *x, const int64_t *xrow,
                   const char *pos_buf, const int64_t *pos_meta, const int64_t *pos_row, int show_ref,
                   int has_qual, int qual_min, char *out, int64_t out_cap, int64_t *out_len, int64_t *nrecords);
+/* The same records written in HBM (csrc/cv_vcf_dev.hip, cv_vcf_core.hpp): the arguments of cv_format_vcf as DEVICE
+ * pointers, line i ('\n'-terminated) at text_dev + off_dev[i], dense and in candidate order; off_dev [n + 1] int64,
+ * off_dev[n] = bytes in all; info_dev [4] int64 = {bytes, records, CV_VCF_HOST candidates, 0}.  status_dev[i] is
+ * CV_VCF_NONE (no record: REF without show_ref, depth 0), CV_VCF_DEVICE (the line is cv_format_vcf's, byte for byte) or
+ * CV_VCF_HOST with length 0: what the device does not vouch for and the caller gives to cv_format_vcf, which prints it
+ * or refuses it with its own message -- decisions out of range; a quality whose integer is not certain (it is where
+ * p2 + 1e-300 == p1 + 1e-300, or where the core's own log puts q further than 2^-40 max(1, |q|) from an integer) or
+ * not finite, whatever the depth; a depth that is not a positive integer below 2^24 (0 is CV_VCF_NONE); an allele
+ * fraction of 1e9 or more, NaN or infinite; a position that is not 1..18 bare digits; a sequence of 16 bytes or
+ * fewer; a contig name above 255 bytes; a centre base outside ACGT where it names the allele.
+ * text_dev = NULL: lengths, status and info only.  A line that would end behind text_cap is not written (text_cap =
+ * n (longest contig name + 160) holds every batch); nothing behind off_dev[n] is.  call / qual / x 4-byte, the int64
+ * arrays 8-byte, the workspace 256-byte aligned.  Asynchronous on `stream`: no allocation, no synchronisation.  n == 0
+ * returns 0 and touches nothing; a null or misaligned pointer or n < 0 returns 1.
+ * cv_vcf_records_host_form: the same core on the CPU over HOST pointers (tests hold the kernels to it).            */
+#define CV_VCF_NONE 0
+#define CV_VCF_DEVICE 1
+#define CV_VCF_HOST 2
+int cv_vcf_records_workspace(int64_t n, int64_t *bytes);
+int cv_vcf_records_dev(const int32_t *call_dev, const float *qual_dev, int64_t n, const float *x_dev, const int64_t *xrow_dev,
+                       const char *pos_buf_dev, const int64_t *pos_meta_dev, const int64_t *pos_row_dev, int show_ref,
+                       int has_qual, int qual_min, int64_t *off_dev, uint8_t *status_dev, int64_t *info_dev, char *text_dev,
+                       int64_t text_cap, void *workspace, int64_t workspace_bytes, void *stream);
+int cv_vcf_records_host_form(const int32_t *call, const float *qual, int64_t n, const float *x, const int64_t *xrow,
+                             const char *pos_buf, const int64_t *pos_meta, const int64_t *pos_row, int show_ref, int has_qual,
+                             int qual_min, int64_t *off, uint8_t *status, int64_t *info, char *text, int64_t text_cap);
 
 /* debug / parity: copy one intermediate of the LAST cv_forward chunk to
  * dst_dev in the reference's natural layout ([n,h,4,c] NHWC or [n,units]).
