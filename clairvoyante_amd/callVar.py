@@ -420,14 +420,15 @@ def enqueue_records(args, m, fetcher, num, xd, pos, call, qual):
     if not isinstance(pos, PosBatch):
         pos = PosBatch.from_strings([pos[i] for i in range(num)])
     d = getattr(pos, "device", None)
-    pieces = pos.pieces()
     calls = []                               # (first candidate, n, text address, meta address, row index tensor or None, longest contig, held)
     if d is not None and not d["merged"] and d.get("text_ptr") and d.get("meta_ptr"):
-        longest = max([int(meta[:, 1].max()) for _s, rows, _b, meta in pieces if rows] or [0])
+        longest = d.get("longest")           # (a batch made on the device knows it without its host copy: DevicePosBatch)
+        if longest is None:
+            longest = max([int(meta[:, 1].max()) for _s, rows, _b, meta in pos.pieces() if rows] or [0])
         keep = None if d["keep"] is None else fetcher.upload([np.ascontiguousarray(d["keep"], dtype=np.int64)])
         calls.append((0, num, d["text_ptr"], d["meta_ptr"], keep[0] if keep else None, longest, (d, keep)))
     else:
-        for start, rows, buf, meta in pieces:
+        for start, rows, buf, meta in pos.pieces():
             n = min(start + rows, num) - start
             if n <= 0:
                 continue
@@ -504,9 +505,18 @@ def CallFromDevice(args, m, call_fh, X_dev, pos, batch=65536):
     """VCF records for tensors that are already in HBM (callVarBam's fused path): X_dev [n,33,4,4] with matrices 1..3
     minus matrix 0; pos: utils_v2.PosBatch (or a function i -> "chrom:coord:seq") for the n rows.  Batch k's decisions
     and the rows that produce a record (non-REF calls, or all with --showRef) come to the host on a side stream and
-    are formatted by the host threads while the GPU runs batch k+1 (called_batches)."""
-    from .utils_v2 import PosBatch
+    are formatted by the host threads while the GPU runs batch k+1 (called_batches).  A utils_v2.DevicePosBatch (its
+    tokens lie in HBM already) is cut into parts that point there: nothing is uploaded for it, and its host copy is
+    fetched only if a batch is formatted by the host."""
+    from .utils_v2 import DevicePosBatch, PosBatch
     n = X_dev.shape[0]
+    if isinstance(pos, DevicePosBatch):
+        if len(pos) != n:
+            raise ValueError("CallFromDevice: %d positions for %d tensors" % (len(pos), n))
+        slices = ((0, min(batch, n - s), X_dev[s:s + batch].contiguous(), pos.part(s, batch)) for s in range(0, n, batch))
+        for _key, text in called_batches(args, m, slices):
+            call_fh.write(text.decode("ascii"))
+        return
     if callable(pos):
         pos = PosBatch.from_strings([pos(i) for i in range(n)])
     pieces = pos.pieces()

@@ -10,6 +10,8 @@ candidate pass, the tensor pass, the network and the per-candidate reductions al
 only the records of non-reference calls come back to the host (clairvoyante_amd/pileup.py,
 csrc/cv_pileup.hip).  Each stage equals its stand-alone drop-in (ExtractVariantCandidates, CreateTensor,
 callVar), so the VCF is the one the reference's pipe produces, with records in ascending position.
+CV_CALL_COLUMNS=device (opt-in) also picks the rows that reach the network and writes their contig / coordinate / window
+tokens on the GPU (csrc/cv_callcols_dev.hip) instead of per candidate in Python: the same VCF bytes.
 --pypy, --threads and --delay are accepted and ignored (no interpreter / TensorFlow start-up to stagger).
 """
 import argparse
@@ -62,10 +64,60 @@ def truth_positions(args, ctgStart, ctgEnd):
     return np.unique(np.asarray(pos, dtype=np.int64))
 
 
+# ---- candidate tokens and row selection: on the host (the definition) or on the device (csrc/cv_callcols_dev.hip) ------
+# CV_CALL_COLUMNS=host|device forces a side; unset means CALL_COLUMNS_DEFAULT.  The VCF is the same bytes either way.
+# "host": measured (profiles/r17/call_columns_device.txt) the device route is 2.4 times ahead end to end on
+# long reads and ahead at 20 000 and 2 M short reads, but at 200 000 short reads the hop is 3.5 ms of a run whose front end
+# varies by more, and not every run was ahead of the parent commit's -- the rule for a default was "every run of every rung".
+CALL_COLUMNS_DEFAULT = "host"
+_COLUMN_KEYS = ("host_regions", "host_candidates", "device_regions", "device_candidates", "handed_over_regions")
+_column_counts = dict.fromkeys(_COLUMN_KEYS, 0)
+
+
+def call_column_counts(reset=False):
+    """regions and candidate centres region_tensors took since the start (or the last reset), per side, and the regions
+    the device route handed over to the host (a contig name or a number of centres above what Pileup.call_columns takes)"""
+    out = dict(_column_counts)
+    if reset:
+        for k in _COLUMN_KEYS:
+            _column_counts[k] = 0
+    return out
+
+
+def call_columns_route():
+    """"host" or "device": CV_CALL_COLUMNS, CALL_COLUMNS_DEFAULT when it is not set"""
+    forced = os.environ.get("CV_CALL_COLUMNS")
+    if forced in ("host", "device"):
+        return forced
+    if forced:
+        raise ValueError("CV_CALL_COLUMNS must be 'host' or 'device', got %r" % forced)
+    return CALL_COLUMNS_DEFAULT
+
+
+class _Region(dict):
+    """region_tensors' result on the device route: "centers" (the kept centres as a host int64 array) and "seqs" (their
+    windows) are made when they are asked for -- the first fetches the index, the second cuts the host's reference"""
+
+    def __init__(self, items, centers, index, ref_seq, shift):
+        dict.__init__(self, items)
+        self._lazy = (centers, index, ref_seq, shift)
+
+    def __missing__(self, key):
+        centers, index, ref_seq, shift = self._lazy
+        if key == "centers":
+            self[key] = centers[index.cpu().numpy()]
+        elif key == "seqs":
+            self[key] = [ref_seq[int(p) - (FLANK + 1):int(p) + FLANK].upper() for p in self["centers"] - shift]     # (kept: p >= 17)
+        else:
+            raise KeyError(key)
+        return self[key]
+
+
 def region_tensors(args, device=None, source=None):
     """candidates + tensors of one region, on the device.  -> dict(centers, tensors (matrices 1..3 minus
-    matrix 0), seqs, stats, reads, candidates)"""
-    import torch
+    matrix 0), seqs, pos (the PosBatch of the kept rows), route, stats, reads, candidates, hop_s: the seconds between
+    finish() and the call loop)"""
+    route = call_columns_route()
     ctgStart, ctgEnd, refStart, refEnd = region_of(args)
     ref_seq = load_reference(args, refStart, refEnd)
     shift = 0 if refStart is None else refStart - 1
@@ -85,19 +137,42 @@ def region_tensors(args, device=None, source=None):
         pl.adopt_candidates(ctgStart, ctgEnd)
         n_candidates = pl.n
     t, depth, touched = pl.finish(subtract=True)
-    centers = pl.centers
-    # a row exists iff a read reached the candidate and its window starts inside the loaded reference
-    # (CreateTensor.py:50-51, --minCoverage 0); the reader drops rows whose centre base is not ACGT after
-    # upper-casing (utils_v2.py:38-40)
-    new_pos = centers - shift
-    seqs = [ref_seq[max(int(p) - (FLANK + 1), 0):int(p) + FLANK].upper() if p - (FLANK + 1) >= 0 else b"" for p in new_pos]
-    ok = np.array([len(sq) > FLANK and sq[FLANK:FLANK + 1] in (b"A", b"C", b"G", b"T") for sq in seqs], dtype=bool)
-    keep = touched & torch.from_numpy(ok).to(t.device)
-    idx = torch.nonzero(keep).squeeze(1)
-    idx_h = idx.cpu().numpy()
-    out = {"centers": centers[idx_h], "tensors": t.index_select(0, idx), "seqs": [seqs[i] for i in idx_h],
-           "stats": pl.stats(), "reads": pl.reads_kept, "candidates": n_candidates}
+    t_hop = time.time()
+    out = select_rows(pl, t, touched, args.ctgName, ref_seq, shift, route)
+    out.update({"stats": pl.stats(), "reads": pl.reads_kept, "candidates": n_candidates, "hop_s": time.time() - t_hop})
     pl.close()
+    return out
+
+
+def select_rows(pl, t, touched, ctg, ref_seq, shift, route):
+    """the hop between pl.finish() and the call loop, on the side `route` names: which centres give a row, their tensors and
+    their tokens -> dict(centers, tensors, seqs, pos, route)"""
+    import torch
+    from .pileup import CALL_COLUMNS_MAX_CTG, CALL_COLUMNS_MAX_ROWS
+    from .utils_v2 import PosBatch
+    centers = pl.centers
+    if route == "device" and (len(str(ctg).encode("ascii")) > CALL_COLUMNS_MAX_CTG or pl.n > CALL_COLUMNS_MAX_ROWS):
+        _column_counts["handed_over_regions"] += 1
+        route = "host"
+    if route == "device":
+        # the verdict, the compaction and the tokens in HBM: two integers come back (Pileup.call_columns)
+        idx, pos = pl.call_columns(touched, ctg)
+        out = _Region({"tensors": t.index_select(0, idx), "pos": pos}, centers, idx, ref_seq, shift)
+    else:
+        # a row exists iff a read reached the candidate and its window starts inside the loaded reference
+        # (CreateTensor.py:50-51, --minCoverage 0); the reader drops rows whose centre base is not ACGT after
+        # upper-casing (utils_v2.py:38-40)
+        new_pos = centers - shift
+        seqs = [ref_seq[max(int(p) - (FLANK + 1), 0):int(p) + FLANK].upper() if p - (FLANK + 1) >= 0 else b"" for p in new_pos]
+        ok = np.array([len(sq) > FLANK and sq[FLANK:FLANK + 1] in (b"A", b"C", b"G", b"T") for sq in seqs], dtype=bool)
+        keep = touched & torch.from_numpy(ok).to(t.device)
+        idx = torch.nonzero(keep).squeeze(1)
+        idx_h = idx.cpu().numpy()
+        out = {"centers": centers[idx_h], "tensors": t.index_select(0, idx), "seqs": [seqs[i] for i in idx_h]}
+        out["pos"] = PosBatch.from_columns(ctg, out["centers"], out["seqs"])
+    _column_counts[route + "_regions"] += 1
+    _column_counts[route + "_candidates"] += pl.n
+    out["route"] = route
     return out
 
 
@@ -130,21 +205,21 @@ def Run(args, model=None, source=None):
         m.restoreParameters(chkpnt_fn)
     else:
         m = model
+    t_model = time.time()
     res = region_tensors(args, device=m.device.index, source=source)
     t1 = time.time()
     cargs = argparse.Namespace(call_fn=args.call_fn, qual=args.qual, sampleName=args.sampleName, ref_fn=args.ref_fn,
                                showRef=False)
-    ctg = args.ctgName
-    centers, seqs = res["centers"], res["seqs"]
     with open(args.call_fn, "w") as call_fh:
         callVar.PrintVCFHeader(cargs, call_fh)
-        from .utils_v2 import PosBatch
-        callVar.CallFromDevice(cargs, m, call_fh, res["tensors"], PosBatch.from_columns(ctg, centers, seqs))
+        callVar.CallFromDevice(cargs, m, call_fh, res["tensors"], res["pos"])
     st = res["stats"]
     logging.info("reads %d, candidates %d, tensors %d; pileup %.2f s (GPU: candidates %.1f ms, scatter %.1f ms, "
-                 "finalize %.1f ms), calling %.2f s" % (res["reads"], res["candidates"], len(centers), t1 - t0,
-                                                        st["candidate_ms"], st["scatter_ms"], st["finalize_ms"],
-                                                        time.time() - t1))
+                 "finalize %.1f ms; rows and tokens on the %s %.1f ms), calling %.2f s"
+                 % (res["reads"], res["candidates"], res["tensors"].shape[0], t1 - t0, st["candidate_ms"], st["scatter_ms"],
+                    st["finalize_ms"], res["route"], res["hop_s"] * 1e3, time.time() - t1))
+    # where the run's time went (seconds): the model, the front end up to finish(), the hop, the call loop
+    res["times"] = {"model_s": t_model - t0, "front_s": t1 - t_model - res["hop_s"], "hop_s": res["hop_s"], "call_s": time.time() - t1}
     if model is None:
         m.close()
     return res

@@ -11,6 +11,9 @@ from . import _lib
 
 FLANK = 16
 WIDTH = 2 * FLANK + 1
+CALL_COLUMNS_ROW_TEXT = 10 + WIDTH      # bytes of a row's coordinate and window at most (CV_CALL_COLUMNS_ROW_TEXT)
+CALL_COLUMNS_MAX_CTG = 1024             # bytes of a contig name call_columns takes (CV_CALL_COLUMNS_MAX_CTG)
+CALL_COLUMNS_MAX_ROWS = 1 << 27
 FLUSH_COLUMNS = 1 << 26         # queue at most this many alignment columns on the host before a scatter launch
 
 # BAM records on the device (csrc/cv_bam_dev.hip): `route` of Pileup.add_bam, else CV_BAM_DECODE=host|device, else the
@@ -297,6 +300,35 @@ class Pileup(object):
                                                 p(col["centre"]), p(col["acgt"]), p(col["cflag"]), p(col["row"]),
                                                 self._stream()))
         return col
+
+    def call_columns(self, touched, contig):
+        """behind finish(): what callVarBam needs between the tensors and the call loop, made in HBM
+        (csrc/cv_callcols_dev.hip) -> (index int64 [k] on the device: the centres that give a row -- touched, window
+        starting inside the loaded reference, centre base one of ACGT -- ascending; utils_v2.DevicePosBatch of those k
+        rows: the bytes and meta of PosBatch.from_columns(contig, centres[index], windows)).  Two integers come to the
+        host here; the batch fetches its host copy only if someone reads it."""
+        import torch
+        from .utils_v2 import DevicePosBatch
+        cb = contig if isinstance(contig, bytes) else str(contig).encode("ascii")
+        n = self.n
+        if touched.numel() != n:
+            raise _lib.CvError("call_columns: %d flags for %d centres" % (touched.numel(), n))
+        with torch.cuda.device(self.device):
+            u8 = touched.contiguous().view(torch.uint8) if touched.dtype == torch.bool else touched.to(torch.uint8).contiguous()
+            need = ctypes.c_int64(0)
+            _lib.check(self.lib.cv_call_columns_workspace(n, ctypes.byref(need)))
+            cap = len(cb) + CALL_COLUMNS_ROW_TEXT * n
+            # info [4] | index [n] | meta [n,6] | text: the meta and the text are neighbours, so one copy fetches both
+            block = torch.empty(32 + 8 * n + 48 * n + cap + 8, dtype=torch.uint8, device=self.device)
+            ws = torch.empty(max(need.value, 256), dtype=torch.uint8, device=self.device)
+            base = block.data_ptr()
+            _lib.check(self.lib.cv_pileup_call_columns(self.h, cb, len(cb), ctypes.c_void_p(u8.data_ptr()) if n else None,
+                                                       ctypes.c_void_p(base + 32), ctypes.c_void_p(base + 32 + 8 * n),
+                                                       ctypes.c_void_p(base + 32 + 56 * n), cap, ctypes.c_void_p(base),
+                                                       ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream()))
+            k, nbytes = block[:16].view(torch.int64).tolist()         # (the synchronisation: ws and u8 are no longer in use)
+            index = block[32:32 + 8 * k].view(torch.int64)
+            return index, DevicePosBatch.over(block[32 + 8 * n:], k, 48 * n, nbytes, len(cb))
 
     def stats(self):
         ms = (ctypes.c_float * 3)()

@@ -100,6 +100,67 @@ class PosBatch(object):
         return PosBatch(b"".join(parts), meta)
 
 
+class _DeviceTokens(object):
+    """what every part of a DevicePosBatch shares: `span` (uint8, on the device: the meta [rows,6] int64 at byte 0, the
+    text at byte text_at) and its host copy once someone has read it"""
+
+    def __init__(self, span, rows, text_at, text_bytes, ctg_len):
+        import torch
+        self.span, self.rows, self.text_at, self.text_bytes, self.ctg_len = span, int(rows), int(text_at), int(text_bytes), int(ctg_len)
+        self.meta_dev = span[:48 * self.rows].view(torch.int64).view(self.rows, 6)
+        self.text_dev = span[self.text_at:self.text_at + self.text_bytes]
+        self.host = None
+
+    def fetch(self):
+        """-> (text bytes as a uint8 array, meta [rows,6] int64): ONE page-locked copy, made once"""
+        if self.host is None:
+            import torch
+            nb = self.text_at + self.text_bytes
+            pin = torch.empty(max(nb, 1), dtype=torch.uint8, pin_memory=True)
+            pin[:nb].copy_(self.span[:nb], non_blocking=True)
+            torch.cuda.current_stream(self.span.device).synchronize()
+            h = pin.numpy()
+            self.host = (h[self.text_at:nb], h[:48 * self.rows].view(np.int64).reshape(self.rows, 6), pin)
+        return self.host[0], self.host[1]
+
+
+class DevicePosBatch(PosBatch):
+    """A PosBatch whose tokens were written in HBM (pileup.Pileup.call_columns): `.device` is callVar.device_tokens over
+    the text and the meta there (plus the length of the contig name, which every row shares), so the device VCF route
+    reads them in place.  The host copy -- what pieces(), [] and iteration give -- is fetched when it is first read, in
+    one page-locked copy of meta and text together, and shared by every part() cut from this batch."""
+
+    def __init__(self, tokens, first=0, count=None):
+        from .callVar import device_tokens
+        self._tokens = tokens
+        self._first, self._rows = int(first), int(tokens.rows - first if count is None else count)
+        self._starts = np.array([0, self._rows], dtype=np.int64)
+        self.meta_dev, self.text_dev = tokens.meta_dev, tokens.text_dev
+        self.device = device_tokens(tokens.text_dev, tokens.meta_dev, self._first)
+        self.device["longest"] = tokens.ctg_len
+
+    @staticmethod
+    def over(span, rows, text_at, text_bytes, ctg_len):
+        """the batch of all `rows` rows of `span`: the meta at byte 0, text_bytes of text at byte text_at, a contig name
+        of ctg_len bytes"""
+        return DevicePosBatch(_DeviceTokens(span, rows, text_at, text_bytes, ctg_len))
+
+    @property
+    def fetched(self):
+        """whether the host copy exists"""
+        return self._tokens.host is not None
+
+    @property
+    def _pieces(self):
+        buf, meta = self._tokens.fetch()
+        return [(buf, meta[self._first:self._first + self._rows])]
+
+    def part(self, first, count):
+        """rows [first, first + count) of this batch: the same bytes in HBM, meta from that row on"""
+        count = max(0, min(int(count), self._rows - int(first)))
+        return DevicePosBatch(self._tokens, self._first + int(first), count)
+
+
 class _GzipFile(object):
     """A gzip file inflated by the library's own DEFLATE decoder (csrc/cv_inflate.cpp, ~2x the rate of `gzip -dc`, no
     child process, no pipe), for regular files: the file is memory-mapped, every member's header is skipped by hand

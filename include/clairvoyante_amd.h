@@ -723,6 +723,38 @@ int cv_tensor_rows_text_dev(const char *ctg, int64_t ctg_len, const int64_t *cen
                             int64_t *off_dev, uint8_t *status_dev, char *text_dev, int64_t text_cap,
                             void *workspace, int64_t workspace_bytes, void *stream);
 
+/* callVarBam's columns written in HBM (csrc/cv_callcols_dev.hip, cv_callcols_core.hpp): which of the n candidate centres
+ * give a row for the call loop, and the tokens of those rows.  Centre i (1-based, ri = centre - 1 - ref_first inside
+ * the reference bytes ref[0, ref_len) whose first byte is 0-based position ref_first >= 0) is kept iff touched[i], ri - 16
+ * >= 0, ri < ref_len and ref[ri], with a..z mapped to A..Z, is one of A, C, G, T.  For the k kept centres, in ascending
+ * order of i (the compaction is stable):
+ *   index [k] int64   i of the row
+ *   text              the contig name, then the k coordinates ("%d", no separator), then the k windows
+ *                     ref[ri - 16, min(ri + 17, ref_len)) with a..z mapped to A..Z and every other byte as it is -- 17 to 33
+ *                     bytes each -- end to end: the bytes of utils_v2.PosBatch.from_columns
+ *   meta [k,6] int64  offset and length of the contig name, the coordinate and the window of the row inside text
+ *   info [4] int64    {k, bytes of text, n, 0}: k and the bytes are all a caller has to fetch
+ * text_cap must be at least ctg_len + CV_CALL_COLUMNS_ROW_TEXT n (there is no sizing pass); nothing behind info[1] bytes
+ * of text or behind row k of index / meta is written.  ctg is host memory, at most CV_CALL_COLUMNS_MAX_CTG bytes; the
+ * centres 4-byte, index / meta / info 8-byte, the workspace 256-byte aligned; at most 2^27 centres.  A null or misaligned
+ * pointer, a capacity below the bound or a negative ref_first returns 1.  Asynchronous on `stream`: no allocation, no
+ * synchronisation, no host round trip.
+ * cv_pileup_call_columns: the same behind cv_pileup_finish(touched_dev) for the handle's own centres and reference.
+ * cv_call_columns_host_form: the same core on the CPU over HOST pointers (tests hold the kernels to it).            */
+#define CV_CALL_COLUMNS_MAX_CTG 1024
+#define CV_CALL_COLUMNS_ROW_TEXT 43
+int cv_call_columns_workspace(int64_t n, int64_t *bytes);
+int cv_call_columns_dev(const char *ctg, int64_t ctg_len, const int32_t *centres_dev, const uint8_t *touched_dev, int64_t n,
+                        const uint8_t *ref_dev, int64_t ref_first, int64_t ref_len, int64_t *index_dev, int64_t *meta_dev,
+                        char *text_dev, int64_t text_cap, int64_t *info_dev, void *workspace, int64_t workspace_bytes,
+                        void *stream);
+int cv_pileup_call_columns(const cv_pileup *p, const char *ctg, int64_t ctg_len, const uint8_t *touched_dev, int64_t *index_dev,
+                           int64_t *meta_dev, char *text_dev, int64_t text_cap, int64_t *info_dev, void *workspace,
+                           int64_t workspace_bytes, void *stream);
+int cv_call_columns_host_form(const char *ctg, int64_t ctg_len, const int32_t *centres, const uint8_t *touched, int64_t n,
+                              const uint8_t *ref, int64_t ref_first, int64_t ref_len, int64_t *index, int64_t *meta, char *text,
+                              int64_t text_cap, int64_t *info);
+
 /* ---- native `samtools view` (optional producer, host only) ------------------------------------
  * The text of `samtools view -F <exclude_flags> BAM CTG[:S-E]` (CreateTensor.py:128-130,
  * ExtractVariantCandidates.py:112-114) without the external process: BGZF blocks inflated by `threads`
