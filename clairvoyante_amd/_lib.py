@@ -90,6 +90,8 @@ _SIGS = {
                                            ctypes.c_void_p]),
     "cv_text_gather_tokens": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                              ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "cv_text_find_newline_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
     # the labelled training set on the device (csrc/cv_trainset.hip)
     "cv_trainset_tokens_workspace": (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     "cv_trainset_tokens": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,

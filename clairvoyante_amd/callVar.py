@@ -582,6 +582,70 @@ def tensor_files(tensor_fn):
 SHARD_BLOCK_LINES = int(os.environ.get("CV_SHARD_BLOCK_LINES", "16384"))
 
 
+# The `range` route of a single file under several ranks (utils_v2.shard_span): rank r reads only the byte range -- of a
+# BGZF file: the members -- that holds its lines.  Whether it is the default of a form ("text": plain text, "bgzf") follows
+# from profiles/r18/sharded_reader.txt by the rule of CV_CALL_COLUMNS: ahead of the `lines` route in every run of every
+# rung at 2 and at 4 ranks, or opt-in (CV_SHARD=range).  When it is the default it applies from a SHARE (file size // ranks)
+# of the floor of the form upwards (TEXT_DEVICE_MIN_BYTES[0], BGZF_DEVICE_MIN_BYTES): the floors stand for fixed costs of
+# the device reader, which every process pays for itself.  That reasoning has NOT been measured under ranks.
+# Measured (1, 2, 4 processes on ONE GPU, the whole command per run): BGZF is ahead in every run at 1 M rows (2.7-3.0 s
+# against 5.1-5.9 s with 2 ranks, 3.0-4.0 s against 5.9-6.5 s with 4) and in the medians at 65 536 and 262 144 rows, where
+# its slowest run misses the fastest `lines` run by 0.3-21 %; plain text is within noise at every rung.  Both stay opt-in.
+SHARD_RANGE_DEFAULT = {"text": False, "bgzf": False}
+_shard_counts = {"lines": 0, "range": 0}
+
+
+def shard_counts():
+    """how often TestSharded took each route in this process: {"lines": .., "range": ..}"""
+    return dict(_shard_counts)
+
+
+def _shard_form(files):
+    """"text" / "bgzf" when --tensor_fn is ONE regular file the ownership rule covers, None otherwise (a list of files,
+    PIPE, a FIFO, ordinary gzip and the other formats `gzip -fdc` decodes, CV_TEXT=stream)"""
+    from . import utils_v2
+    if len(files) != 1 or files[0] == "PIPE" or not os.path.isfile(files[0]) or os.environ.get("CV_TEXT") == "stream":
+        return None
+    if utils_v2.is_compressed(files[0]):
+        return "bgzf" if utils_v2.is_bgzf(files[0]) else None
+    return "text"
+
+
+def shard_route(tensor_fn, ws):
+    """How `ws` ranks split --tensor_fn: "lines" (every rank reads the whole input and parses its blocks of lines; a list
+    of files: file k by rank k % ws) or "range" (ONE plain-text or BGZF file, every rank reads only its byte range).
+    CV_SHARD=lines|range forces a side -- `range` over an input the rule does not cover is an error --; unset, the input
+    decides (SHARD_RANGE_DEFAULT and the floors, above)."""
+    forced = os.environ.get("CV_SHARD")
+    if forced and forced not in ("lines", "range"):
+        raise ValueError("CV_SHARD must be 'lines' or 'range', got %r" % forced)
+    files = tensor_files(tensor_fn)
+    form = _shard_form(files)
+    if forced == "range":
+        if form is None:
+            raise ValueError("CV_SHARD=range needs ONE regular tensor file that is plain text or BGZF, got %r" % tensor_fn)
+        return "range"
+    if forced == "lines" or form is None or not SHARD_RANGE_DEFAULT[form]:
+        return "lines"
+    floor = TEXT_DEVICE_MIN_BYTES[0] if form == "text" else BGZF_DEVICE_MIN_BYTES
+    return "range" if floor is not None and os.path.getsize(files[0]) // ws >= max(floor, 1) else "lines"
+
+
+def range_batches(utils, tensor_fn, rank, ws, device, keep_device=False, batch=65536):
+    """the (endFlag, c, X, pos) batches of the lines rank `rank` of `ws` owns of ONE file: the ranged device reader, or the
+    ranged host reader under CV_TEXT_PARSE=host and without a GPU"""
+    forced = os.environ.get("CV_TEXT_PARSE")
+    if forced and forced not in ("host", "device"):
+        raise ValueError("CV_TEXT_PARSE must be 'host' or 'device', got %r" % forced)
+    on_device = forced != "host" and utils._gpu_present()
+    side = "device" if on_device else "host"
+    utils.text_parse_counts[side] += 1
+    logging.info("Text tensors are parsed on the %s (rank %d reads its range of %s)" % (side, rank, tensor_fn))
+    if on_device:
+        return utils.GetTensorDevice(tensor_fn, batch, device, log=False, keep_device=keep_device, part=(rank, ws))
+    return utils.GetTensor(tensor_fn, batch, log=False, part=(rank, ws))
+
+
 def merge_fragments(call_fn, ws, out_fh):
     """Rank 0: append the per-rank record fragments to the VCF in input order.  Rank r wrote CALL.rank<r> (its
     records, block after block) and CALL.rank<r>.idx (one line per block it owns: "<block> <bytes>"); block k
@@ -615,7 +679,8 @@ def TestSharded(args, m, utils, rank, ws):
     independent (v3.py:54-138 has no cross-candidate state), so the ranks split the INPUT LINES block-cyclically,
     every rank calls its blocks with its own replica of the weights -- no collective on the data path -- and
     rank 0 joins the per-rank record fragments in input order: the VCF is byte-identical to the single-process
-    one."""
+    one.  On the `range` route (shard_route) a rank does not even read the lines of the others: one plain-text or BGZF
+    file is split by byte ranges and rank r's share is block r."""
     import torch
     import torch.distributed as dist
     # the fragments are files next to --call_fn that rank 0 reads back: one node, or a file system all ranks share
@@ -623,6 +688,9 @@ def TestSharded(args, m, utils, rank, ws):
         logging.warning("callVar under %d ranks on several nodes: --call_fn must lie on a file system every rank shares" % ws)
     logging.info("Calling variants (rank %d of %d) ..." % (rank, ws))
     predictStart = time.time()
+    files = tensor_files(args.tensor_fn)
+    route = shard_route(args.tensor_fn, ws)         # (a mistyped CV_SHARD ends the run here, before any file exists)
+    _shard_counts[route] += 1
     frag_fn = "%s.rank%d" % (args.call_fn, rank)
     frag = open(frag_fn, "wb")
     index = []
@@ -630,15 +698,21 @@ def TestSharded(args, m, utils, rank, ws):
     # "--tensor_fn a.gz,b.gz,...": one file per chunk, file k -> rank k % ws (each rank inflates only its own files);
     # a single file: its LINES are split block-cyclically (every rank inflates the whole stream -- the job is then
     # capped by one core's gzip rate whatever the number of GPUs)
-    files = tensor_files(args.tensor_fn)
-    if len(files) == 1 and ws > 1 and rank == 0 and utils.is_compressed(files[0]):
+    # ... unless the file is plain text or BGZF and takes the `range` route (shard_route): rank r then reads only the
+    # bytes (the BGZF members) that hold its share of the lines, and its whole share is block r
+    if route == "lines" and len(files) == 1 and ws > 1 and rank == 0 and utils.is_compressed(files[0]):
         logging.warning("callVar: ONE compressed tensor file under %d ranks -- every rank inflates the whole stream to find its "
                         "line blocks, so the job runs at one core's inflate rate (~0.35 M rows/s) whatever the number of GPUs. "
-                        "Give --tensor_fn a comma-separated list (one file per chunk of the genome; file k goes to rank k mod N) "
-                        "or uncompressed text to scale." % ws)
+                        "Rewrite the file as BGZF (python -m clairvoyante_amd.bgzf IN OUT), whose members the ranks can share "
+                        "(CV_SHARD=range), give --tensor_fn a comma-separated list (one file per chunk of the genome; file k "
+                        "goes to rank k mod N) or uncompressed text to scale." % ws)
 
     def batches():
-        if len(files) > 1:           # this rank's files, compressed ones several at a time, batches as they complete
+        if route == "range":         # this rank's byte range of the one file: its batches are block `rank`
+            for _end, c, X, pos in range_batches(utils, files[0], rank, ws, m.device, keep_device=vcf_format_route() == "device"):
+                yield rank, c, X, pos
+            yield rank, None, None, None
+        elif len(files) > 1:         # this rank's files, compressed ones several at a time, batches as they complete
             for item in utils.GetTensorFiles(files, max(param.predictBatchSize, 16384), rank, ws, ordered=False):
                 yield item
         else:                        # one batch per owned block of lines

@@ -12,6 +12,8 @@
 //                       that token (<= 12 bytes) from LDS into an LDS row, the wave checks the row, subtracts matrix 0
 //                       and stores it with 16-byte stores
 //   tp_gather_rows      rows named by an index list, in list order, into a dense tensor (cv_text_gather_rows)
+//   tp_find_newline     the first newline at or behind a few given offsets (cv_text_find_newline_dev): where the lines
+//                       of ONE rank begin and end in text that several ranks share
 //
 // The slab may start at any address: the kernels read the 16-byte granules that CONTAIN the slab (so up to 15 bytes in
 // front of it and behind it, inside the granules the allocation owns anyway) and mask what lies outside.
@@ -41,6 +43,7 @@ constexpr int WAVE = 64;
 constexpr int PARSE_WAVES = 4;                               // waves (= lines in flight) per block of tp_parse_rows
 constexpr int LINE_LDS = CV_TEXT_LINE_CAP + 32;              // a line of the cap at any offset inside its first granule
 constexpr int PARSE_GRID = 2048;
+constexpr int FIND_GRID = 1024;                              // blocks of tp_find_newline: 4 MiB of text per step of the grid
 
 __device__ __forceinline__ uint32_t newline_mask(const uint4 v, int64_t g0, int64_t lo, int64_t hi)
 {
@@ -302,8 +305,49 @@ __global__ __launch_bounds__(256) void tp_token_copy(const uint8_t *text, const 
     }
 }
 
+// cv_text_find_newline_dev: for up to CV_TEXT_FIND_MAX offsets, the first '\n' at or behind each.  The waves walk the
+// text front to back in grid-sized steps of 16-byte granules; lane i of every wave watches query i: the query is OPEN for
+// the wave while its current answer lies behind the wave's first byte, and it is IN REACH when its offset lies in front
+// of the wave's last byte.  A wave without an open query leaves; one whose open queries are all out of reach steps on
+// without loading; the others load their granule and lower the answers of the queries a newline of theirs serves.
+struct find_queries {
+    int64_t from[CV_TEXT_FIND_MAX];
+};
+
+__global__ void tp_find_begin(int64_t *out, int k, int64_t len)
+{
+    if ((int)threadIdx.x < k) out[threadIdx.x] = len;
+}
+
+__global__ __launch_bounds__(TILE_THREADS) void tp_find_newline(const uint4 *gran, int shift, int64_t len, const find_queries q,
+                                                                 int k, int64_t *out)
+{
+    const int64_t lo = shift, hi = shift + len;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int64_t mine = lane < k ? q.from[lane] : len;                    // (the offset of the query this lane watches)
+    for (int64_t g0 = ((int64_t)blockIdx.x * TILE_THREADS + threadIdx.x) * 16; ; g0 += (int64_t)gridDim.x * TILE) {
+        const int64_t w0 = g0 - (int64_t)lane * 16 - shift;                // the wave's first byte, relative to the text
+        if (w0 >= len) break;                                              // (uniform over the wave)
+        bool open = false, reach = false;
+        if (lane < k) {
+            open = __atomic_load_n(&out[lane], __ATOMIC_RELAXED) > w0;
+            reach = open && mine < w0 + WAVE * 16;
+        }
+        if (!__any(open)) break;
+        if (!__any(reach) || g0 >= hi) continue;
+        const uint32_t m = newline_mask(gran[g0 >> 4], g0, lo, hi);
+        if (!m) continue;
+        const int64_t p0 = g0 - shift;                                     // the granule's first byte, relative to the text
+        for (int i = 0; i < k; i++) {
+            const int64_t d = q.from[i] - p0;
+            const uint32_t mm = d <= 0 ? m : (d >= 16 ? 0u : m & (0xffffu << d));
+            if (mm) atomicMin((unsigned long long *)&out[i], (unsigned long long)(p0 + __ffs(mm) - 1));
+        }
+    }
+}
+
 struct ws_layout {
-    int64_t ntiles_max;          // tiles of a slab of `len` bytes at the worst offset inside its first granule
+    int64_t ntiles_max;         // tiles of a slab of `len` bytes at the worst offset inside its first granule
     size_t tile_cnt, tile_first, line_end, scan_tmp, scan_bytes, total;
 };
 
@@ -402,6 +446,33 @@ extern "C" int cv_text_gather_rows(const float *x_dev, const int64_t *index_dev,
     const int64_t blocks = (nrows * (NV / 4) + 255) / 256;
     hipLaunchKernelGGL(tp_gather_rows, dim3((int)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
                        (const float4 *)x_dev, index_dev, nrows, (float4 *)out_dev);
+    TP_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int cv_text_find_newline_dev(const char *text_dev, int64_t len, const int64_t *from, int k, int64_t *out_dev, void *stream)
+{
+    if (k < 0 || k > CV_TEXT_FIND_MAX || len < 0) {
+        cv_set_error("cv_text_find_newline_dev: %d queries / len %lld out of range (0 .. %d queries)", k, (long long)len, CV_TEXT_FIND_MAX);
+        return 1;
+    }
+    if (k == 0) return 0;
+    if (!from || !out_dev || (!text_dev && len > 0)) { cv_set_error("cv_text_find_newline_dev: null argument"); return 1; }
+    if ((uintptr_t)out_dev & 7) { cv_set_error("cv_text_find_newline_dev: out_dev must be 8-byte aligned"); return 1; }
+    hipStream_t st = (hipStream_t)stream;
+    find_queries q;
+    int64_t first = len;
+    for (int i = 0; i < CV_TEXT_FIND_MAX; i++) {
+        q.from[i] = i < k ? (from[i] < 0 ? 0 : from[i]) : len;
+        if (q.from[i] < first) first = q.from[i];
+    }
+    hipLaunchKernelGGL(tp_find_begin, dim3(1), dim3(CV_TEXT_FIND_MAX), 0, st, out_dev, k, len);
+    if (first < len) {
+        const int shift = (int)((uintptr_t)text_dev & 15);
+        const int64_t ntiles = (shift + len + TILE - 1) / TILE;
+        hipLaunchKernelGGL(tp_find_newline, dim3((int)(ntiles < FIND_GRID ? ntiles : FIND_GRID)), dim3(TILE_THREADS), 0, st,
+                           (const uint4 *)(text_dev - shift), shift, len, q, k, out_dev);
+    }
     TP_HIP(hipGetLastError());
     return 0;
 }

@@ -416,6 +416,84 @@ def GetTensorBlocks(tensor_fn, block_lines, rank, ws):
         spans.close()
 
 
+# ---- one file under several ranks: which rank owns which line (callVar's `range` route) --------------------------------
+# A text of n bytes and cut points B[0] = 0 <= B[1] <= ... <= B[ws] = n.  Rank r owns the lines whose FIRST byte lies in
+# [s_r, e_r):  s_0 = 0;  s_r = 1 + the offset of the first '\n' at or after B[r] - 1 (n when there is none);  e_r = s_(r+1),
+# e_(ws-1) = n.  s is monotone in B, so the ranges tile [0, n): every line has exactly one owner, a line that starts at
+# B[r] belongs to rank r, a rank whose range holds no line start owns nothing, and a last line without newline goes to
+# the rank whose range holds its first byte.  Nobody needs to know anything about the text but the newline behind a cut.
+def shard_cuts(size, ws):
+    """cut points of a plain-text file of `size` bytes: B[r] = size * r // ws"""
+    return [size * r // ws for r in range(ws + 1)]
+
+
+def bgzf_shard_cuts(table, total, filesize, ws):
+    """cut points of a BGZF file from its member table alone (bgzf_scan; nothing is inflated to plan): B[r] = the running
+    inflated offset of the first member whose DEFLATE data starts at or above filesize * r // ws; `total` behind the last"""
+    at = np.searchsorted(table[:, 0], [filesize * r // ws for r in range(ws + 1)], side="left")
+    return [int(table[i, 2]) if i < len(table) else int(total) for i in at]
+
+
+def shard_span(find, n, cuts, rank):
+    """-> (s_r, e_r) of the rule above.  find(j), 0 <= j < n: offset of the first '\\n' at or after j, n if there is none"""
+    def start(r):
+        if r == 0:
+            return 0
+        if r >= len(cuts) - 1 or n == 0:
+            return n
+        j = find(min(max(cuts[r] - 1, 0), n - 1))
+        return n if j >= n else j + 1
+    return start(rank), start(rank + 1)
+
+
+def shard_text(text, cuts, rank):
+    """the rule over bytes that are all there: -> the part of `text` rank `rank` owns (whole lines, in order)"""
+    def find(j):
+        k = text.find(b"\n", j)
+        return len(text) if k < 0 else k
+    s, e = shard_span(find, len(text), cuts, rank)
+    return text[s:e]
+
+
+def _file_find_newline(fd, start, size):
+    """offset of the first '\\n' of the open file at or after `start`, `size` if there is none (reads growing windows)"""
+    w = 4096
+    while start < size:
+        chunk = os.pread(fd, min(w, size - start), start)
+        if not chunk:
+            break
+        k = chunk.find(b"\n")
+        if k >= 0:
+            return start + k
+        start += len(chunk)
+        w = min(w * 8, 1 << 24)
+    return size
+
+
+def _map_plain_range(tensor_fn, part):
+    """part = (rank, ws): -> read-only uint8 array over the lines of the plain-text file `tensor_fn` that rank owns
+    (shard_cuts, shard_span).  The two newlines are looked for with small reads at the cuts; only [s_r, e_r) is mapped
+    (from the page that holds s_r).  ValueError for what _map_plain_text would not map: the rule needs a regular file."""
+    import mmap
+    import stat
+    rank, ws = part
+    if tensor_fn == "PIPE" or os.environ.get("CV_TEXT") == "stream":
+        raise ValueError("a byte range of %s cannot be read: part= needs a regular plain-text or BGZF file" % tensor_fn)
+    with open(tensor_fn, "rb") as fh:
+        st = os.fstat(fh.fileno())
+        if not stat.S_ISREG(st.st_mode) or _gzip_would_decode(fh.read(4)):
+            raise ValueError("a byte range of %s cannot be read: part= needs a regular plain-text or BGZF file" % tensor_fn)
+        size = st.st_size
+        s, e = shard_span(lambda j: _file_find_newline(fh.fileno(), j, size), size, shard_cuts(size, ws), rank)
+        if s >= e:
+            return np.zeros(0, dtype=np.uint8)
+        lo = s - s % mmap.ALLOCATIONGRANULARITY
+        mm = mmap.mmap(fh.fileno(), e - lo, access=mmap.ACCESS_READ, offset=lo)
+    if hasattr(mm, "madvise") and hasattr(mmap, "MADV_SEQUENTIAL"):
+        mm.madvise(mmap.MADV_SEQUENTIAL)
+    return np.frombuffer(mm, dtype=np.uint8)[s - lo:]
+
+
 def _default_readers(nfiles):
     """concurrent file readers of one process: a compressed tensor file arrives at ONE core's inflate rate (~0.15 M
     rows/s), so several files are inflated side by side (each `gzip -dc` is its own process) while the parser threads
@@ -616,14 +694,17 @@ def _flagged(log):
     return done
 
 
-def GetTensor(tensor_fn, num, log=True):
+def GetTensor(tensor_fn, num, log=True, part=None):
     """Generator over batches of `num` candidates: yields (endFlag, c, X, pos) exactly like
     utils_v2.py:23-59 -- X [c,33,4,4] fp32 with matrices 1..3 minus matrix 0, rows whose
     centre base is not ACGT dropped, a final (possibly empty) batch with endFlag 1.  Over a memory-mapped plain-text
     file the parser threads read the lines where the page cache holds them (no pipe, no copies; cv_parse_tensor_text
-    sees the whole rest of the file and sizes its own window); everything else arrives in 16 MiB reads of the stream."""
+    sees the whole rest of the file and sizes its own window); everything else arrives in 16 MiB reads of the stream.
+    part = (rank, ws): the batches of the lines rank `rank` of `ws` owns of ONE plain-text or BGZF file (shard_span);
+    of a BGZF file the host then inflates the members of that range only (_bgzf_range_spans)."""
     batch, done = _RowBatch(num), _flagged(log)
-    spans = _text_spans(tensor_fn)
+    bgzf = _map_bgzf(tensor_fn) if part is not None else None
+    spans = _text_spans(tensor_fn, part=part) if bgzf is None else _bgzf_range_spans(_BgzfRange(tensor_fn, bgzf, part, 1 << 24))
     try:
         for span in spans:
             for full in batch.fill(span):
@@ -773,6 +854,7 @@ class _BgzfSlab(object):
         self.table[:, 2] -= table[0, 2]
         self.n = int(self.table[-1, 2] + (self.table[-1, 3] >> 32))
         self.last, self.fn = False, fn
+        self.queries = ()                   # offsets into the inflated text behind which a ranged reader wants the first newline
 
     def inflate_member(self, i):
         """member i inflated on the host and checked (cv_inflate_raw, cv_crc32_ieee) -> uint8 array; CvError in the words
@@ -790,19 +872,23 @@ class _BgzfSlab(object):
         return out[:isize]
 
 
-def _bgzf_slabs(tensor_fn, data, table, num):
-    """the members of a BGZF file grouped into slabs of about `num` rows of INFLATED text (_slab_bytes of the first
-    line, which the host inflates one member for)"""
+def _bgzf_first_line(data, table):
+    """length of the first line of the first non-empty member among the first 64 of `table` (the host inflates that
+    member; 0 when it has no newline or does not inflate): what the slabs are sized from"""
     import zlib
-    first_line = 0
     for off, clen, _at, packed in table[:64]:
         if packed >> 32:
             try:
-                first_line = zlib.decompressobj(-15).decompress(bytes(data[off:off + clen])).find(b"\n") + 1
+                return zlib.decompressobj(-15).decompress(bytes(data[off:off + clen])).find(b"\n") + 1
             except zlib.error:
-                pass
-            break
-    want = _slab_bytes(first_line, num)
+                return 0
+    return 0
+
+
+def _bgzf_slabs(tensor_fn, data, table, num):
+    """the members of a BGZF file grouped into slabs of about `num` rows of INFLATED text (_slab_bytes of the first
+    line, which the host inflates one member for)"""
+    want = _slab_bytes(_bgzf_first_line(data, table), num)
     ends = table[:, 2] + (table[:, 3] >> 32)              # inflated bytes up to and including each member
     lo, slab = 0, None
     while lo < len(table):
@@ -813,6 +899,107 @@ def _bgzf_slabs(tensor_fn, data, table, num):
         lo = hi
     slab.last = True
     yield slab
+
+
+class _BgzfRange(object):
+    """The members of a BGZF file that ONE rank of several reads (part = (rank, ws); bgzf_shard_cuts, shard_span), as
+    slabs handed out one by one: next() -> the next _BgzfSlab or None; place(slab, found) -> which bytes of it the rank
+    owns, from the newlines the reader found for the slab's `queries`.  What comes next depends on what was found, so
+    the reader calls place() for a slab before it asks for the one behind it.
+      in front    the member that holds byte B[r] - 1 (the nearest non-empty one before the range): the newline at or
+                  after that byte ends the last line of the rank before; until it is found the rank owns nothing;
+      the range   members up to the one that holds byte B[r+1] - 1, in slabs of about `want` inflated bytes;
+      behind      while the newline at or after B[r+1] - 1 has not been found: 1, 2, 4, ... further members.
+    Empty members may sit anywhere: a slab is extended until it holds a byte, and the empty members that end the file
+    (the EOF marker) are never inflated.  A slab's `queries` are offsets into ITS text; `cut` says that the last of them
+    looks for the end of the range; `last`: no text follows (the reader ends a last line without newline)."""
+
+    def __init__(self, tensor_fn, bgzf, part, want):
+        self.fn, (self.data, self.table, total) = tensor_fn, bgzf
+        rank, ws = part
+        cuts = bgzf_shard_cuts(self.table, total, len(self.data), ws)
+        self.ends = self.table[:, 2] + (self.table[:, 3] >> 32)           # inflated bytes up to and including each member
+        self.total = int(total)
+        self.qs = max(cuts[rank] - 1, 0) if rank > 0 else None            # the newline at or after it is in front of s_r ...
+        self.qe = max(cuts[rank + 1] - 1, 0) if rank + 1 < ws else None   # ... and e_r: absolute inflated offsets
+        self.seeking, self.follow = self.qs is not None, 1
+        self.at = self.hi = 0                                             # the next member to hand out; the end of the range
+        self.done = self.total == 0 or (rank > 0 and cuts[rank] == cuts[rank + 1])      # (s_r == e_r whatever the text)
+        if self.done:
+            return
+        self.at = self._member_of(self.qs) if self.seeking else 0
+        self.hi = self._member_of(self.qe if self.qe is not None else self.total - 1) + 1
+        first_line = _bgzf_first_line(self.data, self.table[self.at:]) if callable(want) else 0
+        self.want = max(1, want(first_line) if callable(want) else want)
+
+    def _member_of(self, x):
+        """the member that holds byte x of the inflated text (never an empty one)"""
+        return int(np.searchsorted(self.ends, x, side="right"))
+
+    def next(self):
+        table, lo = self.table, self.at
+        before = int(self.ends[lo - 1]) if lo else 0
+        if self.done or before >= self.total:
+            return None
+        if lo < self.hi:
+            hi = min(max(int(np.searchsorted(self.ends, before + self.want, side="left")) + 1, lo + 1), self.hi)
+        else:
+            hi, self.follow = lo + self.follow, self.follow * 2
+        hi = min(hi, len(table))
+        while self.ends[hi - 1] == before:                                # only empty members so far
+            hi += 1
+        slab = _BgzfSlab(self.data, table[lo:hi], self.fn)
+        slab.last = int(self.ends[hi - 1]) >= self.total
+        base = int(table[lo, 2])
+        slab.cut = self.qe is not None and hi >= self.hi
+        slab.queries = ([max(self.qs - base, 0)] if self.seeking else []) + ([max(self.qe - base, 0)] if slab.cut else [])
+        self.at = hi
+        return slab
+
+    def place(self, slab, found):
+        """found[i]: offset of the first newline at or after slab.queries[i] in the slab's text, slab.n if there is none
+        -> (skip, stop): the rank owns [skip, stop) of the slab's text; a `last` slab's text counts the newline the reader
+        puts behind it"""
+        whole = slab.n + (1 if slab.last else 0)
+        skip, stop = 0, whole
+        found = [int(j) for j in found]
+        if self.seeking:
+            if found[0] < slab.n:
+                skip, self.seeking = found[0] + 1, False
+            else:
+                skip = whole
+        if slab.cut and found[-1] < slab.n:
+            stop, self.done = found[-1] + 1, True
+        if slab.last:
+            self.done = True
+        return skip, max(skip, stop)
+
+
+def _bgzf_range_spans(plan):
+    """the lines a rank owns of a BGZF file as spans of whole lines, inflated by the host (GetTensor with part=): the
+    reader of _BgzfRange without a GPU"""
+    carry = []
+    while True:
+        slab = plan.next()
+        if slab is None:
+            break
+        parts = [slab.inflate_member(i) for i in range(len(slab.table)) if slab.table[i, 3] >> 32]
+        if slab.last:
+            parts.append(np.array([10], dtype=np.uint8))          # (a last line without newline gets one; after one, a blank line)
+        text = parts[0] if len(parts) == 1 else np.concatenate(parts)
+        found = []
+        for q in slab.queries:
+            j = _first_newline(text[:slab.n], q)
+            found.append(slab.n if j < 0 else j)
+        skip, stop = plan.place(slab, found)
+        text = text[skip:stop]
+        k = _last_newline(text)
+        if k < 0:
+            if len(text):
+                carry.append(text)
+            continue
+        yield np.concatenate(carry + [text[:k + 1]]) if carry else text[:k + 1]
+        carry = [text[k + 1:]] if k + 1 < len(text) else []
 
 
 bgzf_member_counts = {"device": 0, "host": 0}       # members GetTensorDevice inflated on the device / handed to the host
@@ -1031,7 +1218,7 @@ def _slab_bytes(first_line, num):
     return min(max(num, 1) * max(first_line, 64), _PinnedPool.MAX_BYTES)     # (what a page-locked staging buffer holds)
 
 
-def _text_spans(tensor_fn, want_bytes=None):
+def _text_spans(tensor_fn, want_bytes=None, part=None):
     """The input as spans of whole lines: uint8 arrays that end in '\n'.  The one place that turns a tensor file into
     lines, and the only one that opens and closes its stream.
       a plain regular file (_map_plain_text): views of the memory map, no copy of the text;
@@ -1041,11 +1228,12 @@ def _text_spans(tensor_fn, want_bytes=None):
     A last line without newline gets one: on the map that line alone is copied and follows as a span of its own.
     want_bytes: None = as the source gives them (the whole map -- cv_parse_tensor_text sizes its own window --, 16 MiB
     of the stream); a number of bytes; or a function of the first line's length (GetTensorDevice: `num` rows' worth).
-    A span is cut at the last newline inside want_bytes, a line longer than that is a span of its own."""
+    A span is cut at the last newline inside want_bytes, a line longer than that is a span of its own.
+    part = (rank, ws): only the lines of a plain-text file that rank owns (_map_plain_range)."""
     def size_for(first_line):
         return want_bytes(first_line) if callable(want_bytes) else want_bytes
 
-    data = _map_plain_text(tensor_fn)
+    data = _map_plain_text(tensor_fn) if part is None else _map_plain_range(tensor_fn, part)
     if data is not None:
         n, off = _last_newline(data) + 1, 0          # the whole lines end here
         size = size_for(_first_newline(data, 0) + 1) if want_bytes is not None and n else n
@@ -1198,31 +1386,54 @@ class _TextSlabDevice(object):
             text = torch.empty(end + 32, dtype=torch.uint8, device=self.device)
             comp = torch.empty(len(slab.comp) + 8, dtype=torch.uint8, device=self.device)
             table = torch.empty((m, 4), dtype=torch.int64, device=self.device)
-            status = torch.zeros(m, dtype=torch.uint8, device=self.device)
+            # member statuses | the newlines a ranged reader asks for (slab.queries): they come back in one copy
+            k, mpad = len(slab.queries), (m + 7) & ~7
+            back = torch.zeros(mpad + 8 * k, dtype=torch.uint8, device=self.device)
+            status = back[:m]
             stage = [self._to_device(comp[:len(slab.comp)], slab.comp), self._to_device(table.view(torch.uint8).reshape(-1), slab.table.view(np.uint8).reshape(-1))]
             _lib.check(self.lib.cv_inflate_bgzf_dev(ctypes.c_void_p(comp.data_ptr()), ctypes.c_void_p(table.data_ptr()), m,
                                                     ctypes.c_void_p(text.data_ptr() + head), slab.n, ctypes.c_void_p(status.data_ptr()),
                                                     ctypes.c_void_p(self.copy_stream.cuda_stream)))
+            if k:
+                self._find_newlines(text, head, slab, back.data_ptr() + mpad, self.copy_stream)
             if slab.last:
                 text[end - 1:end].fill_(10)                          # (a last line without newline gets one; after one, a blank line)
-            host = torch.empty(m, dtype=torch.uint8, pin_memory=True)
-            host.copy_(status, non_blocking=True)
+            host = torch.empty(mpad + 8 * k, dtype=torch.uint8, pin_memory=True)
+            host.copy_(back, non_blocking=True)
             ev = torch.cuda.Event(); ev.record(self.copy_stream)
-        return (text, end, ev, (stage, comp, table, status, host)), end
+        return (text, end, ev, (stage, comp, table, back, host)), end
+
+    def _find_newlines(self, text, head, slab, out_ptr, stream):
+        """enqueues cv_text_find_newline_dev for slab.queries over the slab's inflated text; int64 results at out_ptr"""
+        q = (ctypes.c_int64 * len(slab.queries))(*slab.queries)
+        _lib.check(self.lib.cv_text_find_newline_dev(ctypes.c_void_p(text.data_ptr() + head), slab.n, q, len(slab.queries),
+                                                     ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream.cuda_stream)))
 
     def settle(self, up, slab, head):
-        """waits for the slab's inflate; members the device left to the host are inflated there and copied into place"""
+        """waits for the slab's inflate; members the device left to the host are inflated there and copied into place.
+        -> the newlines found for slab.queries (a ranged reader's; looked for again when the host had to fill text in)"""
         torch = self.torch
-        text, _end, ev, (_stage, _comp, _table, _status, host) = up
+        text, _end, ev, (_stage, _comp, _table, back, host) = up
         ev.synchronize()
-        todo = np.flatnonzero(host.numpy() != 1)                     # CV_BGZF_OK
-        bgzf_member_counts["device"] += len(slab.table) - len(todo)
+        m = len(slab.table)
+        todo = np.flatnonzero(host.numpy()[:m] != 1)                 # CV_BGZF_OK
+        bgzf_member_counts["device"] += m - len(todo)
         bgzf_member_counts["host"] += len(todo)
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             for i in todo:
                 out = slab.inflate_member(int(i))
                 at = head + int(slab.table[i, 2])
                 text[at:at + len(out)].copy_(torch.from_numpy(out))
+            if len(todo) and slab.queries:
+                mpad = (m + 7) & ~7
+                self._find_newlines(text, head, slab, back.data_ptr() + mpad, self.stream)
+                host[mpad:].copy_(back[mpad:], non_blocking=True)
+                self.stream.synchronize()
+        return host.numpy()[(m + 7) & ~7:].view(np.int64)
+
+    def cut(self, up, end):
+        """-> the handle of the same text, ending at byte `end` (a ranged reader: the end of the lines it owns)"""
+        return (up[0], end) + tuple(up[2:])
 
     # -- a slab of an ordinary gzip file: find block starts, count, check the chain, write symbols, resolve, CRC -- all on
     # the copy stream; the host reads back the found starts, the counts and the final statuses
@@ -1468,7 +1679,7 @@ def _closing(items, dev):
 BGZF_HEADROOM = 1 << 16        # free bytes in front of a BGZF slab's inflated text: room for the line the slab before left unfinished
 
 
-def GetTensorDevice(tensor_fn, num, device, log=True, keep_device=False, gzip_device=True):
+def GetTensorDevice(tensor_fn, num, device, log=True, keep_device=False, gzip_device=True, part=None):
     """GetTensor with the rows parsed on the GPU: generator of (endFlag, c, X_dev, pos), X_dev a [c,33,4,4] fp32 torch
     tensor on `device` (the bits GetTensor gives), pos a PosBatch over the host copy of the text.  The input is cut
     into slabs of whole lines (about `num` rows each, from the first line's length), slab k + 1 is copied to the device
@@ -1485,28 +1696,39 @@ def GetTensorDevice(tensor_fn, num, device, log=True, keep_device=False, gzip_de
     whatever the chain of blocks gives, up to GZIP_TEXT_BYTES of text, and yields several batches).  gzip_device=False
     keeps such a file on the host inflate, in slabs of about `num` rows.
     keep_device: every batch's `pos` also says where its tokens lie in HBM (pos.device, for GetTrainingSetDevice), which
-    keeps the slab's text there for as long as the batch is held."""
+    keeps the slab's text there for as long as the batch is held.
+    part = (rank, ws): the batches of the lines rank `rank` of `ws` owns of ONE plain-text or BGZF file (shard_span),
+    in order -- callVar's `range` route.  Of plain text only that byte range is mapped, staged and uploaded.  Of a BGZF
+    file only the members of the range are uploaded and inflated, one member in front and as many behind as the last
+    line needs (_BgzfRange); where the rank's first and last line lie in that text the device says itself
+    (cv_text_find_newline_dev, its answers come back with the members' statuses), and the parser gets that range."""
     parse = _text_parser()
     cap = num + num // 8 + 64
     dev = _TextSlabDevice(device, cap)
     done, held = _flagged(log), None
     bgzf = _map_bgzf(tensor_fn) if os.environ.get("CV_TEXT") != "stream" else None
+    ranged = None
+    if part is not None:
+        if bgzf is not None:
+            ranged = _BgzfRange(tensor_fn, bgzf, part, lambda first_line: _slab_bytes(first_line, num))
+        gzip_device = False                  # (plain text, or _map_plain_range says what it is not)
     # (a stand-in for the device without the gzip inflate keeps the host stream)
     gz = _map_gzip(tensor_fn) if gzip_device and bgzf is None and os.environ.get("CV_TEXT") != "stream" and hasattr(dev, "inflate_gzip") else None
     if gz is not None:
         source = _gzip_slabs(tensor_fn, gz[0], gz[1], num, dev)
         upload = lambda slab: (slab.up, slab.end) if isinstance(slab, _GzipText) else (dev.upload(slab), len(slab))
     elif bgzf is None:
-        source = _text_spans(tensor_fn, lambda first_line: _slab_bytes(first_line, num))
+        source = _text_spans(tensor_fn, lambda first_line: _slab_bytes(first_line, num), part=part)
         upload = lambda slab: (dev.upload(slab), len(slab))
     else:
-        source = _bgzf_slabs(tensor_fn, bgzf[0], bgzf[1], num)
+        source = _bgzf_slabs(tensor_fn, bgzf[0], bgzf[1], num) if ranged is None else iter(ranged.next, None)
         upload = lambda slab: dev.upload_bgzf(slab, BGZF_HEADROOM)
 
     def batches():
         # (the inflate of slab k + 1 runs beside the staging of slab k; the gzip source works on the device itself, on
         # this thread, under the parse of the slab before)
-        slabs = _read_ahead(source, 2) if gz is None else source
+        # (a ranged BGZF reader decides what its next slab is from what it found in this one: nothing reads ahead of it)
+        slabs = _read_ahead(source, 2) if gz is None and ranged is None else source
         slab = next(slabs, None)
         up, end = upload(slab) if slab is not None else (None, 0)
         tail = None                                            # compressed: (handle, first byte, end) of the line the slab before left unfinished
@@ -1519,18 +1741,23 @@ def GetTensorDevice(tensor_fn, num, device, log=True, keep_device=False, gzip_de
                 tail = None
             if inflated:
                 if bgzf is not None:
-                    dev.settle(up, slab, BGZF_HEADROOM)
+                    found = dev.settle(up, slab, BGZF_HEADROOM)
                 start = BGZF_HEADROOM
+                if ranged is not None:                         # the lines of this rank: [skip, stop) of the slab's text
+                    skip, stop = ranged.place(slab, found)
+                    if start + stop < end:
+                        up, end = dev.cut(up, start + stop), start + stop
+                    start += skip                              # (in front of the first owned line there is no tail)
                 if tail is not None:
                     if tail[2] - tail[1] > start:              # one over-long line: more room in front
                         up, end = dev.grow(up, end, tail[2] - tail[1] - start), end + tail[2] - tail[1] - start
                         start = tail[2] - tail[1]
                     start -= tail[2] - tail[1]
                     dev.carry(tail[0], tail[1], tail[2], up, start)
-            job = dev.parse(up, start)
+            job = dev.parse(up, start) if start < end else None    # (a ranged reader may own nothing of a slab)
             nxt = next(slabs, None)                            # (its copy runs under the kernels of `slab`)
             nxt_up, nxt_end = upload(nxt) if nxt is not None else (None, 0)
-            while True:
+            while job is not None:
                 info, status, meta = dev.collect(job)
                 lines = int(info[1])
                 text_line_counts["host"] += int(info[3])

@@ -352,6 +352,16 @@ int cv_text_gather_rows(const float *x_dev, const int64_t *index_dev, int64_t nr
  * token lengths it already holds; a line that would not fit is left out.  Enqueued on `stream`.                       */
 int cv_text_gather_tokens(const char *text_dev, const int64_t *meta_dev, const int64_t *index_dev, int64_t nrows,
                           uint8_t *bytes_dev, int64_t bytes_cap, int64_t *meta_out_dev, void *stream);
+/* Where lines begin in text that exists only on the device (a reader that owns a byte range of a file several ranks
+ * share places the first and the last of its lines with it): for k offsets from[0 .. k) -- a HOST array, k at most
+ * CV_TEXT_FIND_MAX -- out_dev[i] = the smallest j >= from[i] with text_dev[j] == '\n', or len when there is none
+ * (also when from[i] >= len); a negative offset counts as 0.  text_dev may start at any address: the kernel reads the
+ * 16-byte granules that contain text_dev[0, len) and masks what lies outside, as cv_parse_tensor_text_dev does.  One scan
+ * serves all k queries (a vector atomic minimum per query and newline; a wave whose text lies behind every answer found
+ * so far leaves).  out_dev[k] int64 on the device, 8-byte aligned.  Enqueued on `stream`; neither allocates nor
+ * synchronises -- the caller brings out_dev back with whatever else it copies for the slab.                           */
+#define CV_TEXT_FIND_MAX 64
+int cv_text_find_newline_dev(const char *text_dev, int64_t len, const int64_t *from, int k, int64_t *out_dev, void *stream);
 
 /* BGZF (bgzip / htslib: independent gzip members of <= 64 KiB, the compressed size in the "BC" extra subfield).
  * cv_bgzf_scan walks the member headers of a whole file in memory, once: 0 = BGZF (*members, *inflated_bytes set; the
