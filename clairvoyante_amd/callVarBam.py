@@ -54,12 +54,18 @@ def CheckCmdExist(cmd):
 
 
 def truth_positions(args, ctgStart, ctgEnd):
-    """candidate sites from --vcf_fn: what GetTruth.py prints and CreateTensor.py then filters (:59-61)"""
+    """candidate sites from --vcf_fn: what GetTruth.py prints and CreateTensor.py then filters (:59-61); on the device route
+    of utils_v2.truth_tables (CV_TRUTH_TABLES=device) the positions come from its VCF pass, the same ones"""
     from .GetTruth import open_vcf, variant_rows
-    vcf = open_vcf(args.vcf_fn, args.ctgName, ctgStart, ctgEnd)
-    pos = [int(r.split()[1]) for r in variant_rows(vcf.stdout, args.ctgName, ctgStart, ctgEnd)]
-    vcf.stdout.close()
-    vcf.wait()
+    from . import utils_v2
+    pos = None
+    if utils_v2.truth_tables_route(vcf_fn=args.vcf_fn) == "device":       # the same pass that reads a truth VCF for the builders
+        pos = utils_v2.vcf_truth_positions(args.vcf_fn, args.ctgName, ctgStart, ctgEnd)
+    if pos is None:
+        vcf = open_vcf(args.vcf_fn, args.ctgName, ctgStart, ctgEnd)
+        pos = [int(r.split()[1]) for r in variant_rows(vcf.stdout, args.ctgName, ctgStart, ctgEnd)]
+        vcf.stdout.close()
+        vcf.wait()
     pos = [p for p in pos if (ctgStart is None or p >= ctgStart) and (ctgEnd is None or p <= ctgEnd)]
     return np.unique(np.asarray(pos, dtype=np.int64))
 

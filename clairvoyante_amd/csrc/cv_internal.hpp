@@ -263,3 +263,9 @@ int cv_dropout_tm(cv_model *m, const float *h4, float *d4, float *amask, int64_t
                   uint64_t step, int64_t cand0, hipStream_t st);
 int cv_tm_to_natural(const float *tm, int KB, int feat_per_pos_padded, int feat_per_pos, int npos,
                      int64_t n, float *dst, hipStream_t st);
+
+// the newline index of a slab of text in HBM (cv_textparse.hip): line_end[i] = offset of the newline that closes line
+// i < max_lines, in workspace_dev (256-byte aligned, cv_text_line_index_bytes); info_dev = {bytes consumed, lines, 0, 0}
+int cv_text_line_index_bytes(int64_t len, int64_t max_lines, size_t *bytes);
+int cv_text_line_index(const char *text_dev, int64_t len, int64_t max_lines, void *workspace_dev, int64_t *info_dev,
+                       const int64_t **line_end_dev, hipStream_t st);

@@ -21,6 +21,7 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include "../../include/clairvoyante_amd.h"
+#include "cv_internal.hpp"
 
 void cv_set_error(const char *fmt, ...);
 
@@ -370,6 +371,44 @@ int layout(int64_t len, int64_t max_lines, ws_layout *L)
 
 }  // namespace
 
+// The newline index of a slab, for every reader of text in HBM (declared in cv_internal.hpp): workspace_dev (256-byte
+// aligned, cv_text_line_index_bytes) receives line_end[i] = offset of the newline that closes line i < max_lines, info_dev
+// {bytes consumed, lines, 0, 0}.  Enqueued on st; allocates nothing.
+int cv_text_line_index_bytes(int64_t len, int64_t max_lines, size_t *bytes)
+{
+    ws_layout L;
+    if (layout(len, max_lines, &L)) return 1;
+    *bytes = L.total;
+    return 0;
+}
+
+int cv_text_line_index(const char *text_dev, int64_t len, int64_t max_lines, void *workspace_dev, int64_t *info_dev,
+                       const int64_t **line_end_dev, hipStream_t st)
+{
+    ws_layout L;
+    if (layout(len, max_lines, &L)) return 1;
+    char *ws = (char *)workspace_dev;
+    uint32_t *tile_cnt = (uint32_t *)(ws + L.tile_cnt), *tile_first = (uint32_t *)(ws + L.tile_first);
+    int64_t *line_end = (int64_t *)(ws + L.line_end);
+    const int shift = (int)((uintptr_t)text_dev & 15);
+    const uint4 *gran = (const uint4 *)(text_dev - shift);
+    // (the tile count of the worst offset: what the workspace and the scan were sized for; a tile behind the slab counts 0)
+    const int64_t ntiles = len > 0 && max_lines > 0 ? L.ntiles_max : 0;
+    if (ntiles > 0) {
+        const int grid = (int)(ntiles < INDEX_GRID ? ntiles : INDEX_GRID);
+        hipLaunchKernelGGL(tp_count_newlines, dim3(grid), dim3(TILE_THREADS), 0, st, gran, shift, len, ntiles, tile_cnt);
+        size_t need = L.scan_bytes;
+        TP_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.scan_tmp, need, (const uint32_t *)tile_cnt, tile_first, (int)(ntiles + 1), st));
+        hipLaunchKernelGGL(tp_line_ends, dim3(grid), dim3(TILE_THREADS), 0, st, gran, shift, len, ntiles,
+                           (const uint32_t *)tile_first, max_lines, line_end);
+    }
+    hipLaunchKernelGGL(tp_begin, dim3(1), dim3(64), 0, st, (const uint32_t *)tile_first, ntiles, max_lines,
+                       (const int64_t *)line_end, info_dev);
+    TP_HIP(hipGetLastError());
+    *line_end_dev = line_end;
+    return 0;
+}
+
 extern "C" int cv_parse_tensor_text_dev_workspace(int64_t len, int64_t max_lines, int64_t *bytes)
 {
     if (!bytes) { cv_set_error("cv_parse_tensor_text_dev_workspace: null argument"); return 1; }
@@ -408,27 +447,15 @@ extern "C" int cv_parse_tensor_text_dev(const char *text_dev, int64_t len, int64
         return 1;
     }
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace_dev;
-    uint32_t *tile_cnt = (uint32_t *)(ws + L.tile_cnt), *tile_first = (uint32_t *)(ws + L.tile_first);
-    int64_t *line_end = (int64_t *)(ws + L.line_end);
+    const int64_t *line_end = nullptr;
+    if (cv_text_line_index(text_dev, len, max_lines, workspace_dev, info_dev, &line_end, st)) return 1;
     const int shift = (int)((uintptr_t)text_dev & 15);
     const uint4 *gran = (const uint4 *)(text_dev - shift);
-    // (the tile count of the worst offset: what the workspace and the scan were sized for; a tile behind the slab counts 0)
     const int64_t ntiles = len > 0 && max_lines > 0 ? L.ntiles_max : 0;
-    if (ntiles > 0) {
-        const int grid = (int)(ntiles < INDEX_GRID ? ntiles : INDEX_GRID);
-        hipLaunchKernelGGL(tp_count_newlines, dim3(grid), dim3(TILE_THREADS), 0, st, gran, shift, len, ntiles, tile_cnt);
-        size_t need = L.scan_bytes;
-        TP_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.scan_tmp, need, (const uint32_t *)tile_cnt, tile_first, (int)(ntiles + 1), st));
-        hipLaunchKernelGGL(tp_line_ends, dim3(grid), dim3(TILE_THREADS), 0, st, gran, shift, len, ntiles,
-                           (const uint32_t *)tile_first, max_lines, line_end);
-    }
-    hipLaunchKernelGGL(tp_begin, dim3(1), dim3(64), 0, st, (const uint32_t *)tile_first, ntiles, max_lines,
-                       (const int64_t *)line_end, info_dev);
     if (ntiles > 0) {
         const int64_t blocks = (max_lines + PARSE_WAVES - 1) / PARSE_WAVES;
         hipLaunchKernelGGL(tp_parse_rows, dim3((int)(blocks < PARSE_GRID ? blocks : PARSE_GRID)), dim3(PARSE_WAVES * WAVE), 0, st,
-                           gran, shift, (const int64_t *)line_end, info_dev, x_dev, meta_dev, status_dev);
+                           gran, shift, line_end, info_dev, x_dev, meta_dev, status_dev);
     }
     TP_HIP(hipGetLastError());
     return 0;

@@ -5,6 +5,7 @@ blocks) of 500-item blosc chunks -- same command line and layout as
     python -m clairvoyante_amd.tensor2Bin --tensor_fn T.gz --var_fn V.gz --bed_fn B.bed --bin_fn OUT.bin
     python -m clairvoyante_amd.tensor2Bin --bam_fn A.bam,B.bam --ref_fn A.fa,B.fa --ctgName chr21,chr22 \
            --ctgStart S1,S2 --ctgEnd E1,E2 --var_fn V.gz --bed_fn B.bed --seed N --bin_fn OUT.bin
+    (--vcf_fn TRUTH.vcf.gz in place of --var_fn: the truth rows of each source by GetTruth's rules)
 
 The second form (not in the reference) builds the set from the BAMs on the GPU, utils_v2.GetTrainingSetFromBam.
 """
@@ -27,9 +28,10 @@ def Convert(args, utils):
     logging.info("Loading the dataset ...")
     sources = utils.bam_sources(args) if hasattr(utils, "bam_sources") else None
     if sources is not None:
+        var_fn, vcf_fn = utils.truth_inputs(args)
         total, XC, YC, PC = utils.GetTrainingSetFromBam(
-            sources, args.var_fn, args.bed_fn, amp=args.amp, candidates=args.candidates, genomeSize=args.genomeSize,
-            seed=args.seed, samtools=args.samtools, minMQ=args.minMQ, dcov=args.dcov).blocks()
+            sources, var_fn, args.bed_fn, amp=args.amp, candidates=args.candidates, genomeSize=args.genomeSize,
+            seed=args.seed, samtools=args.samtools, minMQ=args.minMQ, dcov=args.dcov, vcf_fn=vcf_fn).blocks()
     else:
         total, XC, YC, PC = utils.GetTrainingArray(args.tensor_fn, args.var_fn, args.bed_fn)
     logging.info("Writing to binary ...")

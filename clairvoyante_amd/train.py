@@ -307,9 +307,11 @@ def load_dataset(args, utils, m=None):
     sources = utils.bam_sources(args) if hasattr(utils, "bam_sources") else None
     if sources is not None:
         from . import parallel
+        var_fn, vcf_fn = utils.truth_inputs(args)
         ts = utils.GetTrainingSetFromBam(
-            sources, args.var_fn, args.bed_fn, amp=args.amp, candidates=args.candidates, genomeSize=args.genomeSize,
-            seed=args.seed, device=getattr(m, "device", None), samtools=args.samtools, minMQ=args.minMQ, dcov=args.dcov)
+            sources, var_fn, args.bed_fn, amp=args.amp, candidates=args.candidates, genomeSize=args.genomeSize,
+            seed=args.seed, device=getattr(m, "device", None), samtools=args.samtools, minMQ=args.minMQ, dcov=args.dcov,
+            vcf_fn=vcf_fn)
         if m is not None and getattr(m, "accepts_device_batches", False) and parallel.world()[1] == 1:
             return ts.resident() + (None,)
         return ts.blocks()

@@ -2038,10 +2038,11 @@ def _gz_lines(fn):
     f.wait()
 
 
-def _read_bed_truth(var_fn, bed_fn, every=None):
+def _read_bed_truth(var_fn, bed_fn, every=None, rows=None):
     """The BED and truth files as utils_v2.py:62-119 reads them -> (tree: contig -> _Intervals, Y: "ctg:pos" -> label of
     the truth rows the BED keeps; the last row of a key wins).  A truth contig the BED file lacks raises KeyError, as there.
-    every: a dict that receives contig -> set of the positions of ALL truth rows, kept by the BED or not."""
+    every: a dict that receives contig -> set of the positions of ALL truth rows, kept by the BED or not.
+    rows: the truth rows as text lines, in place of the lines of var_fn (vcf_truth_rows: the definition of --vcf_fn)."""
     tree = {}
     if bed_fn is not None:
         for row in _gz_lines(bed_fn):
@@ -2054,8 +2055,8 @@ def _read_bed_truth(var_fn, bed_fn, every=None):
                 end += 1
             t.addi(begin, end)
     Y = {}
-    if var_fn is not None:
-        for row in _gz_lines(var_fn):
+    if var_fn is not None or rows is not None:
+        for row in (_gz_lines(var_fn) if rows is None else rows):
             row = row.split()
             if not row:
                 continue
@@ -2214,6 +2215,408 @@ def _trainset_tables(tree, Y, has_bed):
         "labels": np.array(labels, dtype=np.float32).reshape(-1, 16)}
 
 
+# ---- the truth list and the BED file read on the device (csrc/cv_truth_dev.hip) ------------------------------------------
+# CV_TRUTH_TABLES=host|device picks the reader of truth_tables; unset, the size of the truth list (of the BED file when
+# there is no truth list) decides: the device from these bytes on disk upwards -- plain text, ordinary .gz, BGZF; None =
+# never.  The tables are the same either way.  Measured (profiles/r19/truth_tables_device.txt,
+# tools/gpu_truth_tables_probe.py): the device route is ahead of the host route of the same commit, and of the parent
+# commit's loop, in all five runs from the smallest rung, 20 000 truth rows (444 170 bytes of plain text, 89 958 of .gz,
+# 90 561 of BGZF), upwards, with and without a BED -- 1 ms / 1-2 ms / 13-15 ms against 29-157 ms there, 3-4 ms / 29-33 ms /
+# 26-28 ms against 3.6-5.6 s at 1 M rows.  Smaller files were not measured and stay on the host.
+# The probe's files are sorted by contig.  A truth list whose contigs ALTERNATE line by line was not measured: the host
+# then names one run-start token per row (a gather and a Python loop per slab), as GetTrainingSetDevice does for its rows.
+TRUTH_TABLES_DEVICE_MIN_BYTES = {"plain": 440000, "gz": 89000, "bgzf": 90000}
+# A truth VCF (vcf_fn=) with the switch unset: the device from this many bytes of BGZF on; any other form was not measured
+# and stays on the host.  Same file, same rule: ahead in all five runs from the smallest rung (20 000 records, 106 775
+# bytes) upwards, read for four sources -- 9-10 ms against 22-33 ms there, 71-75 ms against 1.34-1.74 s at 1 M records.
+# Every slab passes once per source, so the device's time grows with the number of sources, as the host loop's does.
+TRUTH_VCF_DEVICE_MIN_BYTES = 106000
+TRUTH_SLAB_BYTES = 16 << 20         # text per call of the line pass; its workspace and outputs take about 22 bytes per byte
+TRUTH_FORMAT_VAR, TRUTH_FORMAT_BED, TRUTH_FORMAT_VCF = 0, 1, 2           # CV_TRUTH_FORMAT_*
+TRUTH_MAX_CTG = 256                                 # CV_TRUTH_MAX_CTG: bytes of a source's contig name (format VCF)
+_TRUTH_COUNT_KEYS = ("device_lines", "host_lines", "device_calls", "host_calls", "handed_over_calls")
+_truth_counts = dict.fromkeys(_TRUTH_COUNT_KEYS, 0)
+
+
+def truth_table_counts(reset=False):
+    """lines and calls of truth_tables per side so far; handed_over_calls: calls the device route began and gave to the
+    host (host_lines counts only what the device route saw: the host loop does not count its lines)"""
+    out = dict(_truth_counts)
+    if reset:
+        _truth_counts.update(dict.fromkeys(_TRUTH_COUNT_KEYS, 0))
+    return out
+
+
+def truth_tables_route(var_fn=None, bed_fn=None, vcf_fn=None):
+    """"host" or "device" for truth_tables over these files: CV_TRUTH_TABLES when it is set, else the device from
+    TRUTH_TABLES_DEVICE_MIN_BYTES of the truth list (the BED file when there is none) upwards, a truth VCF from
+    TRUTH_VCF_DEVICE_MIN_BYTES of BGZF upwards; always "host" without a GPU"""
+    forced = os.environ.get("CV_TRUTH_TABLES")
+    if forced not in (None, "", "host", "device"):
+        raise ValueError("CV_TRUTH_TABLES must be 'host' or 'device', got %r" % forced)
+    if forced == "host" or not _gpu_present():
+        return "host"
+    if forced == "device":
+        return "device"
+    if vcf_fn is not None:
+        floor = TRUTH_VCF_DEVICE_MIN_BYTES if os.path.isfile(vcf_fn) and is_bgzf(vcf_fn) else None
+        return "device" if floor is not None and os.path.getsize(vcf_fn) >= max(floor, 1) else "host"
+    fn = var_fn if var_fn is not None else bed_fn
+    if fn is None or not os.path.isfile(fn):
+        return "host"
+    form = "bgzf" if is_bgzf(fn) else "gz" if is_compressed(fn) else "plain"
+    floor = TRUTH_TABLES_DEVICE_MIN_BYTES[form]
+    return "device" if floor is not None and os.path.getsize(fn) >= max(floor, 1) else "host"
+
+
+def vcf_truth_rows(vcf_fn, sources):
+    """The definition of --vcf_fn: GetTruth.variant_rows once per source (bam_fn, ref_fn, ctgName, ctgStart, ctgEnd), in
+    source order, with that source's contig and GetTruth's own bounds ([ctgStart + 1, ctgEnd] when both are given, none
+    otherwise) -> the truth list's lines as _read_bed_truth(rows=...) takes them"""
+    from . import GetTruth
+    out = []
+    for _bam, _ref, ctg, cs, ce in sources:
+        if cs is not None and ce is not None:
+            cs = cs + 1
+        vcf = GetTruth.open_vcf(vcf_fn, ctg, cs, ce)
+        try:
+            out += [r.decode("ascii", "replace") + "\n" for r in GetTruth.variant_rows(vcf.stdout, ctg, cs, ce)]
+        finally:
+            vcf.stdout.close()
+            vcf.wait()
+    return out
+
+
+class TruthTables(object):
+    """truth_tables' result: names (contig id -> bytes), tables (the dict of _trainset_tables: numpy arrays on the host
+    route, device tensors on the device route; cpu() gives numpy either way), every (contig -> ascending int64 array of the
+    positions of ALL truth rows, when asked for), route and, when the host made them, the reason"""
+
+    def __init__(self, names, tables, every, route, reason=None):
+        self.names, self.tables, self.every, self.route, self.reason = names, tables, every, route, reason
+        self.times = {}
+
+    def cpu(self):
+        return {k: (v.cpu().numpy() if hasattr(v, "is_cuda") else v) for k, v in self.tables.items()}
+
+
+class _TruthHandOver(Exception):
+    """the device route met something only the definition answers"""
+
+
+def _truth_chunks(fn, want):
+    """the text of a truth list / BED file in pieces of about `want` bytes -> ("host", uint8 array) for plain text
+    (memory-mapped) and an ordinary .gz (the native inflate), ("bgzf", _BgzfSlab) for BGZF members the device inflates"""
+    bgzf = _map_bgzf(fn)
+    if bgzf is not None:
+        data, table, _total = bgzf
+        if len(table):
+            ends = table[:, 2] + (table[:, 3] >> 32)
+            lo = 0
+            while lo < len(table):
+                hi = max(int(np.searchsorted(ends, (ends[lo - 1] if lo else 0) + want, side="right")), lo + 1)
+                yield "bgzf", _BgzfSlab(data, table[lo:hi], fn)
+                lo = hi
+        return
+    plain = _map_plain_text(fn)
+    if plain is not None:
+        for lo in range(0, len(plain), want):
+            yield "host", plain[lo:lo + want]
+        return
+    if os.path.isfile(fn) and os.path.getsize(fn) == 0:
+        return
+    try:
+        gz = _GzipFile(fn)
+    except (_GzipFallback, OSError, ValueError) as e:
+        raise _TruthHandOver("%s is neither plain text nor gzip the native inflate takes (%s)" % (fn, e))
+    try:
+        while True:
+            try:
+                piece = gz.read(want)
+            except (_GzipFallback, _lib.CvError) as e:       # (a stream that breaks off: `gzip -fdc` is the definition's reader)
+                raise _TruthHandOver(str(e))
+            if not piece:
+                break
+            yield "host", np.frombuffer(piece, dtype=np.uint8)
+    finally:
+        gz.close()
+
+
+class _TruthReader(object):
+    """the device side of truth_tables: the line pass over one file slab by slab, the rows of all slabs, the contig ids"""
+
+    def __init__(self, device):
+        import torch
+        self.torch, self.device, self.lib = torch, device, _lib.load()
+        self.names, self.ids = [], {}
+
+    def _p(self, t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+    def _inflate(self, slab, head):
+        """a group of BGZF members inflated behind `head` free bytes -> the text buffer (members the device leaves to the
+        host are inflated there)"""
+        torch = self.torch
+        m = len(slab.table)
+        text = torch.empty(head + slab.n + 1, dtype=torch.uint8, device=self.device)
+        comp = torch.zeros(len(slab.comp) + 8, dtype=torch.uint8, device=self.device)
+        comp[:len(slab.comp)].copy_(torch.from_numpy(np.array(slab.comp)))
+        table = torch.from_numpy(slab.table).to(self.device)
+        status = torch.zeros(m, dtype=torch.uint8, device=self.device)
+        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self.lib.cv_inflate_bgzf_dev(self._p(comp), self._p(table), m, ctypes.c_void_p(text.data_ptr() + head), slab.n,
+                                                self._p(status), st))
+        for i in np.flatnonzero(status.cpu().numpy() != 1):                # CV_BGZF_OK
+            try:
+                out = slab.inflate_member(int(i))
+            except _lib.CvError as e:
+                raise _TruthHandOver(str(e))
+            at = head + int(slab.table[i, 2])
+            text[at:at + len(out)].copy_(torch.from_numpy(out))
+        return text
+
+    def read(self, fn, fmt, known=None, filters=None):
+        """-> per pass over the file (one, or one per entry of `filters`) the tuple (pos, end or label, run, run_ctg,
+        number of runs) of its rows in arrival order, all device tensors.  known: the contig ids a truth list must stay
+        within (the BED's: a contig outside them is the definition's KeyError).  filters (format VCF): (contig bytes,
+        lower, upper) per source, bounds None for none; the file is read ONCE, every slab passes once per source, and the
+        runs of a source carry no contig id yet (run_ctg is None: they are all the source's contig)"""
+        import warnings
+        torch = self.torch
+        slab_bytes = max(int(TRUTH_SLAB_BYTES), 1)
+        passes = [{"filter": f, "cols": ([], [], []), "run_ctg": []} for f in (filters if filters is not None else [None])]
+        carry = torch.empty(0, dtype=torch.uint8, device=self.device)
+        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        chunks = _truth_chunks(fn, slab_bytes)
+        try:
+            kind, piece = next(chunks, (None, None))
+            while kind is not None:
+                nxt = next(chunks, (None, None))
+                last, head = nxt[0] is None, int(carry.numel())
+                if kind == "bgzf":
+                    buf = self._inflate(piece, head)
+                    n = head + piece.n
+                else:
+                    n = head + len(piece)
+                    buf = torch.empty(n + 1, dtype=torch.uint8, device=self.device)
+                    with warnings.catch_warnings():
+                        warnings.simplefilter("ignore")              # (a read-only source: the memory map, a bytes object)
+                        buf[head:n].copy_(torch.from_numpy(piece))
+                if head:
+                    buf[:head].copy_(carry)
+                if last:                       # a last line without newline is a line; behind a newline this adds a blank one
+                    buf[n:n + 1].fill_(10)
+                    n += 1
+                lo, hi = 0, min(head + slab_bytes, n)
+                while True:
+                    if hi > lo:
+                        lo += self._slab(buf, lo, hi, fmt, known, passes, st)
+                    if hi >= n:
+                        break
+                    hi = min(hi + slab_bytes, n)
+                carry = buf[lo:n].clone()
+                kind, piece = nxt
+        finally:
+            chunks.close()
+        bed = fmt == TRUTH_FORMAT_BED
+        cat = lambda parts, dt, shape: torch.cat(parts) if parts else torch.empty(shape, dtype=dt, device=self.device)
+        out = []
+        for p in passes:
+            run_ctg = None if filters is not None else torch.from_numpy(np.array(p["run_ctg"] or [0], dtype=np.int32)).to(self.device)
+            out.append((cat(p["cols"][0], torch.int64, (0,)), cat(p["cols"][1], torch.int64 if bed else torch.float32, (0,) if bed else (0, 16)),
+                        cat(p["cols"][2], torch.int32, (0,)), run_ctg, len(p["run_ctg"])))
+        return out
+
+    def _slab(self, buf, lo, hi, fmt, known, passes, st):
+        """the line pass over buf[lo:hi], once per entry of `passes`, again while the line table is full -> bytes consumed"""
+        torch, lib = self.torch, self.lib
+        done = 0
+        while lo + done < hi:
+            n = hi - lo - done
+            text_ptr = buf.data_ptr() + lo + done
+            max_lines = n // 6 + 16
+            need = ctypes.c_int64()
+            _lib.check(lib.cv_truth_lines_workspace(n, max_lines, ctypes.byref(need)))
+            ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            bed = fmt == TRUTH_FORMAT_BED
+            for p in passes:
+                pos = torch.empty(max_lines, dtype=torch.int64, device=self.device)
+                end = torch.empty(max_lines, dtype=torch.int64, device=self.device) if bed else None
+                label = None if bed else torch.empty((max_lines, 16), dtype=torch.float32, device=self.device)
+                run = torch.empty(max_lines, dtype=torch.int32, device=self.device)
+                tok = torch.empty((max_lines, 2), dtype=torch.int64, device=self.device)
+                info_dev = torch.empty(8, dtype=torch.int64, device=self.device)
+                ctg, lower, upper = p["filter"] if p["filter"] is not None else (None, None, None)
+                _lib.check(lib.cv_truth_lines_dev(ctypes.c_void_p(text_ptr), n, fmt, ctg, len(ctg or b""), int(lower is not None),
+                                                  lower or 0, upper or 0, max_lines, self._p(pos), self._p(end), self._p(label),
+                                                  self._p(run), self._p(tok), self._p(info_dev), self._p(ws), need.value, st))
+                used, lines, rows, skipped, host, runs = info_dev.cpu().tolist()[:6]
+                _truth_counts["device_lines"] += rows + skipped
+                _truth_counts["host_lines"] += host
+                if host:
+                    raise _TruthHandOver("%d line(s) only the host loop defines the result for (bytes outside printable ASCII, '\\r', "
+                                         "an integer that is not canonical decimal, too few tokens, a base outside ACGT, a genotype "
+                                         "that is not two single digits, ...)" % host)
+                if runs and p["filter"] is not None:
+                    p["run_ctg"] += [-1] * runs                      # (every run of a source is the source's contig)
+                elif runs:
+                    t = tok[:runs].cpu().numpy()
+                    idx = np.repeat(t[:, 0] - np.cumsum(np.concatenate(([0], t[:-1, 1]))), t[:, 1]) + np.arange(int(t[:, 1].sum()))
+                    raw = buf[lo + done:lo + done + n][torch.from_numpy(idx).to(self.device)].cpu().numpy().tobytes()
+                    at = 0
+                    for ln in t[:, 1].tolist():
+                        name = raw[at:at + ln]
+                        at += ln
+                        p["run_ctg"].append(self.contig_id(name, known))
+                if rows:
+                    p["cols"][0].append(pos[:rows].clone())
+                    p["cols"][1].append((end if bed else label)[:rows].clone())
+                    p["cols"][2].append(run[:rows] + (len(p["run_ctg"]) - runs))
+            done += used
+            if lines < max_lines:
+                break
+        return done
+
+    def contig_id(self, name, known):
+        """the id of a truth contig: its BED id (known = number of BED contigs; absent = the definition's KeyError), else
+        ids in order of first appearance"""
+        cid = self.ids.get(name)
+        if cid is None or (known is not None and cid >= known):
+            if known is not None:
+                raise _TruthHandOver("the truth contig %r is absent from the BED file (the host loop's KeyError)"
+                                     % name.decode("ascii", "replace"))
+            if len(self.names) >= TRAINSET_MAX_CONTIGS:
+                raise _TruthHandOver("more than %d contigs" % TRAINSET_MAX_CONTIGS)
+            cid = self.ids[name] = len(self.names)
+            self.names.append(name)
+        return cid
+
+
+def vcf_source_filters(sources):
+    """(contig bytes, lower, upper) per source as GetTruth sees it: [ctgStart + 1, ctgEnd] when both are given, else no bounds"""
+    out = []
+    for _bam, _ref, ctg, cs, ce in sources:
+        both = cs is not None and ce is not None
+        out.append((str(ctg).encode("utf-8"), cs + 1 if both else None, ce if both else None))
+    return out
+
+
+def _truth_tables_device(var_fn, bed_fn, device, want_every, vcf_fn=None, sources=None):
+    """truth_tables on the device -> TruthTables; _TruthHandOver where only the definition answers"""
+    import torch
+    device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+    rd = _TruthReader(device)
+    lib, P = rd.lib, rd._p
+    E = lambda n, dt=torch.int64: torch.empty(n, dtype=dt, device=device)
+    with torch.cuda.device(device):
+        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        need = ctypes.c_int64()
+        has_bed = bed_fn is not None
+        nb = 0
+        if has_bed:
+            (begin, end, run, run_ctg, nruns), = rd.read(bed_fn, TRUTH_FORMAT_BED)
+            nb, nbed_ctg = int(begin.numel()), len(rd.names)
+            bed_off, bed_begin, bed_emax = E(nbed_ctg + 1), E(nb), E(nb)
+            _lib.check(lib.cv_bed_table_workspace(nb, ctypes.byref(need)))
+            ws = E(need.value, torch.uint8)
+            _lib.check(lib.cv_bed_table_dev(nb, P(begin), P(end), P(run), P(run_ctg), nruns, nbed_ctg, P(bed_off), P(bed_begin),
+                                            P(bed_emax), P(ws), need.value, st))
+        n, known = 0, (len(rd.names) if has_bed else None)
+        if var_fn is not None:
+            (pos, label, run, run_ctg, nruns), = rd.read(var_fn, TRUTH_FORMAT_VAR, known=known)
+            n = int(pos.numel())
+        elif vcf_fn is not None:
+            # one read of the VCF, one pass per source over every slab; the rows of the sources one behind the other are
+            # the concatenation the definition feeds its loop, and the contigs get their ids in that order
+            filters = vcf_source_filters(sources)
+            for name, _lo, _hi in filters:
+                if not (1 <= len(name) <= TRUTH_MAX_CTG and contig_token_ok(name)):
+                    raise _TruthHandOver("a source contig name the device route does not take: %r" % (name,))
+            parts, ctg_of_run = [], []
+            for (name, _lo, _hi), (p_pos, p_label, p_run, _none, p_runs) in zip(filters, rd.read(vcf_fn, TRUTH_FORMAT_VCF, filters=filters)):
+                if p_pos.numel():
+                    parts.append((p_pos, p_label, p_run + len(ctg_of_run)))
+                    ctg_of_run += [rd.contig_id(name, known)] * p_runs
+            nruns = len(ctg_of_run)
+            pos = torch.cat([p[0] for p in parts]) if parts else E(0)
+            label = torch.cat([p[1] for p in parts]) if parts else E((0, 16), torch.float32)
+            run = torch.cat([p[2] for p in parts]) if parts else E(0, torch.int32)
+            run_ctg = torch.from_numpy(np.array(ctg_of_run or [0], dtype=np.int32)).to(device)
+            n = int(pos.numel())
+        nctg = len(rd.names)
+        if not has_bed:
+            bed_off, bed_begin, bed_emax = torch.zeros(nctg + 1, dtype=torch.int64, device=device), E(0), E(0)
+        truth_off, every_off = torch.zeros(nctg + 1, dtype=torch.int64, device=device), torch.zeros(nctg + 1, dtype=torch.int64, device=device)
+        truth_pos, every_pos, labels = E(n), E(n), E((n, 16), torch.float32)
+        counts = torch.zeros(2, dtype=torch.int64, device=device)
+        if var_fn is not None or vcf_fn is not None:
+            _lib.check(lib.cv_truth_tables_workspace(n, ctypes.byref(need)))
+            ws = E(need.value, torch.uint8)
+            _lib.check(lib.cv_truth_tables_dev(n, P(pos), P(label), P(run), P(run_ctg), nruns, nctg, 1 if has_bed else 0, P(bed_off),
+                                               P(bed_begin), P(bed_emax), P(truth_off), P(truth_pos), P(labels), P(every_off),
+                                               P(every_pos), P(counts), P(ws), need.value, st))
+        nt, ne = counts.cpu().tolist()                        # (synchronises: the workspaces may go)
+        tables = {"bed_off": bed_off, "bed_begin": bed_begin, "bed_emax": bed_emax, "truth_off": truth_off,
+                  "truth_pos": truth_pos[:nt], "labels": labels[:nt]}
+        every = None
+        if want_every:
+            off, ep = every_off.cpu().numpy(), every_pos[:ne].cpu().numpy()
+            every = {rd.names[c].decode("ascii"): ep[off[c]:off[c + 1]].copy() for c in range(nctg) if off[c + 1] > off[c]}
+    return TruthTables(list(rd.names), tables, every, "device")
+
+
+def vcf_truth_positions(vcf_fn, ctg, lower, upper, device=None):
+    """the sorted unique positions of the rows GetTruth.variant_rows(vcf, ctg, lower, upper) gives, from the device pass
+    (callVarBam.truth_positions on the device route) -> int64 array, or None when a line is only the host loop's"""
+    both = lower is not None and upper is not None
+    try:
+        got = _truth_tables_device(None, None, device, True, vcf_fn, [(None, None, ctg, lower - 1 if both else None, upper if both else None)])
+    except _TruthHandOver:
+        _truth_counts["handed_over_calls"] += 1
+        return None
+    _truth_counts["device_calls"] += 1
+    return got.every.get(str(ctg), np.zeros(0, dtype=np.int64))
+
+
+def truth_tables(var_fn, bed_fn, device=None, vcf_fn=None, sources=None, want_every=False):
+    """(names, tables) of _trainset_tables(*_read_bed_truth(var_fn, bed_fn)) and the positions of all truth rows per contig
+    -> TruthTables.  route "host": that code, unchanged (its exceptions pass through).  route "device"
+    (truth_tables_route(): CV_TRUTH_TABLES, else by the size of the file): the files' text goes to HBM in slabs of TRUTH_SLAB_BYTES -- plain text memory-mapped, BGZF
+    uploaded compressed and inflated there, an ordinary .gz inflated by the native inflate on the host --, cv_truth_lines_dev
+    gives every line its verdict and the rows their fields, cv_bed_table_dev and cv_truth_tables_dev make the tables.  If
+    any line comes back HOST, or a truth contig is absent from a given BED, the WHOLE call runs on the host: same result,
+    same exception, the reason in .reason.  vcf_fn (with the sources of GetTrainingSetFromBam) takes the truth rows from
+    a VCF by the rules of GetTruth (vcf_truth_rows is the definition); the device route reads the file once, every slab
+    passing once per source."""
+    import time
+    t0 = time.time()
+    if vcf_fn is not None:
+        if var_fn is not None:
+            raise ValueError("truth_tables: var_fn and vcf_fn are both given")
+        if sources is None:
+            raise ValueError("truth_tables: vcf_fn needs the sources")
+    route, reason = truth_tables_route(var_fn, bed_fn, vcf_fn), None
+    if route == "device":
+        try:
+            got = _truth_tables_device(var_fn, bed_fn, device, want_every, vcf_fn, sources)
+            _truth_counts["device_calls"] += 1
+            got.times["tables"] = time.time() - t0
+            return got
+        except _TruthHandOver as e:
+            reason = str(e)
+            _truth_counts["handed_over_calls"] += 1
+    _truth_counts["host_calls"] += 1
+    every = {} if want_every else None
+    rows = vcf_truth_rows(vcf_fn, sources) if vcf_fn is not None else None
+    tree, Y = _read_bed_truth(var_fn, bed_fn, every, rows=rows)
+    names, tables = _trainset_tables(tree, Y, bed_fn is not None)
+    if every is not None:
+        every = {k: np.array(sorted(v), dtype=np.int64) for k, v in every.items()}
+    got = TruthTables(names, tables, every, "host", reason)
+    got.times["tables"] = time.time() - t0
+    return got
+
+
 def _estimated_rows(tensor_fn):
     """rows of a tensor file from its size and its first line's length (the inflated size for BGZF, whose table states it)"""
     bgzf = _map_bgzf(tensor_fn)
@@ -2369,7 +2772,7 @@ class _TrainsetBuilder(object):
         self.names, self.ids = list(names), {n: i for i, n in enumerate(names)}
         self.ntab, self.has_bed = len(names), has_bed
         with torch.cuda.device(self.device):
-            self.tab = {k: torch.from_numpy(v).to(self.device) for k, v in tables.items()}
+            self.tab = {k: (v if torch.is_tensor(v) else torch.from_numpy(v)).to(self.device) for k, v in tables.items()}
         self.n, self.cap = 0, 0
         self.cols = None
         self._grow(max(int(rows_hint), 1024))
@@ -2495,8 +2898,8 @@ def GetTrainingSetDevice(tensor_fn, var_fn, bed_fn, shuffle=True, device=None, n
         import torch
         device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         t0 = time.time()
-        tree, Y = _read_bed_truth(var_fn, bed_fn)
-        names, tables = _trainset_tables(tree, Y, bed_fn is not None)
+        tt = truth_tables(var_fn, bed_fn, device)
+        names, tables = tt.names, tt.tables
         t_tables = time.time() - t0
         host0 = text_line_counts["host"]
         b = _TrainsetBuilder(device, names, tables, bed_fn is not None, _estimated_rows(tensor_fn))
@@ -2589,6 +2992,12 @@ class _BamTrainsetBuilder(_TrainsetBuilder):
             return {"v": v, "c": cc, "r": float(r.item()), "picked": picked, "kept": kept}
 
 
+def truth_inputs(args):
+    """-> (var_fn, vcf_fn) of GetTrainingSetFromBam from the flags: --vcf_fn takes the place of --var_fn"""
+    vcf_fn = getattr(args, "vcf_fn", None)
+    return (None if vcf_fn is not None else args.var_fn), vcf_fn
+
+
 def _split_list(value, n=None, typ=str):
     """a comma-separated command-line list; an empty item is None"""
     items = [None if v == "" else typ(v) for v in str(value).split(",")]
@@ -2611,12 +3020,20 @@ BAM_FLAGS = (   # flag, type, default, help: what tensor2Bin and train.py add fo
     ("--samtools", str, "samtools", "Path to the 'samtools', or 'native', default: %(default)s"),
     ("--minMQ", int, 0, "Minimum Mapping Quality, default: %(default)d"),
     ("--dcov", int, 250, "Cap depth per position at %(default)d"),
+    ("--vcf_fn", str, None, "Truth VCF input (needs --bam_fn, excludes --var_fn): the truth rows of each source are taken from "
+                            "it by GetTruth's rules"),
 )
 
 
-def bam_sources(args, tensor_default="vartensors"):
+def bam_sources(args, tensor_default="vartensors", var_default="truthvars"):
     """the `sources` of GetTrainingSetFromBam from the --bam_fn family of flags, or None when --bam_fn is absent;
-    ValueError for lists of unequal length and for --bam_fn together with --tensor_fn"""
+    ValueError for lists of unequal length, for --bam_fn together with --tensor_fn, for --vcf_fn without --bam_fn and for
+    --vcf_fn together with an explicit --var_fn"""
+    if getattr(args, "vcf_fn", None) is not None:
+        if getattr(args, "bam_fn", None) is None:
+            raise ValueError("--vcf_fn needs --bam_fn: a truth VCF is read for the sources of a set built from BAMs")
+        if getattr(args, "var_fn", var_default) not in (None, var_default):
+            raise ValueError("--vcf_fn and --var_fn are both given: the truth rows come from one or the other")
     if getattr(args, "bam_fn", None) is None:
         return None
     if getattr(args, "tensor_fn", tensor_default) != tensor_default:
@@ -2653,7 +3070,7 @@ def _fai_length(ref_fn, ctg):
 
 
 def GetTrainingSetFromBam(sources, var_fn, bed_fn, amp=2, candidates=7000000, genomeSize=3000000000, seed=None, shuffle=True,
-                          device=None, samtools="samtools", minMQ=0, dcov=250, considerleftedge=True):
+                          device=None, samtools="samtools", minMQ=0, dcov=250, considerleftedge=True, vcf_fn=None):
     """From (BAM, reference, truth list, BED) to the labelled, shuffled training set in HBM -> TrainingSet (route "device";
     .pairing = dict(v, c, r, picked, kept)), without text tensors in between.  `sources`: (bam_fn, ref_fn, ctgName, ctgStart,
     ctgEnd) each.  The result is the one the file recipe gives with the same seed: ExtractVariantCandidates
@@ -2664,6 +3081,8 @@ def GetTrainingSetFromBam(sources, var_fn, bed_fn, amp=2, candidates=7000000, ge
     UNION truth) and scatters the retained alignments, cv_bamtrain_columns gives the columns; over all rows
     cv_bamtrain_pair pairs, then cv_trainset_finish / _gather as for the text route.  Deliberate deviation from
     PairWithNonVariants.py:88: with no usable non-variant (c == 0) r is 1, where the reference divides by zero.
+    vcf_fn (in place of var_fn): the truth rows come from a truth VCF by GetTruth's rules, once per source (vcf_truth_rows),
+    so the GetTruth step of the recipe disappears.
     There is no host builder behind this route (the pileup has none): without a GPU, or when twice the estimated set
     would not fit into half of the free device memory, it raises CvError."""
     import argparse
@@ -2679,14 +3098,15 @@ def GetTrainingSetFromBam(sources, var_fn, bed_fn, amp=2, candidates=7000000, ge
     seed = draws.resolve_seed(seed, "GetTrainingSetFromBam")
     outputProb = (candidates * 2.) / genomeSize                      # ExtractVariantCandidates.py:254
     t0 = time.time()
-    truth_all = {}                                                   # contig -> every truth position (not BED-filtered)
-    tree, Y = _read_bed_truth(var_fn, bed_fn, truth_all)
-    names, tables = _trainset_tables(tree, Y, bed_fn is not None)
+    tt = truth_tables(var_fn, bed_fn, device, vcf_fn=vcf_fn, sources=sources if vcf_fn is not None else None, want_every=True)
+    names, tables, truth_all = tt.names, tt.tables, tt.every         # contig -> every truth position, ascending (not BED-filtered)
     plan, estimate = [], 0
     for bam_fn, ref_fn, ctg, cs0, ce0 in sources:
         a = argparse.Namespace(bam_fn=bam_fn, ref_fn=ref_fn, ctgName=ctg, ctgStart=cs0, ctgEnd=ce0, samtools=samtools)
         cs, ce, rs, re_ = region_of(a)
-        truth = sorted(p for p in truth_all.get(ctg, ()) if cs is None or cs <= p <= ce)
+        truth = truth_all.get(ctg, np.zeros(0, dtype=np.int64))
+        if cs is not None:
+            truth = truth[int(np.searchsorted(truth, cs, side="left")):int(np.searchsorted(truth, ce, side="right"))]
         span = (ce - cs + 1) if cs is not None else (_fai_length(ref_fn, ctg) or 0)
         estimate += len(truth) + int(span * min(outputProb, 1.0)) + 1
         plan.append((a, cs, ce, rs, re_, truth))

@@ -469,6 +469,68 @@ int cv_trainset_finish(int64_t nrows, const int32_t *ctg_dev, const int64_t *pos
 int cv_trainset_gather(const float *x_all_dev, const float *y_dev, const int64_t *src_dev, const int64_t *perm_dev,
                        int64_t total, float *x_out_dev, float *y_out_dev, void *stream);
 
+/* ---- the truth list and the BED file read on the device (csrc/cv_truth_dev.hip, csrc/cv_truth_core.hpp) ---------------
+ * What utils_v2._read_bed_truth + utils_v2._trainset_tables do per line of the two small text inputs of the training-set
+ * builders (utils_v2.truth_tables); the host loop stays the definition.  Every *_dev call is enqueued on `stream` and
+ * neither allocates nor synchronises; workspaces (256-byte aligned) are sized by the *_workspace functions and belong to
+ * the call until its kernels have run.
+ *
+ * cv_truth_lines_dev, per slab of text: the lines that END inside text_dev[0, len) (at most max_lines of them), each given
+ * one verdict -- a ROW with its fields, a line the definition SKIPs (no token), or a line only the definition can answer
+ * (HOST: a byte outside 0x21..0x7E / space / tab, more than CV_TRUTH_LINE_CAP bytes, too few tokens, an integer that is
+ * not canonical decimal of at most CV_TRAINSET_MAX_DIGITS digits, a ':' in the contig token, a first base outside ACGT
+ * where utils_v2._label looks it up).  Format VAR is "ctg pos ref alt g1 g2", BED "ctg begin end".  Format VCF is a line
+ * of a truth VCF under GetTruth's rules for ONE source -- ctg[ctg_len] (a HOST pointer, 1 .. CV_TRUTH_MAX_CTG bytes) the
+ * wanted contig, [lower, upper] its bounds when has_bounds; the four arguments are ignored for the other formats --: a
+ * line whose first token starts with '#' or is another contig, or whose position lies outside the bounds, is SKIPped
+ * whatever else it holds; the genotype (last column up to ':') must be digit-or-'.', '/' or '|', digit-or-'.', else HOST;
+ * p1 <= p2; 1|2 with a ',' in ALT becomes 0|1 on the first of the shortest ALT alleles; the row's fields are those of
+ * "ctg pos REF ALT p1 p2" in format VAR.  The per-line status stays in the workspace: the outputs are the rows and the
+ * counters, which is what a whole-call hand-over needs.  Row r = the r-th ROW:
+ *   pos_dev[r] int64      VAR: pos; BED: begin;
+ *   end_dev[r] int64      BED only: int(end) - 1, + 1 when that equals begin (may be null for VAR);
+ *   label_dev[r][16] fp32 VAR and VCF: utils_v2._label of the row (may be null for BED);
+ *   run_dev[r] int32      index of the row's contig run: a run starts at a ROW whose contig token differs byte for byte
+ *                         from the line before, or whose line before is no ROW;
+ *   tok_dev[k][2] int64   offset in the slab and length of the contig token that starts run k;
+ *   info_dev[8] int64     {bytes consumed, lines, rows, skipped, host, runs, 0, 0}.
+ * The four row arrays hold max_lines entries.  cv_truth_lines_host_form: the same core on the CPU over HOST pointers.
+ *
+ * cv_bed_table_dev, once over the n intervals of all slabs, run_ctg_dev[nruns] = contig id of each run (the host compares
+ * the run-start tokens): the intervals of each contig sorted by (begin, end); bed_off_dev[nctg + 1], bed_begin_dev[n],
+ * bed_emax_dev[n] = running maximum of the ends within the contig -- the tables cv_trainset_join reads.  In both table
+ * calls a run index outside [0, nruns) or a contig id outside [0, nctg) is the caller's error and counts as contig 0.
+ *
+ * cv_truth_tables_dev, once over the n truth rows of all slabs in arrival order: the last row of each (contig id, pos)
+ * wins; those the BED keeps (has_bed: upper_bound(begin, pos) = k > 0 and emax[k - 1] > pos; else all) give
+ * truth_off_dev[nctg + 1], truth_pos_dev (ascending per contig), labels_dev[..][16]; all of them give every_off_dev
+ * [nctg + 1], every_pos_dev: the distinct positions per contig.  counts_dev[2] = {truth rows, distinct positions}; the
+ * three row arrays hold n entries; label_dev / labels_dev 16-byte aligned.                                             */
+#define CV_TRUTH_FORMAT_VAR 0
+#define CV_TRUTH_FORMAT_BED 1
+#define CV_TRUTH_FORMAT_VCF 2
+#define CV_TRUTH_MAX_CTG 256
+#define CV_TRUTH_LINE_CAP 8192
+#define CV_TRUTH_MAX_LINES ((int64_t)1 << 27)
+int cv_truth_lines_workspace(int64_t len, int64_t max_lines, int64_t *bytes);
+int cv_truth_lines_dev(const char *text_dev, int64_t len, int format, const char *ctg, int64_t ctg_len, int has_bounds,
+                       int64_t lower, int64_t upper, int64_t max_lines, int64_t *pos_dev, int64_t *end_dev, float *label_dev,
+                       int32_t *run_dev, int64_t *tok_dev, int64_t *info_dev, void *workspace_dev, int64_t workspace_bytes,
+                       void *stream);
+int cv_truth_lines_host_form(const char *text, int64_t len, int format, const char *ctg, int64_t ctg_len, int has_bounds,
+                             int64_t lower, int64_t upper, int64_t max_lines, int64_t *pos, int64_t *end, float *label,
+                             int32_t *run, int64_t *tok, int64_t *info);
+int cv_bed_table_workspace(int64_t n, int64_t *bytes);
+int cv_bed_table_dev(int64_t n, const int64_t *begin_dev, const int64_t *end_dev, const int32_t *run_dev,
+                     const int32_t *run_ctg_dev, int64_t nruns, int32_t nctg, int64_t *bed_off_dev, int64_t *bed_begin_dev,
+                     int64_t *bed_emax_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int cv_truth_tables_workspace(int64_t n, int64_t *bytes);
+int cv_truth_tables_dev(int64_t n, const int64_t *pos_dev, const float *label_dev, const int32_t *run_dev,
+                        const int32_t *run_ctg_dev, int64_t nruns, int32_t nctg, int has_bed, const int64_t *bed_off_dev,
+                        const int64_t *bed_begin_dev, const int64_t *bed_emax_dev, int64_t *truth_off_dev,
+                        int64_t *truth_pos_dev, float *labels_dev, int64_t *every_off_dev, int64_t *every_pos_dev,
+                        int64_t *counts_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* c-blosc 1.x chunk codec for the 500-item blocks of the `.bin` training file
  * (utils_v2.py:159-186 blosc.pack_array(cname='lz4hc'), :189-207 blosc.unpack_array;
  * tensor2Bin.py:24-28).  Decoder: LZ4/LZ4HC streams, byte shuffle, split blocks, memcpy'd
