@@ -7,9 +7,9 @@ import sys
 
 SUBMODULES = ("callVarBamParallel", "callVarBam", "callVar", "calTrainDevDiff", "evaluateListOfModels", "evaluate",
               "tensor2Bin", "trainNonstop", "train", "trainWithoutValidationNonstop", "CreateTensor",
-              "ExtractVariantCandidates", "GetTruth", "PairWithNonVariants")
-NOT_BUILT = ("demoRun", "getEmbedding", "getTensorAndLayerPNG", "ChooseItemInBed", "CombineMultipleDatasetsForTraining",
-             "CountNumInBed", "RandomSampling")
+              "ExtractVariantCandidates", "GetTruth", "PairWithNonVariants", "ChooseItemInBed", "CountNumInBed",
+              "RandomSampling", "CombineMultipleDatasetsForTraining")
+NOT_BUILT = ("demoRun", "getEmbedding", "getTensorAndLayerPNG")
 
 
 def main():

@@ -1,0 +1,473 @@
+"""What the reference's dataPrepScripts helpers compute, shared by ChooseItemInBed, CountNumInBed, RandomSampling and
+CombineMultipleDatasetsForTraining.
+
+The host loops restate the reference line by line and are the definitions:
+  choose_items_host / count_items_host   ChooseItemInBed.py:11-39 and CountNumInBed.py:13-48: the lines of a file whose first
+                                         two columns are contig and position that a BED interval covers
+  sample_positions_host                  RandomSampling.py:64-68: the positions of a range that the BED covers and a draw
+                                         keeps -- with the keyed draws of draws.py (stream RANDOM) in place of the reference's
+                                         unseeded generator, so that a kernel can draw them too
+  prefix_lines                           CombineMultipleDatasetsForTraining.py:29-44: one byte in front of every line
+
+The device route (csrc/cv_beditems_dev.hip; CV_BED_ITEMS=device) reads the BED as truth_tables does, walks the item file
+slab by slab (plain text memory-mapped, BGZF inflated on the device, an ordinary .gz inflated natively on the host),
+gives every line a verdict (cv_item_lines_dev), keeps the rows the BED covers and gathers their bytes
+(cv_items_keep_dev).  A line only the definition answers (HOST) hands the REST of the file to the host's per-line function
+from that slab's first unconsumed line on: what has been written, the counts and the exception raised are the host loop's.
+Sampling walks [start, end) in tiles of SAMPLE_TILE positions (cv_sample_positions_dev)."""
+import ctypes
+import itertools
+import os
+import shlex
+import subprocess
+
+import numpy as np
+
+from . import _lib, draws
+from . import utils_v2
+from .utils_v2 import TRUTH_FORMAT_BED, _Intervals, _TruthHandOver, _TruthReader, _gpu_present, _read_bed_truth, _truth_chunks
+
+SAMPLE_TILE = 1 << 24               # positions per call of the sampler: its workspace takes 8 bytes per position
+SAMPLE_FIRST_CAP = None             # tests: room for kept positions in the first try of every tile (None: from prob)
+# The device route is opt-in (CV_BED_ITEMS=device): the standing rule makes it the default from the smallest rung on which
+# it is ahead of the host loop in EVERY run of every larger rung.  profiles/r20/dataprep_device.txt
+# (tools/gpu_dataprep_probe.py) has it ahead in every run at 16 384 and 65 536 tensor-shaped rows in all three forms and
+# on all three sampling ranges, but the 262 144-row and 1 M-row rungs were not run: no floor until they are.  None = no floor.
+DEVICE_MIN_BYTES = None
+_COUNT_KEYS = ("device_lines", "host_lines", "device_calls", "host_calls", "handed_over_calls", "device_positions")
+_counts = dict.fromkeys(_COUNT_KEYS, 0)
+TIMES = None                        # the probe: a dict that receives the milliseconds of the device calls by name (HIP events)
+
+
+def counts(reset=False):
+    """lines, calls and sampled positions per side so far; handed_over_calls: calls the device route began and gave to
+    the host (host_lines counts only what the device route handed over: the host loop does not count its lines)"""
+    out = dict(_counts)
+    if reset:
+        _counts.update(dict.fromkeys(_COUNT_KEYS, 0))
+    return out
+
+
+def route(input_fn=None):
+    """"host" or "device": CV_BED_ITEMS when it is set, else the device from DEVICE_MIN_BYTES of input_fn upwards (no floor
+    is set: the host); always "host" without a GPU"""
+    forced = os.environ.get("CV_BED_ITEMS")
+    if forced not in (None, "", "host", "device"):
+        raise ValueError("CV_BED_ITEMS must be 'host' or 'device', got %r" % forced)
+    if forced == "host" or not _gpu_present():
+        return "host"
+    if forced == "device":
+        return "device"
+    if DEVICE_MIN_BYTES is None or input_fn is None or not os.path.isfile(input_fn):
+        return "host"
+    return "device" if os.path.getsize(input_fn) >= max(DEVICE_MIN_BYTES, 1) else "host"
+
+
+# ---- the host loops ---------------------------------------------------------------------------------------------------------
+def _gz_byte_lines(fn):
+    """the lines of `gzip -fdc fn` as bytes, each with its own line ending (ChooseItemInBed.py:28-29)"""
+    f = subprocess.Popen(shlex.split("gzip -fdc %s" % fn), stdout=subprocess.PIPE, bufsize=8388608)
+    try:
+        for row in f.stdout:
+            yield row
+    finally:
+        f.stdout.close()
+        f.wait()
+
+
+def _lines_of(blocks):
+    """byte blocks -> their lines, cut at b"\\n" only (as iterating a binary pipe does), the last one with or without"""
+    tail = b""
+    for b in blocks:
+        data = tail + b if tail else b
+        at = 0
+        while True:
+            k = data.find(b"\n", at)
+            if k < 0:
+                break
+            yield data[at:k + 1]
+            at = k + 1
+        tail = data[at:]
+    if tail:
+        yield tail
+
+
+def bed_tree(bed_fn):
+    """contig -> _Intervals: utils_v2._read_bed_truth's reading of a BED file, half-open [int(begin), int(end) - 1), + 1 on
+    the end when that equals the begin (ChooseItemInBed.py:13-23).  Blank BED lines follow the project's reader: they are
+    skipped, where the reference's row[0] raises IndexError."""
+    return _read_bed_truth(None, bed_fn)[0]
+
+
+def _host_lines(lines, tree, out, tally):
+    """the per-line body of both loops (ChooseItemInBed.py:29-36, CountNumInBed.py:35-44) over `lines` (bytes); tally =
+    [lines, kept lines], updated as it goes so that an exception leaves what was counted; out: a binary file or None"""
+    for row in lines:
+        tally[0] += 1
+        tok = row.split()
+        ctg, pos = tok[0], tok[1]                           # one token: IndexError
+        pos = int(pos)                                       # ValueError
+        iv = tree.get(ctg.decode("ascii", "replace"))        # (the BED's names were read as ASCII text)
+        if iv is None or not iv.hit(pos):                    # a contig the BED lacks drops the line: no KeyError
+            continue
+        tally[1] += 1
+        if out is not None:
+            out.write(row)
+
+
+def choose_items_host(input_fn, bed_fn, out):
+    """ChooseItemInBed.Calc: the lines of input_fn whose (contig, position) a BED interval covers, written unchanged (own
+    line ending or none) to the binary file `out`.  A line with fewer than two tokens, or a position int() refuses, raises
+    IndexError / ValueError after the lines in front of it have been written.  -> (lines, kept lines)"""
+    tally = [0, 0]
+    _host_lines(_gz_byte_lines(input_fn), bed_tree(bed_fn), out, tally)
+    return tuple(tally)
+
+
+def count_items_host(input_fn, bed_fn):
+    """CountNumInBed.Calc -> (total, overlapped)"""
+    tally = [0, 0]
+    _host_lines(_gz_byte_lines(input_fn), bed_tree(bed_fn), None, tally)
+    return tuple(tally)
+
+
+def _table_of(intervals):
+    iv = _Intervals()
+    for b, e in intervals:
+        iv.addi(b, e)
+    return iv.table()
+
+
+def sample_positions_host(ctg, start, end, prob, intervals, seed):
+    """RandomSampling.py:64-68 -> the positions i of range(start, end) (end exclusive) that lie in one of `intervals`
+    (half-open (begin, end) pairs; None: there is no BED) and whose draw u(i) = draws.draws(seed, draws.RANDOM, ctg, i)
+    is <= prob, ascending, int64.  Computed over tiles of SAMPLE_TILE positions."""
+    out = []
+    b, emax = _table_of(intervals) if intervals is not None else (None, None)
+    tile = max(int(SAMPLE_TILE), 1)
+    for first in range(start, end, tile):
+        pos = np.arange(first, min(first + tile, end), dtype=np.int64)
+        if intervals is not None:
+            if not len(b):
+                break
+            k = np.searchsorted(b, pos, side="right")        # _Intervals.hit over the tile
+            pos = pos[(k > 0) & (emax[np.maximum(k - 1, 0)] > pos)]
+        out.append(pos[draws.draws(seed, draws.RANDOM, ctg, pos) <= prob])
+    return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
+
+
+def prefix_lines(block, prefix, at_line_start):
+    """`block` (bytes, a piece of a file) with the byte `prefix` put in front of every line that starts inside it ->
+    (bytes, "the next piece starts a line")"""
+    a = np.frombuffer(block, dtype=np.uint8)
+    if not len(a):
+        return b"", at_line_start
+    starts = np.flatnonzero(a[:-1] == 10) + 1
+    if at_line_start:
+        starts = np.concatenate((np.zeros(1, dtype=starts.dtype), starts))
+    return np.insert(a, starts, prefix).tobytes(), bool(a[-1] == 10)
+
+
+# ---- the device route -------------------------------------------------------------------------------------------------------
+class _Timer(object):
+    """HIP events around a device call when TIMES is a dict; read after the caller's next synchronisation"""
+
+    def __init__(self, torch, name):
+        self.name, self.on = name, TIMES is not None
+        if self.on:
+            self.a, self.b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def __enter__(self):
+        if self.on:
+            self.a.record()
+        return self
+
+    def __exit__(self, *exc):
+        if self.on:
+            self.b.record()
+
+    def read(self):
+        if self.on:
+            self.b.synchronize()
+            TIMES[self.name] = TIMES.get(self.name, 0.0) + self.a.elapsed_time(self.b)
+
+
+class _RestToHost(Exception):
+    """a slab holds a line only the definition answers: at = offset in the buffer of the first unconsumed line"""
+
+    def __init__(self, at, reason):
+        Exception.__init__(self, reason)
+        self.at = at
+
+
+class _ItemWalk(object):
+    """the device side of choose / count: the BED tables, then the item file slab by slab"""
+
+    def __init__(self, device, bed_fn, out):
+        import torch
+        self.torch, self.device, self.out = torch, device, out
+        self.rd = _TruthReader(device)
+        self.lib, self.P = self.rd.lib, self.rd._p
+        self.st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        self.total = self.kept = 0
+        self.bytes_per_line = 16.0                           # sizes the line table: the slab before says what to expect
+        self.pinned = None
+        E = lambda n, dt=torch.int64: torch.empty(n, dtype=dt, device=device)
+        self.E = E
+        need = ctypes.c_int64()
+        (begin, end, run, run_ctg, nruns), = self.rd.read(bed_fn, TRUTH_FORMAT_BED)
+        nb, self.nctg = int(begin.numel()), len(self.rd.names)
+        self.bed_off, self.bed_begin, self.bed_emax = E(self.nctg + 1), E(nb), E(nb)
+        _lib.check(self.lib.cv_bed_table_workspace(nb, ctypes.byref(need)))
+        ws = E(max(need.value, 1), torch.uint8)
+        _lib.check(self.lib.cv_bed_table_dev(nb, self.P(begin), self.P(end), self.P(run), self.P(run_ctg), nruns, self.nctg,
+                                             self.P(self.bed_off), self.P(self.bed_begin), self.P(self.bed_emax), self.P(ws),
+                                             need.value, self.st))
+        torch.cuda.current_stream(device).synchronize()       # (the workspace and the rows may go)
+
+    def _run_ids(self, buf, at, n, tok, runs):
+        """the BED contig id of each run from its start token, -1 for a contig the BED lacks"""
+        t = tok[:runs].cpu().numpy()
+        idx = np.repeat(t[:, 0] - np.cumsum(np.concatenate(([0], t[:-1, 1]))), t[:, 1]) + np.arange(int(t[:, 1].sum()))
+        raw = buf[at:at + n][self.torch.from_numpy(idx).to(self.device)].cpu().numpy().tobytes()
+        ids, k = [], 0
+        for ln in t[:, 1].tolist():
+            ids.append(self.rd.ids.get(raw[k:k + ln], -1))
+            k += ln
+        return self.torch.from_numpy(np.array(ids, dtype=np.int32)).to(self.device)
+
+    def slab(self, buf, lo, hi, padded_end):
+        """the two passes over buf[lo:hi], again while the line table is full -> bytes consumed.  padded_end: the offset
+        behind a newline this reader appended to the file's last line (None: there is none): that byte is not written"""
+        torch, lib, P, E = self.torch, self.lib, self.P, self.E
+        want_text = 1 if self.out is not None else 0
+        done = 0
+        need = ctypes.c_int64()
+        while lo + done < hi:
+            at, n = lo + done, hi - lo - done
+            text_ptr = ctypes.c_void_p(buf.data_ptr() + at)
+            max_lines = min(int(n / self.bytes_per_line * 1.25) + 1024, n)
+            _lib.check(lib.cv_item_lines_workspace(n, max_lines, ctypes.byref(need)))
+            ws = E(need.value, torch.uint8)
+            pos, run, off, ln = E(max_lines), E(max_lines, torch.int32), E(max_lines), E(max_lines)
+            tok, info_dev = E((max_lines, 2)), E(8)
+            with _Timer(torch, "lines") as tm:
+                _lib.check(lib.cv_item_lines_dev(text_ptr, n, max_lines, P(pos), P(run), P(off), P(ln), P(tok), P(info_dev), P(ws),
+                                                 need.value, self.st))
+            used, lines, rows, _skipped, host, runs = info_dev.cpu().tolist()[:6]
+            tm.read()
+            if host:
+                raise _RestToHost(at, "%d line(s) only the host loop defines the result for (a blank line, fewer than two tokens, "
+                                      "a position that is not canonical decimal, '\\r', bytes outside printable ASCII, ...)" % host)
+            if rows:
+                run_ctg = self._run_ids(buf, at, n, tok, runs)
+                _lib.check(lib.cv_items_keep_workspace(rows, ctypes.byref(need)))
+                ws = E(need.value, torch.uint8)
+                text_out = E(used, torch.uint8) if want_text else None
+                cnt = E(4)
+                with _Timer(torch, "keep") as tm:
+                    _lib.check(lib.cv_items_keep_dev(text_ptr, n, rows, P(pos), P(run), P(off), P(ln), P(run_ctg), runs, self.nctg,
+                                                     P(self.bed_off), P(self.bed_begin), P(self.bed_emax), want_text, P(text_out),
+                                                     used if want_text else 0, P(cnt), P(ws), need.value, self.st))
+                    last = None
+                    if want_text and padded_end is not None and at + used == padded_end:
+                        # is the file's last line kept?  Then the newline this reader gave it stays behind
+                        last = E(4)
+                        _lib.check(lib.cv_items_keep_dev(text_ptr, n, 1, P(pos[rows - 1:]), P(run[rows - 1:]), P(off[rows - 1:]),
+                                                         P(ln[rows - 1:]), P(run_ctg), runs, self.nctg, P(self.bed_off),
+                                                         P(self.bed_begin), P(self.bed_emax), 0, None, 0, P(last), P(ws), need.value,
+                                                         self.st))
+                _rows, kept, nbytes, _zero = cnt.cpu().tolist()
+                tm.read()
+                if last is not None and last.cpu().tolist()[1]:
+                    nbytes -= 1
+                if want_text and nbytes:
+                    if self.pinned is None or self.pinned.numel() < nbytes:
+                        self.pinned = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8).pin_memory()
+                    self.pinned[:nbytes].copy_(text_out[:nbytes])
+                    self.out.write(self.pinned[:nbytes].numpy().tobytes())
+                self.kept += kept
+            self.total += lines
+            _counts["device_lines"] += lines
+            done += used
+            if lines:
+                self.bytes_per_line = max(used / float(lines), 2.0)
+            if lines < max_lines:
+                break
+        return done
+
+    def walk(self, input_fn):
+        """every slab of the file; _RestToHost / _TruthHandOver with .blocks = the bytes the host continues over"""
+        import warnings
+        torch = self.torch
+        slab_bytes = max(int(utils_v2.TRUTH_SLAB_BYTES), 1)
+        carry = torch.empty(0, dtype=torch.uint8, device=self.device)
+        chunks = _truth_chunks(input_fn, slab_bytes)
+        try:
+            kind, piece = next(chunks, (None, None))
+            while kind is not None:
+                nxt = next(chunks, (None, None))
+                last, head = nxt[0] is None, int(carry.numel())
+                if kind == "host" and not last and not (np.asarray(piece) == 10).any():
+                    # no line ends in this piece: it joins the unfinished line without a pass of its own
+                    with warnings.catch_warnings():
+                        warnings.simplefilter("ignore")
+                        carry = torch.cat((carry, torch.from_numpy(piece).to(self.device)))
+                    kind, piece = nxt
+                    continue
+                if kind == "bgzf":
+                    buf = self.rd._inflate(piece, head)
+                    n = head + piece.n
+                else:
+                    n = head + len(piece)
+                    buf = torch.empty(n + 1, dtype=torch.uint8, device=self.device)
+                    with warnings.catch_warnings():
+                        warnings.simplefilter("ignore")              # (a read-only source: the memory map, a bytes object)
+                        buf[head:n].copy_(torch.from_numpy(piece))
+                if head:
+                    buf[:head].copy_(carry)
+                # a last line without a newline is a line: it gets one here, which is not written; behind a newline
+                # nothing is added (a blank line is the definition's IndexError)
+                padded_end = None
+                if last and n and int(buf[n - 1]) != 10:
+                    buf[n:n + 1].fill_(10)
+                    n += 1
+                    padded_end = n
+                lo, hi = 0, min(head + slab_bytes, n)
+                # several windows over one buffer (BGZF members overshoot the slab; slabs shorter than a line): where the
+                # lines end says which windows are worth a pass at all
+                ends = (buf[:n] == 10).nonzero().flatten().cpu().numpy() + 1 if hi < n else None
+                try:
+                    while True:
+                        stop = hi
+                        if ends is not None:
+                            k = int(np.searchsorted(ends, hi, side="right"))
+                            stop = int(ends[k - 1]) if k else 0
+                        if stop > lo:
+                            lo += self.slab(buf, lo, stop, padded_end)
+                        if hi >= n:
+                            break
+                        hi = min(hi + slab_bytes, n)
+                except _RestToHost as e:
+                    e.blocks = itertools.chain([buf[e.at:n - (padded_end is not None)].cpu().numpy().tobytes()],
+                                               _host_blocks(itertools.chain([nxt], chunks)))
+                    raise
+                carry = buf[lo:n].clone()
+                kind, piece = nxt
+        except (_RestToHost, _TruthHandOver):
+            raise
+        except BaseException:
+            chunks.close()
+            raise
+
+
+def _host_blocks(chunks):
+    """what is left of _truth_chunks as bytes on the host (a stream that breaks off ends there, as the pipe of `gzip -fdc` does)"""
+    try:
+        for kind, piece in chunks:
+            if kind is None:
+                return
+            if kind == "host":
+                yield np.asarray(piece).tobytes()
+            else:
+                for i in range(len(piece.table)):
+                    yield piece.inflate_member(i).tobytes()
+    except (_TruthHandOver, _lib.CvError):
+        return
+
+
+def _items_host(input_fn, bed_fn, out, handed_over=False):
+    _counts["handed_over_calls"] += int(handed_over)
+    _counts["host_calls"] += 1
+    return choose_items_host(input_fn, bed_fn, out) if out is not None else count_items_host(input_fn, bed_fn)
+
+
+def _items(input_fn, bed_fn, out, device=None):
+    """choose (out: a binary file) or count (out: None) by route() -> (lines, kept lines).  (The device route reads the BED
+    through utils_v2._TruthReader, whose lines count in utils_v2.truth_table_counts() as well.)"""
+    if route(input_fn) != "device":
+        return _items_host(input_fn, bed_fn, out)
+    import torch
+    device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+    with torch.cuda.device(device):
+        try:
+            walk = _ItemWalk(device, bed_fn, out)
+        except _TruthHandOver:                               # the BED: nothing has been written, the whole call is the host's
+            return _items_host(input_fn, bed_fn, out, handed_over=True)
+        try:
+            walk.walk(input_fn)
+        except _TruthHandOver:
+            # the item file is nothing the native readers take: the host's pipe reads it.  (A stream that breaks off
+            # LATER ends the device's walk where the pipe of `gzip -fdc` ends too: what was consumed stays.)
+            if walk.total == 0:
+                return _items_host(input_fn, bed_fn, out, handed_over=True)
+        except _RestToHost as e:
+            _counts["handed_over_calls"] += 1
+            tally = [0, 0]
+            try:
+                _host_lines(_lines_of(e.blocks), bed_tree(bed_fn), out, tally)
+            finally:
+                _counts["host_lines"] += tally[0]
+            return walk.total + tally[0], walk.kept + tally[1]
+    _counts["device_calls"] += 1
+    return walk.total, walk.kept
+
+
+def choose_items(input_fn, bed_fn, out, device=None):
+    """ChooseItemInBed by route(): choose_items_host, or the device route with the same bytes, counts and exceptions"""
+    return _items(input_fn, bed_fn, out, device)
+
+
+def count_items(input_fn, bed_fn, device=None):
+    """CountNumInBed by route() -> (total, overlapped)"""
+    return _items(input_fn, bed_fn, None, device)
+
+
+def sample_positions_device(ctg, start, end, prob, intervals, seed, device=None):
+    """sample_positions_host on the device: the contig's table uploaded once, [start, end) walked in tiles of SAMPLE_TILE"""
+    import torch
+    if end <= start or (intervals is not None and not len(intervals)):
+        return np.zeros(0, dtype=np.int64)
+    device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+    lib = _lib.load()
+    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    out = []
+    with torch.cuda.device(device):
+        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        nbed, b_dev, e_dev = 0, None, None
+        if intervals is not None:
+            b, emax = _table_of(intervals)
+            nbed, b_dev, e_dev = len(b), torch.from_numpy(b).to(device), torch.from_numpy(emax).to(device)
+        tile = max(int(SAMPLE_TILE), 1)
+        need = ctypes.c_int64()
+        _lib.check(lib.cv_sample_positions_workspace(min(tile, end - start), ctypes.byref(need)))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=device)
+        cnt = torch.empty(2, dtype=torch.int64, device=device)
+        h = draws.fnv1a32(ctg)
+        for first in range(start, end, tile):
+            count = min(tile, end - first)
+            cap = SAMPLE_FIRST_CAP if SAMPLE_FIRST_CAP is not None else int(count * min(max(prob, 0.0), 1.0) * 1.05) + 4096
+            while True:
+                cap = max(min(cap, count), 1)
+                pos = torch.empty(cap, dtype=torch.int64, device=device)
+                with _Timer(torch, "sample") as tm:
+                    _lib.check(lib.cv_sample_positions_dev(int(seed), h, first, count, float(prob), nbed, P(b_dev), P(e_dev), P(pos), cap,
+                                                           P(cnt), P(ws), need.value, st))
+                wrote, would = cnt.cpu().tolist()
+                tm.read()
+                if wrote == would:
+                    break
+                cap = would                                  # the room was too small: the tile again
+            _counts["device_positions"] += count
+            out.append(pos[:wrote].cpu().numpy())
+    return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
+
+
+def sample_positions(ctg, start, end, prob, intervals, seed, device=None):
+    """the sampled positions by route() (RandomSampling obeys CV_BED_ITEMS too)"""
+    if route() == "device":
+        got = sample_positions_device(ctg, start, end, prob, intervals, seed, device)
+        _counts["device_calls"] += 1
+        return got
+    _counts["host_calls"] += 1
+    return sample_positions_host(ctg, start, end, prob, intervals, seed)

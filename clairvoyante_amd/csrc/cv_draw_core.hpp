@@ -7,7 +7,8 @@
 //   key     = (seed lo32, seed hi32)
 //   counter = (pos lo32, pos hi32, stream | late << 8, h)
 // pos the 1-based coordinate of the row, h = FNV-1a-32 of the contig name's bytes, stream 0 = the gen4Training sample,
-// 1 = the pairing with non-variants, late = 1 for the second ("late") entry of a position in the candidate pass.
+// 1 = the pairing with non-variants, 2 = RandomSampling's draw per position of a range (draws.RANDOM: keep if u <= prob),
+// late = 1 for the second ("late") entry of a position in the candidate pass.
 //   u = ((x0 << 32 | x1) >> 11) * 2^-53   in [0, 1), a double
 // stream 0 keeps a row unless u > outputProb, stream 1 keeps it if u < r -- the reference's two comparisons.
 #pragma once

@@ -22,6 +22,11 @@
 // 99, not empty); then the label of (REF, ALT, p1, p2) as for format VAR.  GetTruth reads bytes and splits at ASCII
 // whitespace; its row then passes through the truth list's reader, so from the position on the whole line is held to the
 // byte rule above.
+//
+// Format ITEM is a line of any file whose first two columns are contig and position (bed_items.choose_items_host: a text
+// tensor, a truth list), read as bytes: a ROW needs two tokens, the second canonical decimal; nothing behind them is
+// looked at beyond the byte rule.  There is no SKIP: a line without a token is the definition's IndexError, so HOST.  The
+// contig token is compared byte for byte and never becomes part of a key, so a ':' in it is no concern.
 #pragma once
 #include <stdint.h>
 
@@ -34,7 +39,7 @@
 namespace cvt {
 
 enum { ROW = 0, SKIP = 1, HOST = 2 };
-enum { FMT_VAR = 0, FMT_BED = 1, FMT_VCF = 2 };
+enum { FMT_VAR = 0, FMT_BED = 1, FMT_VCF = 2, FMT_ITEM = 3 };
 constexpr int LINE_CAP = 8192;
 constexpr int MAX_DIGITS = 12;                  // utils_v2.canonical_coordinate
 
@@ -210,12 +215,12 @@ CVT_FN void verdict(const uint8_t *line, int64_t n64, int format, const Filter *
         if (b < 0x21 || b > 0x7E) return;
         any = true;
     }
-    if (!any) { out->status = SKIP; return; }
+    if (!any) { if (format != FMT_ITEM) out->status = SKIP; return; }
     int from = 0, off[6], len[6];
-    const int need = format == FMT_BED ? 3 : 6;
+    const int need = format == FMT_BED ? 3 : format == FMT_ITEM ? 2 : 6;
     for (int t = 0; t < need; ++t)
         if (!next_token(line, n, &from, &off[t], &len[t])) return;
-    for (int k = 0; k < len[0]; ++k)
+    for (int k = 0; format != FMT_ITEM && k < len[0]; ++k)
         if (line[off[0] + k] == ':') return;                     // utils_v2.contig_token_ok (NUL and >= 0x80 went above)
     int64_t a = 0, b = 0;
     if (!canonical(line + off[1], len[1], &a)) return;
@@ -223,7 +228,7 @@ CVT_FN void verdict(const uint8_t *line, int64_t n64, int format, const Filter *
         if (!canonical(line + off[2], len[2], &b)) return;
         b -= 1;
         if (b == a) b += 1;
-    } else {
+    } else if (format != FMT_ITEM) {
         float scratch[16];
         if (!label_of(line + off[2], len[2], line + off[3], len[3], line + off[4], len[4], line + off[5], len[5],
                       want_label ? out->label : scratch))

@@ -1,6 +1,7 @@
 """The keyed draws of the training-set routes (csrc/cv_draw_core.hpp): Philox4x32-10 keyed by (seed; position, contig
 name, stream, late), the same text on host and device.  Stream SAMPLE is ExtractVariantCandidates --gen4Training
-(keep unless u > outputProb, ExtractVariantCandidates.py:203), stream PAIR is PairWithNonVariants (keep if u < r, :119).
+(keep unless u > outputProb, ExtractVariantCandidates.py:203), stream PAIR is PairWithNonVariants (keep if u < r, :119),
+stream RANDOM is RandomSampling (keep if u <= prob, RandomSampling.py:67).
 """
 import ctypes
 import logging
@@ -10,7 +11,7 @@ import numpy as np
 
 from . import _lib
 
-SAMPLE, PAIR = 0, 1
+SAMPLE, PAIR, RANDOM = 0, 1, 2
 
 
 def fnv1a32(name):

@@ -531,6 +531,62 @@ int cv_truth_tables_dev(int64_t n, const int64_t *pos_dev, const float *label_de
                         int64_t *truth_pos_dev, float *labels_dev, int64_t *every_off_dev, int64_t *every_pos_dev,
                         int64_t *counts_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ---- the dataPrepScripts helpers on the device (csrc/cv_beditems_dev.hip, csrc/cv_beditems_core.hpp) ------------------
+ * ChooseItemInBed / CountNumInBed keep the LINES of a file whose first two columns are contig and position when a BED
+ * interval covers the position; RandomSampling keeps the POSITIONS of a range that a BED covers and a keyed draw selects.
+ * The host loops of clairvoyante_amd/bed_items.py stay the definitions.  As above, every *_dev call is enqueued on
+ * `stream` and neither allocates nor synchronises; workspaces (256-byte aligned) are sized by the *_workspace functions.
+ *
+ * cv_item_lines_dev, per slab of item text: the lines that END inside text_dev[0, len) (at most max_lines), each given a
+ * verdict by csrc/cv_truth_core.hpp in format CV_TRUTH_FORMAT_ITEM -- a ROW (two tokens, the second canonical decimal of
+ * at most CV_TRAINSET_MAX_DIGITS digits; what follows is held to the byte rule only) or HOST (a blank line, one token,
+ * "007", "+5", '\r', a byte outside 0x21..0x7E / space / tab, more than CV_TRUTH_LINE_CAP bytes).  There is no SKIP.
+ * Row r = the r-th ROW:
+ *   pos_dev[r] int64      the position;
+ *   run_dev[r] int32      index of the row's contig run (as in cv_truth_lines_dev);
+ *   off_dev[r] int64      offset of the line's first byte in the slab;
+ *   len_dev[r] int64      its length, the newline included;
+ *   tok_dev[k][2] int64   offset in the slab and length of the contig token that starts run k;
+ *   info_dev[8] int64     {bytes consumed, lines, rows, 0, host, runs, 0, 0}.
+ * The row arrays hold max_lines entries.  cv_item_lines_host_form: the same core on the CPU over HOST pointers.
+ *
+ * cv_items_keep_dev, over the n rows of one slab: run_ctg_dev[nruns] = the BED contig id of each run, -1 for a contig the
+ * BED lacks (the host compares the run-start tokens; the rows may be a part of the slab's rows, so nruns may exceed n);
+ * bed_off / bed_begin / bed_emax are cv_bed_table_dev's tables over nctg contigs.  A row is kept when its id is not -1 and upper_bound(begin, pos) = k > 0 and emax[k - 1] > pos.  With
+ * want_text the kept lines' bytes go to out_text_dev[0, out_cap) in order, one behind the other (an exclusive sum of their
+ * lengths places them; one wave copies one line, in 16-byte granules where source and destination agree modulo 16); a
+ * line that would not fit, or that does not lie inside the slab, is not copied.  counts_dev[4] = {rows, kept rows, kept
+ * bytes, 0}; without want_text neither the sum nor the copy runs and kept bytes is 0.
+ * cv_items_keep_host_form: the same on the CPU, the copy lane by lane.
+ *
+ * cv_sample_positions_dev, one tile of positions first .. first + count - 1 of the contig whose name hashes to h
+ * (FNV-1a-32): a position is kept when the contig's sorted table bed_begin_dev / bed_emax_dev[nbed] covers it (nbed = 0:
+ * no BED, every position passes) and cv_draw(seed, 2, h, pos, 0) <= prob in double.  The kept positions go to
+ * out_pos_dev[0, cap) ascending; count_dev[2] = {positions written, positions kept}: where they differ `cap` was too
+ * small and the caller repeats the tile.  The workspace depends on count (at most CV_SAMPLE_MAX_TILE) alone.          */
+#define CV_TRUTH_FORMAT_ITEM 3
+#define CV_SAMPLE_MAX_TILE ((int64_t)1 << 28)
+int cv_item_lines_workspace(int64_t len, int64_t max_lines, int64_t *bytes);
+int cv_item_lines_dev(const char *text_dev, int64_t len, int64_t max_lines, int64_t *pos_dev, int32_t *run_dev, int64_t *off_dev,
+                      int64_t *len_dev, int64_t *tok_dev, int64_t *info_dev, void *workspace_dev, int64_t workspace_bytes,
+                      void *stream);
+int cv_item_lines_host_form(const char *text, int64_t len, int64_t max_lines, int64_t *pos, int32_t *run, int64_t *off,
+                            int64_t *llen, int64_t *tok, int64_t *info);
+int cv_items_keep_workspace(int64_t n, int64_t *bytes);
+int cv_items_keep_dev(const char *text_dev, int64_t len, int64_t n, const int64_t *pos_dev, const int32_t *run_dev,
+                      const int64_t *off_dev, const int64_t *len_dev, const int32_t *run_ctg_dev, int64_t nruns, int32_t nctg,
+                      const int64_t *bed_off_dev, const int64_t *bed_begin_dev, const int64_t *bed_emax_dev, int want_text,
+                      char *out_text_dev, int64_t out_cap, int64_t *counts_dev, void *workspace_dev, int64_t workspace_bytes,
+                      void *stream);
+int cv_items_keep_host_form(const char *text, int64_t len, int64_t n, const int64_t *pos, const int32_t *run, const int64_t *off,
+                            const int64_t *llen, const int32_t *run_ctg, int64_t nruns, int32_t nctg, const int64_t *bed_off,
+                            const int64_t *bed_begin, const int64_t *bed_emax, int want_text, char *out_text, int64_t out_cap,
+                            int64_t *counts);
+int cv_sample_positions_workspace(int64_t count, int64_t *bytes);
+int cv_sample_positions_dev(uint64_t seed, uint32_t h, int64_t first, int64_t count, double prob, int64_t nbed,
+                            const int64_t *bed_begin_dev, const int64_t *bed_emax_dev, int64_t *out_pos_dev, int64_t cap,
+                            int64_t *count_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* c-blosc 1.x chunk codec for the 500-item blocks of the `.bin` training file
  * (utils_v2.py:159-186 blosc.pack_array(cname='lz4hc'), :189-207 blosc.unpack_array;
  * tensor2Bin.py:24-28).  Decoder: LZ4/LZ4HC streams, byte shuffle, split blocks, memcpy'd
