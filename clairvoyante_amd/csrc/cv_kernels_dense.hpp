@@ -402,14 +402,18 @@ __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_t
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = (blockIdx.x * WAVES + wid) * GR;
     CV_STAMP_BEGIN
-    // this wave's activation fragments: byte offsets from in_tm (a scalar base + a 32-bit vector offset per group
-    // instead of a 64-bit pointer: 2 VGPRs less per group, which the fc5 + heads tail of EPI 3 needs; a pass is at most
-    // 4 096 groups x 288 fragments = 1.2 GB)
+    // this wave's activation fragments: byte offsets from the first group of the WORKGROUP (a scalar base + a 32-bit
+    // vector offset per group instead of a 64-bit pointer: 2 VGPRs less per group, which the fc5 + heads tail of EPI 3
+    // needs).  The base moves with the workgroup, so the offset spans WAVES * GR groups whatever the pass holds: taken
+    // from in_tm itself it wrapped at 2^32 bytes, which fc4's input reaches at 14 564 groups of 288 fragments -- a pass
+    // of 233 024 candidates, option "chunk" allows 2^22 -- and the wave then read another group's activations.
+    const int gw = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES * GR);       // (< G: the grid is ceil(G / (WAVES GR)))
+    const f4 *const in_wg = in_tm + (size_t)gw * KBA * 64;
     unsigned bo[GR];
 #pragma unroll
     for (int r = 0; r < GR; r++) {
         const int gl = g + r < G ? g + r : G - 1;
-        bo[r] = (unsigned)((((size_t)gl * KBA + kb0) * 64 + lane) * sizeof(f4));
+        bo[r] = (unsigned)((((size_t)(gl - gw) * KBA + kb0) * 64 + lane) * sizeof(f4));
     }
     const f4 zero = (f4){0.f, 0.f, 0.f, 0.f};
     f4 acc[GR][NB];
@@ -444,7 +448,7 @@ __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_t
     };
     auto load_frag_off = [&](unsigned byte_off) {
         f4 v;
-        asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(v) : "v"(byte_off), "s"(in_tm) : "memory");
+        asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(v) : "v"(byte_off), "s"(in_wg) : "memory");
         return v;
     };
     stage_async(0, 0);
@@ -768,8 +772,12 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 2) void dense_rag(const f4 *__r
 #pragma unroll
     for (int i = 0; i < NBS; i++) tj[i] = __builtin_amdgcn_readfirstlane(i < n0 ? t0 + i : (i < c ? i - n0 : 0));
     const int ga = g0 < G ? g0 : G - 1, gb = g0 + 1 < G ? g0 + 1 : G - 1;
-    const unsigned bo0 = (unsigned)((((size_t)ga * KB) * 64 + lane) * sizeof(f4));
-    const unsigned bo1 = (unsigned)((((size_t)gb * KB) * 64 + lane) * sizeof(f4));
+    // (32-bit offsets from the first group of the WORKGROUP's units, as in dense_tm: from in_tm itself they wrap at 2^32 bytes)
+    const int gw0 = __builtin_amdgcn_readfirstlane(bx * HW * (ca + cb) / NBS);
+    const int gw = gw0 < G ? gw0 : G - 1;
+    const f4 *const in_wg = in_tm + (size_t)gw * KB * 64;
+    const unsigned bo0 = (unsigned)((((size_t)(ga - gw) * KB) * 64 + lane) * sizeof(f4));
+    const unsigned bo1 = (unsigned)((((size_t)(gb - gw) * KB) * 64 + lane) * sizeof(f4));
     const f4 zero = (f4){0.f, 0.f, 0.f, 0.f};
     f4 acc[NBS];
 #pragma unroll
@@ -785,7 +793,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 2) void dense_rag(const f4 *__r
     };
     auto load_frag_off = [&](unsigned byte_off) {
         f4 v;
-        asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(v) : "v"(byte_off), "s"(in_tm) : "memory");
+        asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(v) : "v"(byte_off), "s"(in_wg) : "memory");
         return v;
     };
     // the k loop for a piece of CC positions of which the first N0 belong to the first group (both compile-time).

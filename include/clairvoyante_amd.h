@@ -185,7 +185,8 @@ int cv_get_activation(cv_model *m, int layer, float *dst_dev, int64_t n, void *s
 int cv_selu_sweep(int device, uint32_t lo_bits, uint32_t hi_bits, uint64_t *violations, uint64_t *checksum);
 
 /* knobs: "impl" (0 = plain one-thread-per-output kernels, 1 = MFMA tile kernels),
- * "chunk" (candidates per internal pass), "profile" (0/1, see cv_kernel_times), "keep_activations" (0/1, default 0:
+ * "chunk" (candidates per internal pass, 16 .. 2^22, an error beyond; default 65 536; the workspace of a pass takes 41 KB
+ * per candidate of the full topology), "profile" (0/1, see cv_kernel_times), "keep_activations" (0/1, default 0:
  * a pass whose fc5 + heads ride on the tail of the fc4 kernel -- variant bit 10 -- also stores the fc4 / fc5 maps,
  * which then only cv_get_activation layers 4 / 5 read; off, those layers report an error after such a pass and the
  * kernel writes a third of the bytes), "train_overlap" (0/1: weight
