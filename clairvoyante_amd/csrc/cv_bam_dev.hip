@@ -30,17 +30,8 @@
 
 #include "../../include/clairvoyante_amd.h"
 #include "cv_bam_core.hpp"
+#include "cv_dev_scan.hpp"
 
-void cv_set_error(const char *fmt, ...);
-
-#define BD_HIP(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess) {                                                                   \
-            cv_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return 1;                                                                             \
-        }                                                                                         \
-    } while (0)
 
 namespace {
 
@@ -190,7 +181,7 @@ int ensure(devbuf &b, size_t bytes)
     if (bytes <= b.cap) return 0;
     if (b.p) { hipFree(b.p); b.p = nullptr; b.cap = 0; }
     const size_t want = bytes + bytes / 4 + 256;
-    BD_HIP(hipMalloc(&b.p, want));
+    CV_HIP(hipMalloc(&b.p, want));
     b.cap = want;
     return 0;
 }
@@ -213,7 +204,7 @@ extern "C" int cv_bam_dev_create(int device, cv_bam_dev **out)
 {
     if (!out) { cv_set_error("cv_bam_dev_create: null argument"); return 1; }
     int ndev = 0;
-    BD_HIP(hipGetDeviceCount(&ndev));
+    CV_HIP(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) { cv_set_error("cv_bam_dev_create: device %d not present (%d visible)", device, ndev); return 1; }
     cv_bam_dev *d = new (std::nothrow) cv_bam_dev();
     if (!d) { cv_set_error("cv_bam_dev_create: out of host memory"); return 1; }
@@ -276,26 +267,26 @@ static int inflate_slab(cv_bam_dev *d, cv_bam *b, slab &s, hipStream_t st, int64
     std::vector<uint8_t> status((size_t)s.members);
     {
         sync_on_exit wait{st};
-        if (s.tail) BD_HIP(hipMemcpyAsync(s.sb, (const uint8_t *)d->stream[d->cur].p + d->from, (size_t)s.tail, hipMemcpyDeviceToDevice, st));
+        if (s.tail) CV_HIP(hipMemcpyAsync(s.sb, (const uint8_t *)d->stream[d->cur].p + d->from, (size_t)s.tail, hipMemcpyDeviceToDevice, st));
         d->cur = nxt;
-        BD_HIP(hipMemcpyAsync(d->comp.p, s.comp, (size_t)s.comp_bytes, hipMemcpyHostToDevice, st));
-        BD_HIP(hipMemcpyAsync(d->table.p, s.table, (size_t)s.members * 32, hipMemcpyHostToDevice, st));
-        BD_HIP(hipMemsetAsync(d->status.p, 0, (size_t)s.members, st));
-        BD_HIP(hipEventRecord(d->ev[0], st));
+        CV_HIP(hipMemcpyAsync(d->comp.p, s.comp, (size_t)s.comp_bytes, hipMemcpyHostToDevice, st));
+        CV_HIP(hipMemcpyAsync(d->table.p, s.table, (size_t)s.members * 32, hipMemcpyHostToDevice, st));
+        CV_HIP(hipMemsetAsync(d->status.p, 0, (size_t)s.members, st));
+        CV_HIP(hipEventRecord(d->ev[0], st));
         if (cv_inflate_bgzf_dev((const uint8_t *)d->comp.p, (const int64_t *)d->table.p, s.members, s.sb + s.tail, s.inflated,
                                 (uint8_t *)d->status.p, st)) return 1;
-        BD_HIP(hipEventRecord(d->ev[1], st));
-        BD_HIP(hipMemcpyAsync(status.data(), d->status.p, (size_t)s.members, hipMemcpyDeviceToHost, st));
+        CV_HIP(hipEventRecord(d->ev[1], st));
+        CV_HIP(hipMemcpyAsync(status.data(), d->status.p, (size_t)s.members, hipMemcpyDeviceToHost, st));
     }
     float ms = 0.f;
-    BD_HIP(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
+    CV_HIP(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
     d->ms[5] += ms;
     for (int64_t m = 0; m < s.members; m++) {
         if (status[(size_t)m] == CV_BGZF_OK) { counts[2] += 1; continue; }
         uint8_t tmp[65536];
         if (cv_bam_plan_inflate_host(b, m, tmp)) return 1;
         const int64_t isize = (int64_t)((uint64_t)s.table[4 * m + 3] >> 32);
-        if (isize) BD_HIP(hipMemcpy(s.sb + s.tail + s.table[4 * m + 2], tmp, (size_t)isize, hipMemcpyHostToDevice));
+        if (isize) CV_HIP(hipMemcpy(s.sb + s.tail + s.table[4 * m + 2], tmp, (size_t)isize, hipMemcpyHostToDevice));
         counts[3] += 1;
     }
     return 0;
@@ -319,17 +310,17 @@ static int walk_slab(cv_bam_dev *d, slab &s, const cvb::view &v, hipStream_t st,
         ensure(d->sparse, (size_t)part.back() * 4) || ensure(d->wout, (size_t)nwalk * sizeof(walk_out))) return 1;
     {
         sync_on_exit wait{st};
-        BD_HIP(hipMemcpyAsync(d->bounds.p, bounds.data(), bounds.size() * 8, hipMemcpyHostToDevice, st));
-        BD_HIP(hipMemcpyAsync(d->part.p, part.data(), part.size() * 8, hipMemcpyHostToDevice, st));
-        BD_HIP(hipEventRecord(d->ev[2], st));
+        CV_HIP(hipMemcpyAsync(d->bounds.p, bounds.data(), bounds.size() * 8, hipMemcpyHostToDevice, st));
+        CV_HIP(hipMemcpyAsync(d->part.p, part.data(), part.size() * 8, hipMemcpyHostToDevice, st));
+        CV_HIP(hipEventRecord(d->ev[2], st));
         bam_walk<<<(unsigned)((nwalk + 63) / 64), 64, 0, st>>>(s.sb, s.lim, (const int64_t *)d->bounds.p, (const int64_t *)d->part.p, nwalk, v,
                                                               (uint32_t *)d->sparse.p, (walk_out *)d->wout.p);
-        BD_HIP(hipGetLastError());
-        BD_HIP(hipEventRecord(d->ev[3], st));
-        BD_HIP(hipMemcpyAsync(wout.data(), d->wout.p, (size_t)nwalk * sizeof(walk_out), hipMemcpyDeviceToHost, st));
+        CV_HIP(hipGetLastError());
+        CV_HIP(hipEventRecord(d->ev[3], st));
+        CV_HIP(hipMemcpyAsync(wout.data(), d->wout.p, (size_t)nwalk * sizeof(walk_out), hipMemcpyDeviceToHost, st));
     }
     float ms = 0.f;
-    BD_HIP(hipEventElapsedTime(&ms, d->ev[2], d->ev[3]));
+    CV_HIP(hipEventElapsedTime(&ms, d->ev[2], d->ev[3]));
     d->ms[6] += ms;
     place.push_back(0);
     int used = 0;
@@ -348,10 +339,10 @@ static int walk_slab(cv_bam_dev *d, slab &s, const cvb::view &v, hipStream_t st,
     if (s.records == 0) return 0;
     while ((int)place.size() < nwalk + 1) place.push_back(place.back());     // the walkers behind the end of the view took nothing that counts
     if (ensure(d->recs, (size_t)s.records * 4)) return 1;
-    BD_HIP(hipMemcpyAsync(d->place.p, place.data(), place.size() * 8, hipMemcpyHostToDevice, st));
+    CV_HIP(hipMemcpyAsync(d->place.p, place.data(), place.size() * 8, hipMemcpyHostToDevice, st));
     bam_gather<<<(unsigned)(nwalk < 4096 ? nwalk : 4096), 256, 0, st>>>((const uint32_t *)d->sparse.p, (const int64_t *)d->part.p,
                                                                        (const int64_t *)d->place.p, nwalk, (uint32_t *)d->recs.p);
-    BD_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -374,25 +365,24 @@ static int emit_slab(cv_bam_dev *d, cv_pileup *p, slab &s, int contig_ok, hipStr
     unsigned long long *keptd = (unsigned long long *)((uint8_t *)d->small.p + 128);
     int32_t *refd = (int32_t *)((uint8_t *)d->small.p + 136);
     size_t t1 = 0, t2 = 0;
-    BD_HIP(hipcub::DeviceScan::ExclusiveScan(nullptr, t1, in, ex, add5(), sum5{0, 0, 0, 0, 0}, (int)n, st));
-    BD_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, t2, head, runstart, hipcub::Max(), (int)n, st));
+    if (cv_exclusive_scan_temp_bytes(n, add5(), sum5{0, 0, 0, 0, 0}, &t1) || cv_max_scan_temp_bytes<int32_t>(n, &t2)) return 1;
     if (ensure(d->tmp, t1 > t2 ? t1 : t2)) return 1;
     const unsigned g = (unsigned)((n + 255) / 256);
-    BD_HIP(hipMemsetAsync(d->small.p, 0, 256, st));
+    CV_HIP(hipMemsetAsync(d->small.p, 0, 256, st));
     bam_count<<<g, 256, 0, st>>>(s.sb, recs, n, f, in, ri, refd);
     size_t tb = d->tmp.cap;
-    BD_HIP(hipcub::DeviceScan::ExclusiveScan(d->tmp.p, tb, in, ex, add5(), sum5{0, 0, 0, 0, 0}, (int)n, st));
-    BD_HIP(hipMemsetAsync(head, 0xff, (size_t)n * 4, st));                 // -1: no head (entries behind the last read)
+    CV_HIP(hipcub::DeviceScan::ExclusiveScan(d->tmp.p, tb, in, ex, add5(), sum5{0, 0, 0, 0, 0}, (int)n, st));
+    CV_HIP(hipMemsetAsync(head, 0xff, (size_t)n * 4, st));                 // -1: no head (entries behind the last read)
     bam_split<<<g, 256, 0, st>>>(in, ex, ri, n, ctpos, evcpos);
     bam_heads<<<g, 256, 0, st>>>(in, ex, n, ctpos, pp[5], head);
     tb = d->tmp.cap;
-    BD_HIP(hipcub::DeviceScan::InclusiveScan(d->tmp.p, tb, head, runstart, hipcub::Max(), (int)n, st));
+    CV_HIP(hipcub::DeviceScan::InclusiveScan(d->tmp.p, tb, head, runstart, hipcub::Max(), (int)n, st));
     bam_resolve<<<g, 256, 0, st>>>(in, ex, ri, n, evcpos, runstart, pp[1], pp[6], pp[7], keptd);
     bam_totals<<<1, 64, 0, st>>>(in, ex, n, ctpos, evcpos, runstart, pp[5], pp[6], pp[7], pp[8], keptd, refd, so);
-    BD_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     slab_out res;
-    BD_HIP(hipMemcpyAsync(&res, so, sizeof(res), hipMemcpyDeviceToHost, st));
-    BD_HIP(hipStreamSynchronize(st));
+    CV_HIP(hipMemcpyAsync(&res, so, sizeof(res), hipMemcpyDeviceToHost, st));
+    CV_HIP(hipStreamSynchronize(st));
     d->ms[2] += lap(clock);
     if (res.refuse || (uint64_t)res.nseq >= 0xffffff00ull - 64 || res.nseg >= ((int64_t)1 << 31)) { *refuse = true; return 0; }
     if (res.nseg > 0) {
@@ -400,7 +390,7 @@ static int emit_slab(cv_bam_dev *d, cv_pileup *p, slab &s, int contig_ok, hipStr
         uint8_t *seq = nullptr;
         if (cv_pileup_reserve_bam_dev(p, res.nseg, res.nseq, &segs, &seq, st)) return 1;
         bam_emit<<<(unsigned)((n + EMIT_WAVES - 1) / EMIT_WAVES), EMIT_WAVES * 64, 0, st>>>(s.sb, recs, n, in, ex, ri, (cvb::seg *)segs, seq);
-        BD_HIP(hipGetLastError());
+        CV_HIP(hipGetLastError());
         if (cv_pileup_add_bam_dev(p, segs, res.nseg, seq, res.nseq, res.cols, res.state, st)) return 1;
     } else if (cv_pileup_add_bam_dev(p, nullptr, 0, nullptr, 0, res.cols, res.state, st)) return 1;
     s.kept = res.kept;
@@ -413,8 +403,8 @@ static int emit_slab(cv_bam_dev *d, cv_pileup *p, slab &s, int contig_ok, hipStr
 static int host_slab(cv_bam_dev *d, cv_pileup *p, const cvb::view &v, slab &s, int contig_ok, hipStream_t st)
 {
     std::vector<uint8_t> bytes((size_t)s.lim + 8);
-    BD_HIP(hipMemcpyAsync(bytes.data(), s.sb, (size_t)s.lim, hipMemcpyDeviceToHost, st));
-    BD_HIP(hipStreamSynchronize(st));
+    CV_HIP(hipMemcpyAsync(bytes.data(), s.sb, (size_t)s.lim, hipMemcpyDeviceToHost, st));
+    CV_HIP(hipStreamSynchronize(st));
     std::vector<uint32_t> offs;
     int64_t at = s.first;
     s.done = 0; s.kept = 0;
@@ -446,13 +436,13 @@ extern "C" int cv_bam_dev_view(cv_bam_dev *d, cv_bam *b, cv_pileup *p, int64_t s
                                int64_t counts[8])
 {
     if (!d || !b || !p || !kept_out || !counts) { cv_set_error("cv_bam_dev_view: null argument"); return 1; }
-    BD_HIP(hipSetDevice(d->device));
+    CV_HIP(hipSetDevice(d->device));
     hipStream_t st = (hipStream_t)stream;
     for (int k = 0; k < 8; k++) counts[k] = 0;
     *kept_out = 0;
     d->tail = 0;
     for (int k = 0; k < 4; k++)
-        if (!d->ev[k]) BD_HIP(hipEventCreate(&d->ev[k]));
+        if (!d->ev[k]) CV_HIP(hipEventCreate(&d->ev[k]));
     int64_t vp[4];
     if (cv_bam_view_params(b, vp)) return 1;
     const cvb::view v{(int32_t)vp[0], (int32_t)vp[1], vp[2], vp[3]};

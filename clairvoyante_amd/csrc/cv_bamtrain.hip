@@ -18,34 +18,22 @@
 #include <stdint.h>
 #include "../../include/clairvoyante_amd.h"
 #include "cv_draw_core.hpp"
+#include "cv_dev_common.hpp"
 
-void cv_set_error(const char *fmt, ...);
 int cv_pileup_centres_dev(const cv_pileup *p, const int32_t **centres_dev, const uint8_t **flags_dev, const uint8_t **ref_dev,
                           int64_t *ref_first, int64_t *ref_len, int64_t *n);      // cv_pileup.hip
-
-#define BT_HIP(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) {                                                                        \
-            cv_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-            return 1;                                                                                  \
-        }                                                                                              \
-    } while (0)
 
 namespace {
 
 constexpr int FLANK = CV_INPUT_H / 2;                        // 16
 constexpr int THREADS = 256;
-constexpr int MAX_GRID = 4096;
-
-inline int grid_for(int64_t n) { const int64_t b = (n + THREADS - 1) / THREADS; return (int)(b < 1 ? 1 : b < MAX_GRID ? b : MAX_GRID); }
 
 __global__ __launch_bounds__(THREADS) void bt_columns(int64_t n, const int32_t *centres, const uint8_t *cflags, const uint8_t *ref,
                                                       int64_t ref_first, int64_t ref_len, const int32_t *depth,
                                                       const uint8_t *touched, int64_t min_coverage, int64_t *pos, uint8_t *digits,
                                                       uint8_t *centre, uint8_t *acgt, uint8_t *flags, uint8_t *row)
 {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    CV_GRID_STRIDE(i, n) {
         const int64_t c = centres[i];
         const int64_t ri = c - 1 - ref_first;                // the centre in the loaded reference
         const bool inside = ri - FLANK >= 0;                 // the window starts inside it (CreateTensor.py:50)
@@ -77,7 +65,7 @@ __global__ __launch_bounds__(THREADS) void bt_pair_count(int64_t nrows, const ui
                                                          unsigned long long *sums)
 {
     int v = 0, c = 0;                                        // (<= 2^30 rows over 2^20 lanes: an int holds a lane's share)
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+    CV_GRID_STRIDE(r, nrows) {
         if (flags[r] & CV_CENTRE_TRUTH) ++v;                 // not BED-filtered (:50-62)
         else if (keep[r]) ++c;
     }
@@ -97,7 +85,7 @@ __global__ __launch_bounds__(THREADS) void bt_pair_keep(int64_t nrows, const int
 {
     const double ratio = pair_ratio(sums[0], sums[1], amp);
     int picked = 0, final = 0;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+    CV_GRID_STRIDE(r, nrows) {
         bool k = keep[r] != 0;
         if (k && !(flags[r] & CV_CENTRE_TRUTH)) {
             const int32_t c = ctg[r];
@@ -135,9 +123,9 @@ extern "C" int cv_bamtrain_columns(const cv_pileup *p, const int32_t *depth_dev,
         return 1;
     }
     if (((uintptr_t)pos_dev & 7) || ((uintptr_t)depth_dev & 3)) { cv_set_error("cv_bamtrain_columns: pos must be 8-byte, depth 4-byte aligned"); return 1; }
-    hipLaunchKernelGGL(bt_columns, dim3(grid_for(n)), dim3(THREADS), 0, (hipStream_t)stream, n, centres, cflags, ref, ref_first, ref_len,
+    hipLaunchKernelGGL(bt_columns, dim3(cv_grid_for(n)), dim3(THREADS), 0, (hipStream_t)stream, n, centres, cflags, ref, ref_first, ref_len,
                        depth_dev, touched_dev, min_coverage, pos_dev, digits_dev, centre_dev, acgt_dev, flags_dev, row_dev);
-    BT_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -159,10 +147,10 @@ extern "C" int cv_bamtrain_pair(int64_t nrows, const int32_t *ctg_dev, const int
     }
     hipStream_t st = (hipStream_t)stream;
     unsigned long long *sums = (unsigned long long *)counts_dev;
-    BT_HIP(hipMemsetAsync(sums, 0, 4 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(bt_pair_count, dim3(grid_for(nrows)), dim3(THREADS), 0, st, nrows, flags_dev, (const uint8_t *)keep_dev, sums);
-    hipLaunchKernelGGL(bt_pair_keep, dim3(grid_for(nrows)), dim3(THREADS), 0, st, nrows, ctg_dev, pos_dev, flags_dev, acgt_dev,
+    CV_HIP(hipMemsetAsync(sums, 0, 4 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(bt_pair_count, dim3(cv_grid_for(nrows)), dim3(THREADS), 0, st, nrows, flags_dev, (const uint8_t *)keep_dev, sums);
+    hipLaunchKernelGGL(bt_pair_keep, dim3(cv_grid_for(nrows)), dim3(THREADS), 0, st, nrows, ctg_dev, pos_dev, flags_dev, acgt_dev,
                        ctg_hash_dev, nctg, seed, amp, keep_dev, sums, r_dev);
-    BT_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }

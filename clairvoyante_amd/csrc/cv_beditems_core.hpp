@@ -3,6 +3,7 @@
 // for the device (cv_beditems_dev.hip) and for the host (the *_host_form entry points; tests/native/bed_items_driver.cpp
 // runs it under AddressSanitizer / UBSan over heap blocks of exactly the bytes it may touch).
 //
+//   lower_bound / upper_bound   the binary searches of every device reader over its sorted tables
 //   stab          _Intervals.hit over one contig's sorted table: upper_bound(begin, pos) = k > 0 and emax[k - 1] > pos
 //   copy_lane     one lane's share of a line copied by a wave of 64 lanes (see cv_beditems_dev.hip for the form)
 //   sample_keep   "in an interval, when there are intervals, and u(pos) <= prob"
@@ -16,6 +17,17 @@ namespace cvb {
 
 constexpr int WAVE = 64;
 constexpr int DRAW_RANDOM = 2;                                   // draws.RANDOM
+
+// first slot of the sorted a[0, n) whose value is >= v
+CVT_FN int64_t lower_bound(const uint64_t *a, int64_t n, uint64_t v)
+{
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
 
 // number of elements of the sorted a[0, n) that are <= v
 CVT_FN int64_t upper_bound(const int64_t *a, int64_t n, int64_t v)

@@ -8,7 +8,8 @@
 //   newline index       cv_text_line_index of cv_textparse.hip
 //   il_verdicts         one thread per line: the core's status, the position and the contig token's span (the core runs ONCE
 //                       per line: an item row has two fields and both fit the workspace)
-//   il_flags            "this ROW's contig token differs byte for byte from the line before" (or that line is no ROW)
+//   run-start flags     cv_text_run_flags of cv_textparse.hip: "this ROW's contig token differs byte for byte from the line
+//                       before" (or that line is no ROW)
 //   hipcub ExclusiveSum over the ROW flags and over the run-start flags -> row index, run index
 //   il_rows             the ROW lines' position, run, start offset and length at their row index, the run-start tokens
 //
@@ -31,33 +32,19 @@
 #include <stdint.h>
 #include "../../include/clairvoyante_amd.h"
 #include "cv_internal.hpp"
+#include "cv_dev_scan.hpp"
 #include "cv_beditems_core.hpp"
-
-#define BI_HIP(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) {                                                                        \
-            cv_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-            return 1;                                                                                  \
-        }                                                                                              \
-    } while (0)
 
 namespace {
 
 constexpr int THREADS = 256;
-constexpr int MAX_GRID = 4096;
-
-inline int grid_for(int64_t n) { const int64_t b = (n + THREADS - 1) / THREADS; return (int)(b < 1 ? 1 : b < MAX_GRID ? b : MAX_GRID); }
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-#define GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
 // ---- the line pass ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void il_verdicts(const uint8_t *text, const int64_t *line_end, const int64_t *index_info,
                                                        int64_t max_lines, int64_t *span, int64_t *line_pos, int32_t *isrow, int64_t *info)
 {
     const int64_t lines = index_info[1];
-    GRID_STRIDE(i, max_lines + 1) {
+    CV_GRID_STRIDE(i, max_lines + 1) {
         int row = 0;
         if (i < lines) {
             const int64_t start = i ? line_end[i - 1] + 1 : 0;
@@ -73,27 +60,13 @@ __global__ __launch_bounds__(THREADS) void il_verdicts(const uint8_t *text, cons
     }
 }
 
-__global__ __launch_bounds__(THREADS) void il_flags(const uint8_t *text, const int64_t *span, const int32_t *isrow, int64_t max_lines,
-                                                    int32_t *flag)
-{
-    GRID_STRIDE(i, max_lines + 1) {
-        int f = 0;
-        if (i < max_lines && isrow[i]) {
-            f = i == 0 || !isrow[i - 1] || span[2 * i + 1] != span[2 * i - 1];
-            const uint8_t *a = text + span[2 * i], *b = f ? a : text + span[2 * i - 2];
-            for (int64_t k = 0; !f && k < span[2 * i + 1]; ++k) f = a[k] != b[k];
-        }
-        flag[i] = f;
-    }
-}
-
 __global__ __launch_bounds__(THREADS) void il_rows(const int64_t *line_end, const int64_t *index_info, int64_t max_lines,
                                                    const int32_t *isrow, const int32_t *rowidx, const int32_t *flag, const int32_t *runidx,
                                                    const int64_t *span, const int64_t *line_pos, int64_t *pos, int32_t *run, int64_t *off,
                                                    int64_t *llen, int64_t *tok, int64_t *info)
 {
     const int64_t lines = index_info[1];
-    GRID_STRIDE(i, lines) {
+    CV_GRID_STRIDE(i, lines) {
         if (!isrow[i]) continue;
         const int64_t start = i ? line_end[i - 1] + 1 : 0;
         const int64_t r = rowidx[i];
@@ -111,26 +84,29 @@ __global__ __launch_bounds__(THREADS) void il_rows(const int64_t *line_end, cons
     }
 }
 
-struct lines_layout {
-    size_t index, index_info, span, line_pos, isrow, rowidx, flag, runidx, tmp, tmp_bytes, total;
+struct lines_ws {
+    void *index;
+    int64_t *index_info, *span, *line_pos;
+    int32_t *isrow, *rowidx, *flag, *runidx;
+    void *tmp;
+    size_t tmp_bytes;
 };
 
-int lines_plan(int64_t len, int64_t max_lines, lines_layout *L)
+int lines_plan(cv_carver &c, int64_t len, int64_t max_lines, lines_ws *W)
 {
     const size_t n = (size_t)max_lines + 1;
-    size_t o = 0, ib = 0, sb = 0;
+    size_t ib = 0;
     if (cv_text_line_index_bytes(len, max_lines, &ib)) return 1;
-    L->index = o; o = up256(o + ib);
-    L->index_info = o; o = up256(o + 4 * 8);
-    L->span = o; o = up256(o + n * 16);
-    L->line_pos = o; o = up256(o + n * 8);
-    L->isrow = o; o = up256(o + n * 4);
-    L->rowidx = o; o = up256(o + n * 4);
-    L->flag = o; o = up256(o + n * 4);
-    L->runidx = o; o = up256(o + n * 4);
-    BI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, (const int32_t *)nullptr, (int32_t *)nullptr, (int)n, (hipStream_t)0));
-    L->tmp = o; L->tmp_bytes = sb; o = up256(o + sb);
-    L->total = o;
+    W->index = c.take_bytes(ib);
+    W->index_info = c.take<int64_t>(4);
+    W->span = c.take<int64_t>(2 * n);
+    W->line_pos = c.take<int64_t>(n);
+    W->isrow = c.take<int32_t>(n);
+    W->rowidx = c.take<int32_t>(n);
+    W->flag = c.take<int32_t>(n);
+    W->runidx = c.take<int32_t>(n);
+    if (cv_scan_temp_bytes<int32_t>(n, &W->tmp_bytes)) return 1;
+    W->tmp = c.take_bytes(W->tmp_bytes);
     return 0;
 }
 
@@ -154,7 +130,7 @@ __global__ __launch_bounds__(THREADS) void ik_flags(int64_t n, const int64_t *po
     if (threadIdx.x == 0) block_kept = 0;
     __syncthreads();
     unsigned long long mine = 0;
-    GRID_STRIDE(i, n + 1) {
+    CV_GRID_STRIDE(i, n + 1) {
         const bool k = i < n && cvb::keep_row(pos[i], run[i], run_ctg, nruns, nctg, bed_off, bed_begin, bed_emax);
         mine += k;
         if (want_text) kept_len[i] = k && llen[i] > 0 ? llen[i] : 0;
@@ -183,17 +159,19 @@ __global__ __launch_bounds__(THREADS) void ik_copy(const uint8_t *text, int64_t 
     if (blockIdx.x == 0 && threadIdx.x == 0) counts[2] = dst_at[n];
 }
 
-struct keep_layout { size_t kept_len, dst_at, tmp, tmp_bytes, total; };
+struct keep_ws {
+    int64_t *kept_len, *dst_at;
+    void *tmp;
+    size_t tmp_bytes;
+};
 
-int keep_plan(int64_t n, keep_layout *L)
+int keep_plan(cv_carver &c, int64_t n, keep_ws *W)
 {
     const size_t m = (size_t)n + 1;
-    size_t o = 0, sb = 0;
-    L->kept_len = o; o = up256(o + m * 8);
-    L->dst_at = o; o = up256(o + m * 8);
-    BI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, (const int64_t *)nullptr, (int64_t *)nullptr, (int)m, (hipStream_t)0));
-    L->tmp = o; L->tmp_bytes = sb; o = up256(o + sb);
-    L->total = o;
+    W->kept_len = c.take<int64_t>(m);
+    W->dst_at = c.take<int64_t>(m);
+    if (cv_scan_temp_bytes<int64_t>(m, &W->tmp_bytes)) return 1;
+    W->tmp = c.take_bytes(W->tmp_bytes);
     return 0;
 }
 
@@ -214,13 +192,13 @@ bool keep_args_ok(const char *who, int64_t len, int64_t n, int64_t nruns, int32_
 __global__ __launch_bounds__(THREADS) void sp_flags(uint64_t seed, uint32_t h, int64_t first, int64_t count, double prob, int64_t nbed,
                                                     const int64_t *bed_begin, const int64_t *bed_emax, int32_t *flag)
 {
-    GRID_STRIDE(i, count + 1) flag[i] = i < count && cvb::sample_keep(seed, h, first + i, prob, nbed, bed_begin, bed_emax);
+    CV_GRID_STRIDE(i, count + 1) flag[i] = i < count && cvb::sample_keep(seed, h, first + i, prob, nbed, bed_begin, bed_emax);
 }
 
 __global__ __launch_bounds__(THREADS) void sp_emit(int64_t first, int64_t count, const int32_t *flag, const int32_t *at, int64_t *out_pos,
                                                    int64_t cap, int64_t *counts)
 {
-    GRID_STRIDE(i, count)
+    CV_GRID_STRIDE(i, count)
         if (flag[i] && at[i] < cap) out_pos[at[i]] = first + i;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const int64_t would = at[count];
@@ -229,17 +207,19 @@ __global__ __launch_bounds__(THREADS) void sp_emit(int64_t first, int64_t count,
     }
 }
 
-struct sample_layout { size_t flag, at, tmp, tmp_bytes, total; };
+struct sample_ws {
+    int32_t *flag, *at;
+    void *tmp;
+    size_t tmp_bytes;
+};
 
-int sample_plan(int64_t count, sample_layout *L)
+int sample_plan(cv_carver &c, int64_t count, sample_ws *W)
 {
     const size_t m = (size_t)count + 1;
-    size_t o = 0, sb = 0;
-    L->flag = o; o = up256(o + m * 4);
-    L->at = o; o = up256(o + m * 4);
-    BI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, (const int32_t *)nullptr, (int32_t *)nullptr, (int)m, (hipStream_t)0));
-    L->tmp = o; L->tmp_bytes = sb; o = up256(o + sb);
-    L->total = o;
+    W->flag = c.take<int32_t>(m);
+    W->at = c.take<int32_t>(m);
+    if (cv_scan_temp_bytes<int32_t>(m, &W->tmp_bytes)) return 1;
+    W->tmp = c.take_bytes(W->tmp_bytes);
     return 0;
 }
 
@@ -261,9 +241,10 @@ extern "C" int cv_item_lines_workspace(int64_t len, int64_t max_lines, int64_t *
 {
     if (!bytes) { cv_set_error("cv_item_lines_workspace: null argument"); return 1; }
     if (!lines_args_ok("cv_item_lines_workspace", len, max_lines)) return 1;
-    lines_layout L;
-    if (lines_plan(len, max_lines, &L)) return 1;
-    *bytes = (int64_t)L.total;
+    cv_carver c;
+    lines_ws W;
+    if (lines_plan(c, len, max_lines, &W)) return 1;
+    *bytes = (int64_t)c.total();
     return 0;
 }
 
@@ -277,37 +258,31 @@ extern "C" int cv_item_lines_dev(const char *text_dev, int64_t len, int64_t max_
         return 1;
     }
     if (((uintptr_t)pos_dev & 7) || ((uintptr_t)run_dev & 3) || ((uintptr_t)off_dev & 7) || ((uintptr_t)len_dev & 7) ||
-        ((uintptr_t)tok_dev & 7) || ((uintptr_t)info_dev & 7) || ((uintptr_t)workspace_dev & 255)) {
-        cv_set_error("cv_item_lines_dev: pos / off / len / tok / info must be 8-byte, run 4-byte, the workspace 256-byte aligned");
+        ((uintptr_t)tok_dev & 7) || ((uintptr_t)info_dev & 7)) {
+        cv_set_error("cv_item_lines_dev: pos / off / len / tok / info must be 8-byte, run 4-byte aligned");
         return 1;
     }
-    lines_layout L;
-    if (lines_plan(len, max_lines, &L)) return 1;
-    if (workspace_bytes < (int64_t)L.total) {
-        cv_set_error("cv_item_lines_dev: workspace holds %lld bytes, need %lld", (long long)workspace_bytes, (long long)L.total);
-        return 1;
-    }
+    cv_carver c(workspace_dev);
+    lines_ws W;
+    if (lines_plan(c, len, max_lines, &W)) return 1;
+    if (!cv_workspace_ok("cv_item_lines_dev", workspace_dev, workspace_bytes, c.total())) return 1;
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace_dev;
-    int64_t *index_info = (int64_t *)(ws + L.index_info), *span = (int64_t *)(ws + L.span), *line_pos = (int64_t *)(ws + L.line_pos);
-    int32_t *isrow = (int32_t *)(ws + L.isrow), *rowidx = (int32_t *)(ws + L.rowidx), *flag = (int32_t *)(ws + L.flag),
-            *runidx = (int32_t *)(ws + L.runidx);
     const int64_t *line_end = nullptr;
-    BI_HIP(hipMemsetAsync(info_dev, 0, 8 * sizeof(int64_t), st));
-    if (cv_text_line_index(text_dev, len, max_lines, ws + L.index, index_info, &line_end, st)) return 1;
+    CV_HIP(hipMemsetAsync(info_dev, 0, 8 * sizeof(int64_t), st));
+    if (cv_text_line_index(text_dev, len, max_lines, W.index, W.index_info, &line_end, st)) return 1;
     const uint8_t *text = (const uint8_t *)text_dev;
-    const int grid = grid_for(max_lines + 1);
-    hipLaunchKernelGGL(il_verdicts, dim3(grid), dim3(THREADS), 0, st, text, line_end, (const int64_t *)index_info, max_lines, span,
-                       line_pos, isrow, info_dev);
-    hipLaunchKernelGGL(il_flags, dim3(grid), dim3(THREADS), 0, st, text, (const int64_t *)span, (const int32_t *)isrow, max_lines, flag);
-    size_t tb = L.tmp_bytes;
-    BI_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.tmp, tb, (const int32_t *)isrow, rowidx, (int)(max_lines + 1), st));
-    tb = L.tmp_bytes;
-    BI_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.tmp, tb, (const int32_t *)flag, runidx, (int)(max_lines + 1), st));
-    hipLaunchKernelGGL(il_rows, dim3(grid), dim3(THREADS), 0, st, line_end, (const int64_t *)index_info, max_lines, (const int32_t *)isrow,
-                       (const int32_t *)rowidx, (const int32_t *)flag, (const int32_t *)runidx, (const int64_t *)span,
-                       (const int64_t *)line_pos, pos_dev, run_dev, off_dev, len_dev, tok_dev, info_dev);
-    BI_HIP(hipGetLastError());
+    const int grid = cv_grid_for(max_lines + 1);
+    hipLaunchKernelGGL(il_verdicts, dim3(grid), dim3(THREADS), 0, st, text, line_end, (const int64_t *)W.index_info, max_lines, W.span,
+                       W.line_pos, W.isrow, info_dev);
+    cv_text_run_flags(text, W.span, W.isrow, max_lines, W.flag, st);
+    size_t tb = W.tmp_bytes;
+    CV_HIP(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, (const int32_t *)W.isrow, W.rowidx, (int)(max_lines + 1), st));
+    tb = W.tmp_bytes;
+    CV_HIP(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, (const int32_t *)W.flag, W.runidx, (int)(max_lines + 1), st));
+    hipLaunchKernelGGL(il_rows, dim3(grid), dim3(THREADS), 0, st, line_end, (const int64_t *)W.index_info, max_lines,
+                       (const int32_t *)W.isrow, (const int32_t *)W.rowidx, (const int32_t *)W.flag, (const int32_t *)W.runidx,
+                       (const int64_t *)W.span, (const int64_t *)W.line_pos, pos_dev, run_dev, off_dev, len_dev, tok_dev, info_dev);
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -332,9 +307,10 @@ extern "C" int cv_items_keep_workspace(int64_t n, int64_t *bytes)
 {
     if (!bytes) { cv_set_error("cv_items_keep_workspace: null argument"); return 1; }
     if (!keep_args_ok("cv_items_keep_workspace", 0, n, 0, 0, 0)) return 1;
-    keep_layout L;
-    if (keep_plan(n, &L)) return 1;
-    *bytes = (int64_t)L.total;
+    cv_carver c;
+    keep_ws W;
+    if (keep_plan(c, n, &W)) return 1;
+    *bytes = (int64_t)c.total();
     return 0;
 }
 
@@ -366,31 +342,24 @@ extern "C" int cv_items_keep_dev(const char *text_dev, int64_t len, int64_t n, c
     if (!keep_pointers_ok("cv_items_keep_dev", text_dev, len, n, pos_dev, run_dev, off_dev, len_dev, run_ctg_dev, nctg, bed_off_dev,
                           bed_begin_dev, bed_emax_dev, want_text, out_text_dev, out_cap, counts_dev))
         return 1;
-    if (!workspace_dev || ((uintptr_t)workspace_dev & 255)) {
-        cv_set_error("cv_items_keep_dev: the workspace must be there and 256-byte aligned");
-        return 1;
-    }
-    keep_layout L;
-    if (keep_plan(n, &L)) return 1;
-    if (workspace_bytes < (int64_t)L.total) {
-        cv_set_error("cv_items_keep_dev: workspace holds %lld bytes, need %lld", (long long)workspace_bytes, (long long)L.total);
-        return 1;
-    }
+    cv_carver c(workspace_dev);
+    keep_ws W;
+    if (keep_plan(c, n, &W)) return 1;
+    if (!cv_workspace_ok("cv_items_keep_dev", workspace_dev, workspace_bytes, c.total())) return 1;
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace_dev;
-    int64_t *kept_len = (int64_t *)(ws + L.kept_len), *dst_at = (int64_t *)(ws + L.dst_at);
-    BI_HIP(hipMemsetAsync(counts_dev, 0, 4 * sizeof(int64_t), st));
-    hipLaunchKernelGGL(ik_flags, dim3(grid_for(n + 1)), dim3(THREADS), 0, st, n, pos_dev, run_dev, len_dev, run_ctg_dev, nruns, nctg,
+    int64_t *kept_len = W.kept_len, *dst_at = W.dst_at;
+    CV_HIP(hipMemsetAsync(counts_dev, 0, 4 * sizeof(int64_t), st));
+    hipLaunchKernelGGL(ik_flags, dim3(cv_grid_for(n + 1)), dim3(THREADS), 0, st, n, pos_dev, run_dev, len_dev, run_ctg_dev, nruns, nctg,
                        bed_off_dev, bed_begin_dev, bed_emax_dev, want_text, kept_len, counts_dev);
     if (want_text) {
-        size_t tb = L.tmp_bytes;
-        BI_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.tmp, tb, (const int64_t *)kept_len, dst_at, (int)(n + 1), st));
+        size_t tb = W.tmp_bytes;
+        CV_HIP(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, (const int64_t *)kept_len, dst_at, (int)(n + 1), st));
         const int64_t blocks = (n + THREADS / cvb::WAVE - 1) / (THREADS / cvb::WAVE);
         hipLaunchKernelGGL(ik_copy, dim3((unsigned)(blocks < 1 ? 1 : blocks < 65536 ? blocks : 65536)), dim3(THREADS), 0, st,
                            (const uint8_t *)text_dev, len, n, off_dev, (const int64_t *)kept_len, (const int64_t *)dst_at,
                            (uint8_t *)out_text_dev, out_cap, counts_dev);
     }
-    BI_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -412,9 +381,10 @@ extern "C" int cv_sample_positions_workspace(int64_t count, int64_t *bytes)
 {
     if (!bytes) { cv_set_error("cv_sample_positions_workspace: null argument"); return 1; }
     if (!sample_args_ok("cv_sample_positions_workspace", 0, count, 0.0, 0, 0)) return 1;
-    sample_layout L;
-    if (sample_plan(count, &L)) return 1;
-    *bytes = (int64_t)L.total;
+    cv_carver c;
+    sample_ws W;
+    if (sample_plan(c, count, &W)) return 1;
+    *bytes = (int64_t)c.total();
     return 0;
 }
 
@@ -427,26 +397,22 @@ extern "C" int cv_sample_positions_dev(uint64_t seed, uint32_t h, int64_t first,
         cv_set_error("cv_sample_positions_dev: null argument");
         return 1;
     }
-    if (((uintptr_t)bed_begin_dev & 7) || ((uintptr_t)bed_emax_dev & 7) || ((uintptr_t)out_pos_dev & 7) || ((uintptr_t)count_dev & 7) ||
-        ((uintptr_t)workspace_dev & 255)) {
-        cv_set_error("cv_sample_positions_dev: the int64 arrays must be 8-byte, the workspace 256-byte aligned");
+    if (((uintptr_t)bed_begin_dev & 7) || ((uintptr_t)bed_emax_dev & 7) || ((uintptr_t)out_pos_dev & 7) || ((uintptr_t)count_dev & 7)) {
+        cv_set_error("cv_sample_positions_dev: the int64 arrays must be 8-byte aligned");
         return 1;
     }
-    sample_layout L;
-    if (sample_plan(count, &L)) return 1;
-    if (workspace_bytes < (int64_t)L.total) {
-        cv_set_error("cv_sample_positions_dev: workspace holds %lld bytes, need %lld", (long long)workspace_bytes, (long long)L.total);
-        return 1;
-    }
+    cv_carver c(workspace_dev);
+    sample_ws W;
+    if (sample_plan(c, count, &W)) return 1;
+    if (!cv_workspace_ok("cv_sample_positions_dev", workspace_dev, workspace_bytes, c.total())) return 1;
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace_dev;
-    int32_t *flag = (int32_t *)(ws + L.flag), *at = (int32_t *)(ws + L.at);
-    const int grid = grid_for(count + 1);
+    int32_t *flag = W.flag, *at = W.at;
+    const int grid = cv_grid_for(count + 1);
     hipLaunchKernelGGL(sp_flags, dim3(grid), dim3(THREADS), 0, st, seed, h, first, count, prob, nbed, bed_begin_dev, bed_emax_dev, flag);
-    size_t tb = L.tmp_bytes;
-    BI_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.tmp, tb, (const int32_t *)flag, at, (int)(count + 1), st));
+    size_t tb = W.tmp_bytes;
+    CV_HIP(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, (const int32_t *)flag, at, (int)(count + 1), st));
     hipLaunchKernelGGL(sp_emit, dim3(grid), dim3(THREADS), 0, st, first, count, (const int32_t *)flag, (const int32_t *)at, out_pos_dev, cap,
                        count_dev);
-    BI_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }

@@ -18,20 +18,11 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include "../../include/clairvoyante_amd.h"
+#include "cv_dev_scan.hpp"
 #include "cv_callcols_core.hpp"
 
-void cv_set_error(const char *fmt, ...);
 int cv_pileup_centres_dev(const cv_pileup *p, const int32_t **centres_dev, const uint8_t **flags_dev, const uint8_t **ref_dev,
                           int64_t *ref_first, int64_t *ref_len, int64_t *n);      // cv_pileup.hip
-
-#define CC_HIP(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) {                                                                        \
-            cv_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-            return 1;                                                                                  \
-        }                                                                                              \
-    } while (0)
 
 static_assert(CV_CALL_COLUMNS_MAX_CTG == 1024 && CV_CALL_COLUMNS_ROW_TEXT == cvk::MAX_ROW_TEXT, "the header's bounds");
 
@@ -91,16 +82,21 @@ __global__ __launch_bounds__(THREADS) void cc_write(CtgName ctg, int64_t ctg_len
     for (int t = l; t < wlen; t += GROUP) text[seq_at + t] = (char)cvk::upper(ref[w0 + t]);
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the workspace: a_in | b_in | a_out | b_out (n + 1 int64 each) | hipcub's
-int plan(int64_t n, size_t *column, size_t *tmp_bytes, size_t *total)
+struct columns_ws {
+    int64_t *a_in, *b_in, *a, *b;
+    void *tmp;
+    size_t tmp_bytes;
+};
+
+int plan(cv_carver &c, int64_t n, columns_ws *W)
 {
-    size_t t = 0;
-    CC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t, (const int64_t *)nullptr, (int64_t *)nullptr, (int)(n + 1), (hipStream_t)0));
-    *column = up256((size_t)(n + 1) * 8);
-    *tmp_bytes = t;
-    *total = up256(4 * *column + t);
+    W->a_in = c.take<int64_t>((size_t)(n + 1));
+    W->b_in = c.take<int64_t>((size_t)(n + 1));
+    W->a = c.take<int64_t>((size_t)(n + 1));
+    W->b = c.take<int64_t>((size_t)(n + 1));
+    if (cv_scan_temp_bytes<int64_t>(n + 1, &W->tmp_bytes)) return 1;
+    W->tmp = c.take_bytes(W->tmp_bytes);
     return 0;
 }
 
@@ -146,28 +142,25 @@ int run_dev(const char *who, const char *ctg, int64_t ctg_len, const int32_t *ce
 {
     if (!args_ok(who, ctg, ctg_len, n, ref_first, ref_len)) return 1;
     if (!outputs_ok(who, n, ctg_len, centres, touched, ref, ref_len, index, meta, text, text_cap, info)) return 1;
-    if (!workspace || ((uintptr_t)workspace & 255)) { cv_set_error("%s: the workspace must be there and 256-byte aligned", who); return 1; }
-    size_t col, tb, total;
-    if (plan(n, &col, &tb, &total)) return 1;
-    if (workspace_bytes < (int64_t)total) {
-        cv_set_error("%s: workspace holds %lld bytes, need %lld", who, (long long)workspace_bytes, (long long)total);
-        return 1;
-    }
+    cv_carver c(workspace);
+    columns_ws W;
+    if (plan(c, n, &W)) return 1;
+    if (!cv_workspace_ok(who, workspace, workspace_bytes, c.total())) return 1;
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    int64_t *a_in = (int64_t *)ws, *b_in = (int64_t *)(ws + col), *a = (int64_t *)(ws + 2 * col), *b = (int64_t *)(ws + 3 * col);
-    void *tmp = ws + 4 * col;
+    int64_t *a_in = W.a_in, *b_in = W.b_in, *a = W.a, *b = W.b;
+    void *tmp = W.tmp;
+    size_t tb = W.tmp_bytes;
     CtgName name;
     for (int64_t t = 0; t < CV_CALL_COLUMNS_MAX_CTG; t++) name.s[t] = t < ctg_len ? ctg[t] : 0;
     hipLaunchKernelGGL(cc_verdict, dim3((unsigned)((n + 1 + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, n, centres, touched, ref, ref_first,
                        ref_len, a_in, b_in);
-    CC_HIP(hipGetLastError());
-    CC_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, (const int64_t *)a_in, a, (int)(n + 1), st));
-    CC_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, (const int64_t *)b_in, b, (int)(n + 1), st));
+    CV_HIP(hipGetLastError());
+    CV_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, (const int64_t *)a_in, a, (int)(n + 1), st));
+    CV_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, (const int64_t *)b_in, b, (int)(n + 1), st));
     const int64_t blocks = n > 0 ? (n + PER_BLOCK - 1) / PER_BLOCK : 1;
     hipLaunchKernelGGL(cc_write, dim3((unsigned)blocks), dim3(THREADS), 0, st, name, ctg_len, n, centres, ref, ref_first, (const int64_t *)a,
                        (const int64_t *)b, index, meta, text, text_cap, info);
-    CC_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -180,9 +173,10 @@ extern "C" int cv_call_columns_workspace(int64_t n, int64_t *bytes)
         cv_set_error("cv_call_columns_workspace: %lld centres out of range (0 .. %lld)", (long long)n, (long long)MAX_N);
         return 1;
     }
-    size_t col, tb, total;
-    if (plan(n, &col, &tb, &total)) return 1;
-    *bytes = (int64_t)total;
+    cv_carver c;
+    columns_ws W;
+    if (plan(c, n, &W)) return 1;
+    *bytes = (int64_t)c.total();
     return 0;
 }
 

@@ -10,17 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/clairvoyante_amd.h"
-
-void cv_set_error(const char *fmt, ...);
-
-#define EV_HIP(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) {                                                                        \
-            cv_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-            return 1;                                                                                  \
-        }                                                                                              \
-    } while (0)
+#include "cv_dev_common.hpp"
 
 namespace {
 
@@ -139,6 +129,6 @@ extern "C" int cv_eval_counts(const float *out16_dev, const void *y_dev, int y_i
     else
         hipLaunchKernelGGL(eval_counts<float>, grid, dim3(EV_THREADS), 0, (hipStream_t)stream, out16_dev,
                            (const float *)y_dev, n, c);
-    EV_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }

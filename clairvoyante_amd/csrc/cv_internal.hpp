@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/clairvoyante_amd.h"
+#include "cv_dev_common.hpp"
 
 // ---------------------------------------------------------------------------
 // Tile-major ("TM") activation layout -- the HBM layout of every intermediate.
@@ -175,8 +176,6 @@ void cv_prof_begin(cv_model *m, int stage, hipStream_t st);
 void cv_prof_end(cv_model *m, int stage, hipStream_t st);
 void cv_prof_free(cv_model *m);
 
-void cv_set_error(const char *fmt, ...);
-
 // layouts of cv_model::packed_valid
 enum : unsigned {
     CVL_CONV = 1u,      // wp_conv1, wp_conv[1..2]
@@ -201,15 +200,6 @@ int cv_layout_current(const cv_model *m, unsigned layout, const char *who);    /
 #define CV_WG_REGIONS 6
 #define CV_TR_SIDES 3          // side streams of the weight-gradient kernels (tr_side + tr_side_more)
 #define CV_GRAD_HEADER 16     // floats in front of the flat gradient: the loss header (cv_train.hip)
-
-#define CV_HIP(expr)                                                                     \
-    do {                                                                                 \
-        hipError_t _e = (expr);                                                          \
-        if (_e != hipSuccess) {                                                          \
-            cv_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return 1;                                                                    \
-        }                                                                                \
-    } while (0)
 
 // kernel launchers (defined in the .hip files)
 int cv_ref_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStream_t st);
@@ -269,3 +259,7 @@ int cv_tm_to_natural(const float *tm, int KB, int feat_per_pos_padded, int feat_
 int cv_text_line_index_bytes(int64_t len, int64_t max_lines, size_t *bytes);
 int cv_text_line_index(const char *text_dev, int64_t len, int64_t max_lines, void *workspace_dev, int64_t *info_dev,
                        const int64_t **line_end_dev, hipStream_t st);
+// flag[i] = 1 where line i < max_lines is a ROW (isrow) whose contig token (span[2 i], span[2 i + 1] = offset, length)
+// differs byte for byte from the line before, or that line is no ROW; flag[max_lines] = 0 (the scan's last input)
+void cv_text_run_flags(const uint8_t *text_dev, const int64_t *span_dev, const int32_t *isrow_dev, int64_t max_lines, int32_t *flag_dev,
+                       hipStream_t st);

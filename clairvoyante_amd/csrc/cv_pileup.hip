@@ -49,17 +49,8 @@
 
 #include "../../include/clairvoyante_amd.h"
 #include "cv_draw_core.hpp"
+#include "cv_dev_scan.hpp"
 
-void cv_set_error(const char *fmt, ...);
-
-#define PL_HIP(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess) {                                                                   \
-            cv_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return 1;                                                                             \
-        }                                                                                         \
-    } while (0)
 
 namespace {
 
@@ -414,8 +405,8 @@ static int drain(std::vector<hipEvent_t> &ev, float &acc)
 {
     for (size_t k = 0; k + 1 < ev.size(); k += 2) {
         float ms = 0.f;
-        PL_HIP(hipEventSynchronize(ev[k + 1]));
-        PL_HIP(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+        CV_HIP(hipEventSynchronize(ev[k + 1]));
+        CV_HIP(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
         acc += ms;
         hipEventDestroy(ev[k]);
         hipEventDestroy(ev[k + 1]);
@@ -444,7 +435,7 @@ extern "C" int cv_pileup_create(int device, int min_mq, int dcov, int consider_l
 {
     if (!out) { cv_set_error("cv_pileup_create: null argument"); return 1; }
     int ndev = 0;
-    PL_HIP(hipGetDeviceCount(&ndev));
+    CV_HIP(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) {
         cv_set_error("cv_pileup_create: device %d not present (%d visible)", device, ndev);
         return 1;
@@ -501,11 +492,11 @@ extern "C" int cv_pileup_set_contig(cv_pileup *p, const char *name)
 extern "C" int cv_pileup_set_reference(cv_pileup *p, const char *seq, int64_t len, int64_t first_pos0)
 {
     if (!p || (!seq && len > 0) || len < 0) { cv_set_error("cv_pileup_set_reference: bad argument"); return 1; }
-    PL_HIP(hipSetDevice(p->device));
-    if (p->ref_dev) { PL_HIP(hipFree(p->ref_dev)); p->ref_dev = nullptr; }
-    if (p->pos_cnt) { PL_HIP(hipFree(p->pos_cnt)); p->pos_cnt = nullptr; }
-    PL_HIP(hipMalloc(&p->ref_dev, (size_t)(len > 0 ? len : 1)));
-    if (len > 0) PL_HIP(hipMemcpy(p->ref_dev, seq, (size_t)len, hipMemcpyHostToDevice));
+    CV_HIP(hipSetDevice(p->device));
+    if (p->ref_dev) { CV_HIP(hipFree(p->ref_dev)); p->ref_dev = nullptr; }
+    if (p->pos_cnt) { CV_HIP(hipFree(p->pos_cnt)); p->pos_cnt = nullptr; }
+    CV_HIP(hipMalloc(&p->ref_dev, (size_t)(len > 0 ? len : 1)));
+    if (len > 0) CV_HIP(hipMemcpy(p->ref_dev, seq, (size_t)len, hipMemcpyHostToDevice));
     p->ref_len = len; p->ref_first = first_pos0;
     return 0;
 }
@@ -517,11 +508,11 @@ static int install_alloc(cv_pileup *p, int64_t n)
     p->cand_dev = nullptr; p->bucket_dev = nullptr; p->cnt_dev = nullptr; p->touched_dev = nullptr; p->cflag_dev = nullptr;
     p->n = n;
     size_t n1 = (size_t)(n > 0 ? n : 1);
-    PL_HIP(hipMalloc(&p->cand_dev, n1 * sizeof(int32_t)));
-    PL_HIP(hipMalloc(&p->cnt_dev, n1 * WIDTH * NCNT * sizeof(int32_t)));
-    PL_HIP(hipMalloc(&p->touched_dev, n1));
-    PL_HIP(hipMemset(p->cnt_dev, 0, n1 * WIDTH * NCNT * sizeof(int32_t)));
-    PL_HIP(hipMemset(p->touched_dev, 0, n1));
+    CV_HIP(hipMalloc(&p->cand_dev, n1 * sizeof(int32_t)));
+    CV_HIP(hipMalloc(&p->cnt_dev, n1 * WIDTH * NCNT * sizeof(int32_t)));
+    CV_HIP(hipMalloc(&p->touched_dev, n1));
+    CV_HIP(hipMemset(p->cnt_dev, 0, n1 * WIDTH * NCNT * sizeof(int32_t)));
+    CV_HIP(hipMemset(p->touched_dev, 0, n1));
     return 0;
 }
 
@@ -535,12 +526,12 @@ static int install_buckets(cv_pileup *p, int32_t first, int32_t last)
     } else {
         p->bucket_lo = 0; p->nb = 1;
     }
-    PL_HIP(hipMalloc(&p->bucket_dev, (size_t)p->nb * sizeof(int32_t)));
+    CV_HIP(hipMalloc(&p->bucket_dev, (size_t)p->nb * sizeof(int32_t)));
     int threads = 256;
     bucket_build<<<(unsigned)((p->nb + threads - 1) / threads), threads>>>(p->cand_dev, (int)n, p->bucket_lo, p->nb,
                                                                              p->bucket_dev);
-    PL_HIP(hipGetLastError());
-    PL_HIP(hipDeviceSynchronize());
+    CV_HIP(hipGetLastError());
+    CV_HIP(hipDeviceSynchronize());
     return 0;
 }
 
@@ -548,7 +539,7 @@ static int install_candidates(cv_pileup *p, const std::vector<int32_t> &c32)
 {
     const int64_t n = (int64_t)c32.size();
     if (install_alloc(p, n)) return 1;
-    if (n > 0) PL_HIP(hipMemcpy(p->cand_dev, c32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (n > 0) CV_HIP(hipMemcpy(p->cand_dev, c32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     return install_buckets(p, n > 0 ? c32[0] : 0, n > 0 ? c32[(size_t)n - 1] : 0);
 }
 
@@ -556,7 +547,7 @@ extern "C" int cv_pileup_set_candidates(cv_pileup *p, const int64_t *centers, in
 {
     if (!p || (!centers && n > 0) || n < 0) { cv_set_error("cv_pileup_set_candidates: bad argument"); return 1; }
     if (!p->queue.empty()) { cv_set_error("cv_pileup_set_candidates: reads are queued; flush first"); return 1; }
-    PL_HIP(hipSetDevice(p->device));
+    CV_HIP(hipSetDevice(p->device));
     std::vector<int32_t> c32((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         if (centers[i] < -(1LL << 30) || centers[i] > (1LL << 31) - 64 || (i && centers[i] <= centers[i - 1])) {
@@ -914,7 +905,7 @@ static int launch_scatter(cv_pileup *p, const dev_batch &b, hipStream_t st)
             b.segs, (int64_t)b.nseg, b.seq, p->ref_dev, p->ref_first, p->ref_len, p->cand_dev, (int)p->n, p->bucket_dev,
             p->bucket_lo, p->nb, p->cnt_dev, p->touched_dev, p->left);
     }
-    PL_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     p->launches += 1;
     return 0;
 }
@@ -927,7 +918,7 @@ extern "C" int cv_pileup_flush(cv_pileup *p, void *stream)
         cv_set_error("cv_pileup_flush: set the reference and the candidates first");
         return 1;
     }
-    PL_HIP(hipSetDevice(p->device));
+    CV_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     // one device allocation for everything queued; every parser slice is uploaded to its own range (its q0 offsets
     // are relative to its own SEQ bytes: a small kernel rebases them in place), nothing is merged on the host
@@ -936,33 +927,33 @@ extern "C" int cv_pileup_flush(cv_pileup *p, void *stream)
     dev_batch fresh;
     dev_batch &b = p->retain ? fresh : p->work;
     if (ns > b.segs_cap) {
-        PL_HIP(hipStreamSynchronize(st));
+        CV_HIP(hipStreamSynchronize(st));
         hipFree(b.segs); b.segs = nullptr;
         b.segs_cap = p->retain ? ns : ns + ns / 4;
-        PL_HIP(hipMalloc(&b.segs, b.segs_cap * sizeof(seg_t)));
+        CV_HIP(hipMalloc(&b.segs, b.segs_cap * sizeof(seg_t)));
     }
     if (nq > b.seq_cap) {
-        PL_HIP(hipStreamSynchronize(st));
+        CV_HIP(hipStreamSynchronize(st));
         hipFree(b.seq); b.seq = nullptr;
         b.seq_cap = p->retain ? nq : nq + nq / 4;
-        PL_HIP(hipMalloc(&b.seq, b.seq_cap));
+        CV_HIP(hipMalloc(&b.seq, b.seq_cap));
     }
     b.nseg = ns;
     if (p->evc && !p->pos_cnt) {
         const size_t bytes = (size_t)(p->ref_len > 0 ? p->ref_len : 1) * NPOS * sizeof(int32_t);
-        PL_HIP(hipMalloc(&p->pos_cnt, bytes));
-        PL_HIP(hipMemsetAsync(p->pos_cnt, 0, bytes, st));
+        CV_HIP(hipMalloc(&p->pos_cnt, bytes));
+        CV_HIP(hipMemsetAsync(p->pos_cnt, 0, bytes, st));
     }
     if (nq >= 0xffffff00ull) { cv_set_error("cv_pileup_flush: more than 4 Gi query bases queued; flush more often"); return 1; }
     size_t so = 0, qo = 0;
     for (const auto &part : p->queue) {
         const size_t n1 = part.segs.size();
-        PL_HIP(hipMemcpyAsync(b.segs + so, part.segs.data(), n1 * sizeof(seg_t), hipMemcpyHostToDevice, st));
-        if (!part.seq.empty()) PL_HIP(hipMemcpyAsync(b.seq + qo, part.seq.data(), part.seq.size(), hipMemcpyHostToDevice, st));
+        CV_HIP(hipMemcpyAsync(b.segs + so, part.segs.data(), n1 * sizeof(seg_t), hipMemcpyHostToDevice, st));
+        if (!part.seq.empty()) CV_HIP(hipMemcpyAsync(b.seq + qo, part.seq.data(), part.seq.size(), hipMemcpyHostToDevice, st));
         if (qo) rebase_q0<<<(unsigned)((n1 + 255) / 256), 256, 0, st>>>(b.segs + so, (int64_t)n1, (uint32_t)qo);
         so += n1; qo += (part.seq.size() + 15) / 16 * 16;
     }
-    PL_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     if (p->evc) {
         if (p->eve.size() >= 128 && drain(p->eve, p->ms_evc)) return 1;
         {
@@ -970,13 +961,13 @@ extern "C" int cv_pileup_flush(cv_pileup *p, void *stream)
             evc_count<<<(unsigned)((ns + EVC_SEGS - 1) / EVC_SEGS), 1024, 0, st>>>(b.segs, (int64_t)ns, b.seq, p->ref_first,
                                                                                    p->ref_len, p->pos_cnt);
         }
-        PL_HIP(hipGetLastError());
+        CV_HIP(hipGetLastError());
     }
     if (p->cand_dev && launch_scatter(p, b, st)) return 1;
     if (p->retain) p->kept.push_back(b);
     p->nsegs += (int64_t)ns;
     // pageable copies are staged before hipMemcpyAsync returns only for small sizes: wait for them
-    PL_HIP(hipStreamSynchronize(st));
+    CV_HIP(hipStreamSynchronize(st));
     p->cols += p->pending_cols;
     p->queue.clear(); p->pending_cols = 0;
     return 0;
@@ -997,16 +988,16 @@ extern "C" int cv_pileup_bam_params(const cv_pileup *p, int64_t out[9])
 static int batch_room(cv_pileup *p, dev_batch &b, size_t ns, size_t nqq, hipStream_t st)
 {
     if (ns > b.segs_cap) {
-        PL_HIP(hipStreamSynchronize(st));
+        CV_HIP(hipStreamSynchronize(st));
         hipFree(b.segs); b.segs = nullptr;
         b.segs_cap = p->retain ? ns : ns + ns / 4;
-        PL_HIP(hipMalloc(&b.segs, b.segs_cap * sizeof(seg_t)));
+        CV_HIP(hipMalloc(&b.segs, b.segs_cap * sizeof(seg_t)));
     }
     if (nqq > b.seq_cap) {
-        PL_HIP(hipStreamSynchronize(st));
+        CV_HIP(hipStreamSynchronize(st));
         hipFree(b.seq); b.seq = nullptr;
         b.seq_cap = p->retain ? nqq : nqq + nqq / 4;
-        PL_HIP(hipMalloc(&b.seq, b.seq_cap));
+        CV_HIP(hipMalloc(&b.seq, b.seq_cap));
     }
     return 0;
 }
@@ -1030,7 +1021,7 @@ extern "C" int cv_pileup_reserve_bam_dev(cv_pileup *p, int64_t nseg, int64_t nq,
     if (!segs_dev || !seq_dev || nseg < 1) { cv_set_error("cv_pileup_reserve_bam_dev: bad argument"); return 1; }
     if (bam_dev_args(p, nseg, nq, "cv_pileup_reserve_bam_dev")) return 1;
     if (cv_pileup_flush(p, stream)) return 1;
-    PL_HIP(hipSetDevice(p->device));
+    CV_HIP(hipSetDevice(p->device));
     if (p->has_reserved && p->retain) free_batch(p->reserved);             // reserved and never handed over
     p->has_reserved = false;
     if (p->retain) p->reserved = dev_batch();
@@ -1059,23 +1050,23 @@ extern "C" int cv_pileup_add_bam_dev(cv_pileup *p, const void *segs_dev, int64_t
     p->prev_pos = state[0]; p->depth_cap = state[1]; p->evc_prev_pos = state[2]; p->evc_reads = state[3];
     p->cols += cols;
     if (nseg == 0) return 0;
-    PL_HIP(hipSetDevice(p->device));
+    CV_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     const size_t ns = (size_t)nseg;
     dev_batch fresh;
     dev_batch &b = in_place ? (p->retain ? p->reserved : p->work) : (p->retain ? fresh : p->work);
     if (!in_place) {
         if (batch_room(p, b, ns, (size_t)nq + 64, st)) return 1;
-        PL_HIP(hipMemcpyAsync(b.segs, segs_dev, ns * sizeof(seg_t), hipMemcpyDeviceToDevice, st));
-        if (nq > 0) PL_HIP(hipMemcpyAsync(b.seq, seq_dev, (size_t)nq, hipMemcpyDeviceToDevice, st));
+        CV_HIP(hipMemcpyAsync(b.segs, segs_dev, ns * sizeof(seg_t), hipMemcpyDeviceToDevice, st));
+        if (nq > 0) CV_HIP(hipMemcpyAsync(b.seq, seq_dev, (size_t)nq, hipMemcpyDeviceToDevice, st));
     }
     b.nseg = ns;
     if (p->evc && !p->pos_cnt) {
         const size_t bytes = (size_t)(p->ref_len > 0 ? p->ref_len : 1) * NPOS * sizeof(int32_t);
-        PL_HIP(hipMalloc(&p->pos_cnt, bytes));
-        PL_HIP(hipMemsetAsync(p->pos_cnt, 0, bytes, st));
+        CV_HIP(hipMalloc(&p->pos_cnt, bytes));
+        CV_HIP(hipMemsetAsync(p->pos_cnt, 0, bytes, st));
     }
-    PL_HIP(hipMemsetAsync(b.seq + nq, 0, 64, st));
+    CV_HIP(hipMemsetAsync(b.seq + nq, 0, 64, st));
     if (p->evc) {
         if (p->eve.size() >= 128 && drain(p->eve, p->ms_evc)) return 1;
         {
@@ -1083,13 +1074,13 @@ extern "C" int cv_pileup_add_bam_dev(cv_pileup *p, const void *segs_dev, int64_t
             evc_count<<<(unsigned)((ns + EVC_SEGS - 1) / EVC_SEGS), 1024, 0, st>>>(b.segs, (int64_t)ns, b.seq, p->ref_first,
                                                                                    p->ref_len, p->pos_cnt);
         }
-        PL_HIP(hipGetLastError());
+        CV_HIP(hipGetLastError());
     }
     if (p->cand_dev && launch_scatter(p, b, st)) return 1;
     if (p->retain) p->kept.push_back(b);
     if (in_place) { p->has_reserved = false; p->reserved = dev_batch(); }
     p->nsegs += (int64_t)ns;
-    PL_HIP(hipStreamSynchronize(st));
+    CV_HIP(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -1112,11 +1103,11 @@ static int bed_upload(bed_dev &d, const int64_t *bed_begin, const int64_t *bed_e
         else { bb.push_back(x.first); be.push_back(x.second); }
     }
     const size_t nb1 = bb.size() ? bb.size() : 1;
-    PL_HIP(hipMalloc(&d.bb, nb1 * sizeof(int64_t)));
-    PL_HIP(hipMalloc(&d.be, nb1 * sizeof(int64_t)));
+    CV_HIP(hipMalloc(&d.bb, nb1 * sizeof(int64_t)));
+    CV_HIP(hipMalloc(&d.be, nb1 * sizeof(int64_t)));
     if (!bb.empty()) {
-        PL_HIP(hipMemcpy(d.bb, bb.data(), bb.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        PL_HIP(hipMemcpy(d.be, be.data(), be.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        CV_HIP(hipMemcpy(d.bb, bb.data(), bb.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        CV_HIP(hipMemcpy(d.be, be.data(), be.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     }
     d.n = (int)bb.size();
     return 0;
@@ -1144,8 +1135,8 @@ static int select_entries(cv_pileup *p, const Pred &pred, hipStream_t st)
     hipFree(p->sel_dev); p->sel_dev = nullptr; p->nsel_dev = 0;
     const int64_t items = p->ref_len * 2;
     int64_t *count_dev = nullptr;
-    PL_HIP(hipMalloc(&p->sel_dev, (size_t)items * sizeof(int64_t)));
-    PL_HIP(hipMalloc(&count_dev, sizeof(int64_t)));
+    CV_HIP(hipMalloc(&p->sel_dev, (size_t)items * sizeof(int64_t)));
+    CV_HIP(hipMalloc(&count_dev, sizeof(int64_t)));
     int64_t nsel = 0;
     void *tmp = nullptr;
     size_t tmp_bytes = 0;
@@ -1156,22 +1147,22 @@ static int select_entries(cv_pileup *p, const Pred &pred, hipStream_t st)
         const int cnt = (int)std::min<int64_t>(SLICE, items - off);
         hipcub::CountingInputIterator<int64_t> it(off);
         size_t need = 0;
-        PL_HIP(hipcub::DeviceSelect::If(nullptr, need, it, p->sel_dev + written, count_dev, cnt, pred, st));
-        if (need > tmp_bytes) { hipFree(tmp); tmp = nullptr; PL_HIP(hipMalloc(&tmp, need)); tmp_bytes = need; }
+        CV_HIP(hipcub::DeviceSelect::If(nullptr, need, it, p->sel_dev + written, count_dev, cnt, pred, st));
+        if (need > tmp_bytes) { hipFree(tmp); tmp = nullptr; CV_HIP(hipMalloc(&tmp, need)); tmp_bytes = need; }
         {
             timed t(p->eve, st);
-            PL_HIP(hipcub::DeviceSelect::If(tmp, need, it, p->sel_dev + written, count_dev, cnt, pred, st));
+            CV_HIP(hipcub::DeviceSelect::If(tmp, need, it, p->sel_dev + written, count_dev, cnt, pred, st));
         }
-        PL_HIP(hipMemcpyAsync(&nsel, count_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        PL_HIP(hipStreamSynchronize(st));
+        CV_HIP(hipMemcpyAsync(&nsel, count_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        CV_HIP(hipStreamSynchronize(st));
         written += nsel;
     }
     hipFree(tmp); hipFree(count_dev);
     // the select needed room for every entry of the window; what stays resident is the selected ones only
     int64_t *fit = nullptr;
-    PL_HIP(hipMalloc(&fit, (size_t)(written > 0 ? written : 1) * sizeof(int64_t)));
-    if (written) PL_HIP(hipMemcpyAsync(fit, p->sel_dev, (size_t)written * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-    PL_HIP(hipStreamSynchronize(st));
+    CV_HIP(hipMalloc(&fit, (size_t)(written > 0 ? written : 1) * sizeof(int64_t)));
+    if (written) CV_HIP(hipMemcpyAsync(fit, p->sel_dev, (size_t)written * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    CV_HIP(hipStreamSynchronize(st));
     hipFree(p->sel_dev);
     p->sel_dev = fit;
     p->nsel_dev = written;
@@ -1186,12 +1177,12 @@ static int fetch_selected(cv_pileup *p, hipStream_t st)
     p->sel_counts.resize((size_t)written * 7);
     if (written) {
         int32_t *c7 = nullptr;
-        PL_HIP(hipMalloc(&c7, (size_t)written * 7 * sizeof(int32_t)));
+        CV_HIP(hipMalloc(&c7, (size_t)written * 7 * sizeof(int32_t)));
         evc_gather<<<(unsigned)((written + 255) / 256), 256, 0, st>>>(p->sel_dev, written, p->pos_cnt, c7);
-        PL_HIP(hipGetLastError());
-        PL_HIP(hipMemcpyAsync(p->sel_host.data(), p->sel_dev, (size_t)written * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        PL_HIP(hipMemcpyAsync(p->sel_counts.data(), c7, (size_t)written * 7 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        PL_HIP(hipStreamSynchronize(st));
+        CV_HIP(hipGetLastError());
+        CV_HIP(hipMemcpyAsync(p->sel_host.data(), p->sel_dev, (size_t)written * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        CV_HIP(hipMemcpyAsync(p->sel_counts.data(), c7, (size_t)written * 7 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        CV_HIP(hipStreamSynchronize(st));
         hipFree(c7);
     }
     p->sel_host_stale = false;
@@ -1205,7 +1196,7 @@ extern "C" int cv_pileup_extract_candidates(cv_pileup *p, double threshold, doub
     if (!p || !n_out) { cv_set_error("cv_pileup_extract_candidates: null argument"); return 1; }
     if (!p->evc) { cv_set_error("cv_pileup_extract_candidates: option 'evc' was not set"); return 1; }
     if (cv_pileup_flush(p, stream)) return 1;
-    PL_HIP(hipSetDevice(p->device));
+    CV_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     p->sel_host.clear(); p->sel_counts.clear();
     hipFree(p->sel_dev); p->sel_dev = nullptr; p->nsel_dev = 0; p->sel_host_stale = false;
@@ -1230,7 +1221,7 @@ extern "C" int cv_pileup_sample_candidates(cv_pileup *p, uint64_t seed, double o
     if (!p->evc) { cv_set_error("cv_pileup_sample_candidates: option 'evc' was not set"); return 1; }
     if (p->contig.empty()) { cv_set_error("cv_pileup_sample_candidates: no contig set (the draws are keyed by its name)"); return 1; }
     if (cv_pileup_flush(p, stream)) return 1;
-    PL_HIP(hipSetDevice(p->device));
+    CV_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     p->sel_host.clear(); p->sel_counts.clear();
     hipFree(p->sel_dev); p->sel_dev = nullptr; p->nsel_dev = 0; p->sel_host_stale = false;
@@ -1252,7 +1243,7 @@ extern "C" int cv_pileup_get_extracted(cv_pileup *p, int64_t *pos0, int32_t *lat
 {
     if (!p) { cv_set_error("cv_pileup_get_extracted: null handle"); return 1; }
     if (p->sel_host_stale) {
-        PL_HIP(hipSetDevice(p->device));
+        CV_HIP(hipSetDevice(p->device));
         if (fetch_selected(p, (hipStream_t)0)) return 1;
     }
     for (size_t i = 0; i < p->sel_host.size(); ++i) {
@@ -1270,7 +1261,7 @@ extern "C" int cv_pileup_adopt_candidates(cv_pileup *p, int has_range, int64_t l
     if (!p) { cv_set_error("cv_pileup_adopt_candidates: null handle"); return 1; }
     if (!p->retain) { cv_set_error("cv_pileup_adopt_candidates: option 'retain' was not set"); return 1; }
     if (cv_pileup_flush(p, stream)) return 1;
-    PL_HIP(hipSetDevice(p->device));
+    CV_HIP(hipSetDevice(p->device));
     if (p->sel_host_stale && fetch_selected(p, (hipStream_t)stream)) return 1;
     std::vector<int32_t> c32;
     for (size_t i = 0; i < p->sel_host.size(); ++i) {
@@ -1345,7 +1336,7 @@ extern "C" int cv_pileup_adopt_union(cv_pileup *p, int has_range, int64_t lo1, i
             return 1;
         }
     if (cv_pileup_flush(p, stream)) return 1;
-    PL_HIP(hipSetDevice(p->device));
+    CV_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     const int64_t ns = p->sel_dev ? p->nsel_dev : 0, m = ns + ntruth;
     if (m >= (1LL << 31) - 1) { cv_set_error("cv_pileup_adopt_union: %lld entries, more than one sort takes", (long long)m); return 1; }
@@ -1360,45 +1351,43 @@ extern "C" int cv_pileup_adopt_union(cv_pileup *p, int has_range, int64_t lo1, i
         uint8_t *val_in = nullptr, *val_out = nullptr;
         void *ws = nullptr;
         size_t a = 0, b = 0;
-        PL_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, a, (const int32_t *)nullptr, (int32_t *)nullptr, (const uint8_t *)nullptr,
-                                                  (uint8_t *)nullptr, (int)m, 0, 32, st));
-        PL_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t *)nullptr, (int32_t *)nullptr, (int)(m + 1), st));
+        if (cv_sort_pairs_temp_bytes<int32_t, uint8_t>(m, &a) || cv_scan_temp_bytes<int32_t>(m + 1, &b)) return 1;
         const size_t ws_bytes = a > b ? a : b;
-        PL_HIP(tmp.alloc(&truth_dev, (size_t)ntruth * 8));
-        PL_HIP(tmp.alloc(&key_in, (size_t)m * 4)); PL_HIP(tmp.alloc(&key_out, (size_t)m * 4));
-        PL_HIP(tmp.alloc(&val_in, (size_t)m)); PL_HIP(tmp.alloc(&val_out, (size_t)m));
-        PL_HIP(tmp.alloc(&head, (size_t)(m + 1) * 4)); PL_HIP(tmp.alloc(&before, (size_t)(m + 1) * 4));
-        PL_HIP(tmp.alloc(&cands, (size_t)m * 4)); PL_HIP(tmp.alloc(&flags, (size_t)m));
-        PL_HIP(tmp.alloc(&ws, ws_bytes));
-        if (ntruth) PL_HIP(hipMemcpyAsync(truth_dev, truth, (size_t)ntruth * 8, hipMemcpyHostToDevice, st));
+        CV_HIP(tmp.alloc(&truth_dev, (size_t)ntruth * 8));
+        CV_HIP(tmp.alloc(&key_in, (size_t)m * 4)); CV_HIP(tmp.alloc(&key_out, (size_t)m * 4));
+        CV_HIP(tmp.alloc(&val_in, (size_t)m)); CV_HIP(tmp.alloc(&val_out, (size_t)m));
+        CV_HIP(tmp.alloc(&head, (size_t)(m + 1) * 4)); CV_HIP(tmp.alloc(&before, (size_t)(m + 1) * 4));
+        CV_HIP(tmp.alloc(&cands, (size_t)m * 4)); CV_HIP(tmp.alloc(&flags, (size_t)m));
+        CV_HIP(tmp.alloc(&ws, ws_bytes));
+        if (ntruth) CV_HIP(hipMemcpyAsync(truth_dev, truth, (size_t)ntruth * 8, hipMemcpyHostToDevice, st));
         const unsigned grid = (unsigned)((m + 1 + 255) / 256);
         {
             timed t(p->eve, st);
             union_fill<<<grid, 256, 0, st>>>(p->sel_dev, ns, p->ref_first, has_range, lo1, hi1, truth_dev, ntruth, key_in, val_in);
             size_t wb = ws_bytes;
-            PL_HIP(hipcub::DeviceRadixSort::SortPairs(ws, wb, (const int32_t *)key_in, key_out, (const uint8_t *)val_in, val_out, (int)m,
+            CV_HIP(hipcub::DeviceRadixSort::SortPairs(ws, wb, (const int32_t *)key_in, key_out, (const uint8_t *)val_in, val_out, (int)m,
                                                       0, 32, st));
             union_heads<<<grid, 256, 0, st>>>(key_out, m, head);
             wb = ws_bytes;
-            PL_HIP(hipcub::DeviceScan::ExclusiveSum(ws, wb, (const int32_t *)head, before, (int)(m + 1), st));
+            CV_HIP(hipcub::DeviceScan::ExclusiveSum(ws, wb, (const int32_t *)head, before, (int)(m + 1), st));
             union_write<<<grid, 256, 0, st>>>(key_out, val_out, head, before, m, cands, flags);
         }
-        PL_HIP(hipGetLastError());
+        CV_HIP(hipGetLastError());
         int32_t n32 = 0;
-        PL_HIP(hipMemcpyAsync(&n32, before + m, 4, hipMemcpyDeviceToHost, st));
-        PL_HIP(hipStreamSynchronize(st));                 // (also: `truth` may go after the call)
+        CV_HIP(hipMemcpyAsync(&n32, before + m, 4, hipMemcpyDeviceToHost, st));
+        CV_HIP(hipStreamSynchronize(st));                 // (also: `truth` may go after the call)
         n = n32;
         if (n > 0) {
-            PL_HIP(hipMemcpyAsync(&ends[0], cands, 4, hipMemcpyDeviceToHost, st));
-            PL_HIP(hipMemcpyAsync(&ends[1], cands + (n - 1), 4, hipMemcpyDeviceToHost, st));
-            PL_HIP(hipStreamSynchronize(st));
+            CV_HIP(hipMemcpyAsync(&ends[0], cands, 4, hipMemcpyDeviceToHost, st));
+            CV_HIP(hipMemcpyAsync(&ends[1], cands + (n - 1), 4, hipMemcpyDeviceToHost, st));
+            CV_HIP(hipStreamSynchronize(st));
         }
     }
     if (install_alloc(p, n)) return 1;
-    PL_HIP(hipMalloc(&p->cflag_dev, (size_t)(n > 0 ? n : 1)));
+    CV_HIP(hipMalloc(&p->cflag_dev, (size_t)(n > 0 ? n : 1)));
     if (n > 0) {
-        PL_HIP(hipMemcpy(p->cand_dev, cands, (size_t)n * 4, hipMemcpyDeviceToDevice));
-        PL_HIP(hipMemcpy(p->cflag_dev, flags, (size_t)n, hipMemcpyDeviceToDevice));
+        CV_HIP(hipMemcpy(p->cand_dev, cands, (size_t)n * 4, hipMemcpyDeviceToDevice));
+        CV_HIP(hipMemcpy(p->cflag_dev, flags, (size_t)n, hipMemcpyDeviceToDevice));
     }
     if (install_buckets(p, ends[0], ends[1])) return 1;
     for (const auto &b : p->kept) if (launch_scatter(p, b, st)) return 1;
@@ -1427,16 +1416,16 @@ extern "C" int cv_pileup_recount(cv_pileup *p, void *stream)
     if (!p->evc || !p->retain) { cv_set_error("cv_pileup_recount: needs options 'evc' and 'retain'"); return 1; }
     if (cv_pileup_flush(p, stream)) return 1;
     if (!p->pos_cnt) return 0;
-    PL_HIP(hipSetDevice(p->device));
+    CV_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
     if (p->eve.size() >= 128 && drain(p->eve, p->ms_evc)) return 1;
-    PL_HIP(hipMemsetAsync(p->pos_cnt, 0, (size_t)p->ref_len * NPOS * sizeof(int32_t), st));
+    CV_HIP(hipMemsetAsync(p->pos_cnt, 0, (size_t)p->ref_len * NPOS * sizeof(int32_t), st));
     for (const auto &b : p->kept) {
         timed t(p->eve, st);
         evc_count<<<(unsigned)((b.nseg + EVC_SEGS - 1) / EVC_SEGS), 1024, 0, st>>>(b.segs, (int64_t)b.nseg, b.seq,
                                                                                    p->ref_first, p->ref_len, p->pos_cnt);
     }
-    PL_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -1447,8 +1436,8 @@ extern "C" int cv_pileup_get_candidates(cv_pileup *p, int64_t *centers, int64_t 
     if (centers && p->n > 0) {
         if (cap < p->n) { cv_set_error("cv_pileup_get_candidates: buffer holds %lld, need %lld", (long long)cap, (long long)p->n); return 1; }
         std::vector<int32_t> c32((size_t)p->n);
-        PL_HIP(hipSetDevice(p->device));
-        PL_HIP(hipMemcpy(c32.data(), p->cand_dev, (size_t)p->n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        CV_HIP(hipSetDevice(p->device));
+        CV_HIP(hipMemcpy(c32.data(), p->cand_dev, (size_t)p->n * sizeof(int32_t), hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < p->n; ++i) centers[i] = c32[(size_t)i];
     }
     return 0;
@@ -1472,16 +1461,16 @@ extern "C" int cv_pileup_finish(cv_pileup *p, float *tensors_dev, int32_t *depth
                                                                            p->ref_first, p->ref_len, tensors_dev,
                                                                            depth_dev, subtract);
     }
-    PL_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     if (touched_dev)
-        PL_HIP(hipMemcpyAsync(touched_dev, p->touched_dev, (size_t)p->n, hipMemcpyDeviceToDevice, st));
+        CV_HIP(hipMemcpyAsync(touched_dev, p->touched_dev, (size_t)p->n, hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
 extern "C" int cv_pileup_stats(cv_pileup *p, float ms[3], int64_t counts[3])
 {
     if (!p) { cv_set_error("cv_pileup_stats: null handle"); return 1; }
-    PL_HIP(hipSetDevice(p->device));
+    CV_HIP(hipSetDevice(p->device));
     if (drain(p->ev, p->ms_scatter) || drain(p->evf, p->ms_final) || drain(p->eve, p->ms_evc)) return 1;
     if (ms) { ms[0] = p->ms_scatter; ms[1] = p->ms_final; ms[2] = p->ms_evc; }
     if (counts) { counts[0] = p->cols; counts[1] = p->nsegs; counts[2] = p->launches; }

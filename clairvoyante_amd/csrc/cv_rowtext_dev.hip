@@ -18,18 +18,8 @@
 #include <stdint.h>
 #include <string.h>
 #include "../../include/clairvoyante_amd.h"
+#include "cv_dev_scan.hpp"
 #include "cv_rowtext_core.hpp"
-
-void cv_set_error(const char *fmt, ...);
-
-#define RT_HIP(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) {                                                                        \
-            cv_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-            return 1;                                                                                  \
-        }                                                                                              \
-    } while (0)
 
 namespace {
 
@@ -154,14 +144,18 @@ __global__ __launch_bounds__(THREADS) void rowtext_write(CtgName ctg, int ctg_le
 
 constexpr int64_t MAX_ROWS = (int64_t)1 << 30;
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+// the workspace: the row lengths (rows + 1 int64) | hipcub's
+struct rows_ws {
+    int64_t *len;
+    void *tmp;
+    size_t tmp_bytes;
+};
 
-int plan(int64_t rows, size_t *tmp, size_t *tmp_bytes, size_t *total)
+int plan(cv_carver &c, int64_t rows, rows_ws *W)
 {
-    size_t o = up256((size_t)(rows + 1) * 8), a = 0;
-    RT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, a, (const int64_t *)nullptr, (int64_t *)nullptr, (int)(rows + 1), (hipStream_t)0));
-    *tmp = o; *tmp_bytes = a;
-    *total = up256(o + a);
+    W->len = c.take<int64_t>((size_t)(rows + 1));
+    if (cv_scan_temp_bytes<int64_t>(rows + 1, &W->tmp_bytes)) return 1;
+    W->tmp = c.take_bytes(W->tmp_bytes);
     return 0;
 }
 
@@ -180,9 +174,10 @@ extern "C" int cv_tensor_rows_text_workspace(int64_t rows, int64_t *bytes)
 {
     if (!bytes) { cv_set_error("cv_tensor_rows_text_workspace: null argument"); return 1; }
     if (!rows_ok("cv_tensor_rows_text_workspace", rows)) return 1;
-    size_t t, tb, total;
-    if (plan(rows, &t, &tb, &total)) return 1;
-    *bytes = (int64_t)total;
+    cv_carver c;
+    rows_ws W;
+    if (plan(c, rows, &W)) return 1;
+    *bytes = (int64_t)c.total();
     return 0;
 }
 
@@ -198,29 +193,27 @@ extern "C" int cv_tensor_rows_text_dev(const char *ctg, int64_t ctg_len, const i
         cv_set_error("%s: null argument, or a negative length", who);
         return 1;
     }
-    if (((uintptr_t)centres_dev & 7) || ((uintptr_t)off_dev & 7) || ((uintptr_t)counts_dev & 15) || ((uintptr_t)workspace & 255)) {
-        cv_set_error("%s: centres / off must be 8-byte, counts 16-byte, the workspace 256-byte aligned", who);
+    if (((uintptr_t)centres_dev & 7) || ((uintptr_t)off_dev & 7) || ((uintptr_t)counts_dev & 15)) {
+        cv_set_error("%s: centres / off must be 8-byte, counts 16-byte aligned", who);
         return 1;
     }
-    size_t t, tb, total;
-    if (plan(rows, &t, &tb, &total)) return 1;
-    if (workspace_bytes < (int64_t)total) {
-        cv_set_error("%s: workspace holds %lld bytes, need %lld", who, (long long)workspace_bytes, (long long)total);
-        return 1;
-    }
+    cv_carver c(workspace);
+    rows_ws W;
+    if (plan(c, rows, &W)) return 1;
+    if (!cv_workspace_ok(who, workspace, workspace_bytes, c.total())) return 1;
     hipStream_t st = (hipStream_t)stream;
     if (ctg_len > cvr::MAX_CTG) {                   // the whole call is the host's: no lengths, every row CV_ROWTEXT_HOST
-        RT_HIP(hipMemsetAsync(off_dev, 0, (size_t)(rows + 1) * 8, st));
-        if (rows) RT_HIP(hipMemsetAsync(status_dev, CV_ROWTEXT_HOST, (size_t)rows, st));
+        CV_HIP(hipMemsetAsync(off_dev, 0, (size_t)(rows + 1) * 8, st));
+        if (rows) CV_HIP(hipMemsetAsync(status_dev, CV_ROWTEXT_HOST, (size_t)rows, st));
         return 0;
     }
-    char *ws = (char *)workspace;
-    int64_t *len = (int64_t *)ws;
+    int64_t *len = W.len;
+    size_t tb = W.tmp_bytes;
     const unsigned len_blocks = (unsigned)((rows + 1 + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
     hipLaunchKernelGGL(rowtext_len, dim3(len_blocks), dim3(THREADS), 0, st, (int)ctg_len, centres_dev, rows, ref_first0, ref_len,
                        counts_dev, len, status_dev);
-    RT_HIP(hipGetLastError());
-    RT_HIP(hipcub::DeviceScan::ExclusiveSum(ws + t, tb, (const int64_t *)len, off_dev, (int)(rows + 1), st));
+    CV_HIP(hipGetLastError());
+    CV_HIP(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, (const int64_t *)len, off_dev, (int)(rows + 1), st));
     if (text_dev && rows) {
         CtgName name;
         memset(&name, 0, sizeof(name));
@@ -228,7 +221,7 @@ extern "C" int cv_tensor_rows_text_dev(const char *ctg, int64_t ctg_len, const i
         const unsigned blocks = (unsigned)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
         hipLaunchKernelGGL(rowtext_write, dim3(blocks), dim3(THREADS), 0, st, name, (int)ctg_len, centres_dev, rows, ref_dev, ref_first0,
                            ref_len, counts_dev, (const int64_t *)off_dev, (const uint8_t *)status_dev, text_dev, text_cap);
-        RT_HIP(hipGetLastError());
+        CV_HIP(hipGetLastError());
     }
     return 0;
 }

@@ -22,17 +22,7 @@
 #include <stdint.h>
 #include "../../include/clairvoyante_amd.h"
 #include "cv_internal.hpp"
-
-void cv_set_error(const char *fmt, ...);
-
-#define TP_HIP(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) {                                                                        \
-            cv_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-            return 1;                                                                                  \
-        }                                                                                              \
-    } while (0)
+#include "cv_dev_scan.hpp"
 
 namespace {
 
@@ -255,7 +245,7 @@ __global__ __launch_bounds__(PARSE_WAVES * WAVE) void tp_parse_rows(const uint4 
 __global__ __launch_bounds__(256) void tp_gather_rows(const float4 *x, const int64_t *idx, int64_t nrows, float4 *out)
 {
     const int64_t total = nrows * (NV / 4);
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    CV_GRID_STRIDE(e, total) {
         const int64_t r = e / (NV / 4), c = e - r * (NV / 4);
         out[e] = x[idx[r] * (NV / 4) + c];
     }
@@ -296,7 +286,7 @@ __global__ __launch_bounds__(TOKEN_THREADS) void tp_token_offsets(const int64_t 
 __global__ __launch_bounds__(256) void tp_token_copy(const uint8_t *text, const int64_t *meta, const int64_t *idx, int64_t nrows,
                                                      const int64_t *meta_out, uint8_t *bytes, int64_t cap)
 {
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+    CV_GRID_STRIDE(r, nrows) {
         const int64_t *m = meta + idx[r] * 6, *o = meta_out + r * 6;
         for (int t = 0; t < 3; t++) {
             const int64_t from = m[2 * t], to = o[2 * t], n = o[2 * t + 1];
@@ -347,26 +337,38 @@ __global__ __launch_bounds__(TILE_THREADS) void tp_find_newline(const uint4 *gra
     }
 }
 
-struct ws_layout {
+struct index_ws {
     int64_t ntiles_max;         // tiles of a slab of `len` bytes at the worst offset inside its first granule
-    size_t tile_cnt, tile_first, line_end, scan_tmp, scan_bytes, total;
+    uint32_t *tile_cnt, *tile_first;
+    int64_t *line_end;
+    void *scan_tmp;
+    size_t scan_bytes;
 };
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-int layout(int64_t len, int64_t max_lines, ws_layout *L)
+int index_plan(cv_carver &c, int64_t len, int64_t max_lines, index_ws *W)
 {
-    L->ntiles_max = (len + 15 + TILE - 1) / TILE;
-    size_t o = 0;
-    L->tile_cnt = o; o = up256(o + (size_t)(L->ntiles_max + 1) * 4);
-    L->tile_first = o; o = up256(o + (size_t)(L->ntiles_max + 1) * 4);
-    L->line_end = o; o = up256(o + (size_t)(max_lines > 0 ? max_lines : 1) * 8);
-    size_t need = 0;
-    TP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, (const uint32_t *)nullptr, (uint32_t *)nullptr,
-                                            (int)(L->ntiles_max + 1), (hipStream_t)0));
-    L->scan_tmp = o; L->scan_bytes = need; o = up256(o + need);
-    L->total = o;
+    W->ntiles_max = (len + 15 + TILE - 1) / TILE;
+    W->tile_cnt = c.take<uint32_t>((size_t)(W->ntiles_max + 1));
+    W->tile_first = c.take<uint32_t>((size_t)(W->ntiles_max + 1));
+    W->line_end = c.take<int64_t>((size_t)(max_lines > 0 ? max_lines : 1));
+    if (cv_scan_temp_bytes<uint32_t>(W->ntiles_max + 1, &W->scan_bytes)) return 1;
+    W->scan_tmp = c.take_bytes(W->scan_bytes);
     return 0;
+}
+
+// cv_text_run_flags: one thread per line
+__global__ __launch_bounds__(256) void tp_run_flags(const uint8_t *text, const int64_t *span, const int32_t *isrow, int64_t max_lines,
+                                                    int32_t *flag)
+{
+    CV_GRID_STRIDE(i, max_lines + 1) {
+        int f = 0;
+        if (i < max_lines && isrow[i]) {
+            f = i == 0 || !isrow[i - 1] || span[2 * i + 1] != span[2 * i - 1];
+            const uint8_t *a = text + span[2 * i], *b = f ? a : text + span[2 * i - 2];
+            for (int64_t k = 0; !f && k < span[2 * i + 1]; ++k) f = a[k] != b[k];
+        }
+        flag[i] = f;
+    }
 }
 
 }  // namespace
@@ -376,37 +378,44 @@ int layout(int64_t len, int64_t max_lines, ws_layout *L)
 // {bytes consumed, lines, 0, 0}.  Enqueued on st; allocates nothing.
 int cv_text_line_index_bytes(int64_t len, int64_t max_lines, size_t *bytes)
 {
-    ws_layout L;
-    if (layout(len, max_lines, &L)) return 1;
-    *bytes = L.total;
+    cv_carver c;
+    index_ws W;
+    if (index_plan(c, len, max_lines, &W)) return 1;
+    *bytes = c.total();
     return 0;
 }
 
 int cv_text_line_index(const char *text_dev, int64_t len, int64_t max_lines, void *workspace_dev, int64_t *info_dev,
                        const int64_t **line_end_dev, hipStream_t st)
 {
-    ws_layout L;
-    if (layout(len, max_lines, &L)) return 1;
-    char *ws = (char *)workspace_dev;
-    uint32_t *tile_cnt = (uint32_t *)(ws + L.tile_cnt), *tile_first = (uint32_t *)(ws + L.tile_first);
-    int64_t *line_end = (int64_t *)(ws + L.line_end);
+    cv_carver c(workspace_dev);
+    index_ws W;
+    if (index_plan(c, len, max_lines, &W)) return 1;
+    uint32_t *tile_cnt = W.tile_cnt, *tile_first = W.tile_first;
+    int64_t *line_end = W.line_end;
     const int shift = (int)((uintptr_t)text_dev & 15);
     const uint4 *gran = (const uint4 *)(text_dev - shift);
     // (the tile count of the worst offset: what the workspace and the scan were sized for; a tile behind the slab counts 0)
-    const int64_t ntiles = len > 0 && max_lines > 0 ? L.ntiles_max : 0;
+    const int64_t ntiles = len > 0 && max_lines > 0 ? W.ntiles_max : 0;
     if (ntiles > 0) {
         const int grid = (int)(ntiles < INDEX_GRID ? ntiles : INDEX_GRID);
         hipLaunchKernelGGL(tp_count_newlines, dim3(grid), dim3(TILE_THREADS), 0, st, gran, shift, len, ntiles, tile_cnt);
-        size_t need = L.scan_bytes;
-        TP_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.scan_tmp, need, (const uint32_t *)tile_cnt, tile_first, (int)(ntiles + 1), st));
+        size_t need = W.scan_bytes;
+        CV_HIP(hipcub::DeviceScan::ExclusiveSum(W.scan_tmp, need, (const uint32_t *)tile_cnt, tile_first, (int)(ntiles + 1), st));
         hipLaunchKernelGGL(tp_line_ends, dim3(grid), dim3(TILE_THREADS), 0, st, gran, shift, len, ntiles,
                            (const uint32_t *)tile_first, max_lines, line_end);
     }
     hipLaunchKernelGGL(tp_begin, dim3(1), dim3(64), 0, st, (const uint32_t *)tile_first, ntiles, max_lines,
                        (const int64_t *)line_end, info_dev);
-    TP_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     *line_end_dev = line_end;
     return 0;
+}
+
+void cv_text_run_flags(const uint8_t *text_dev, const int64_t *span_dev, const int32_t *isrow_dev, int64_t max_lines, int32_t *flag_dev,
+                       hipStream_t st)
+{
+    hipLaunchKernelGGL(tp_run_flags, dim3(cv_grid_for(max_lines + 1)), dim3(256), 0, st, text_dev, span_dev, isrow_dev, max_lines, flag_dev);
 }
 
 extern "C" int cv_parse_tensor_text_dev_workspace(int64_t len, int64_t max_lines, int64_t *bytes)
@@ -417,9 +426,9 @@ extern "C" int cv_parse_tensor_text_dev_workspace(int64_t len, int64_t max_lines
                      (long long)len, (long long)max_lines, (long long)CV_TEXT_SLAB_MAX);
         return 1;
     }
-    ws_layout L;
-    if (layout(len, max_lines, &L)) return 1;
-    *bytes = (int64_t)L.total;
+    size_t need = 0;
+    if (cv_text_line_index_bytes(len, max_lines, &need)) return 1;
+    *bytes = (int64_t)need;
     return 0;
 }
 
@@ -436,28 +445,24 @@ extern "C" int cv_parse_tensor_text_dev(const char *text_dev, int64_t len, int64
                      (long long)max_lines, (long long)CV_TEXT_SLAB_MAX);
         return 1;
     }
-    if (((uintptr_t)x_dev & 15) || ((uintptr_t)meta_dev & 7) || ((uintptr_t)info_dev & 7) || ((uintptr_t)workspace_dev & 255)) {
-        cv_set_error("cv_parse_tensor_text_dev: x_dev must be 16-byte, meta_dev / info_dev 8-byte, the workspace 256-byte aligned");
+    if (((uintptr_t)x_dev & 15) || ((uintptr_t)meta_dev & 7) || ((uintptr_t)info_dev & 7)) {
+        cv_set_error("cv_parse_tensor_text_dev: x_dev must be 16-byte, meta_dev / info_dev 8-byte aligned");
         return 1;
     }
-    ws_layout L;
-    if (layout(len, max_lines, &L)) return 1;
-    if (workspace_bytes < (int64_t)L.total) {
-        cv_set_error("cv_parse_tensor_text_dev: workspace holds %lld bytes, need %lld", (long long)workspace_bytes, (long long)L.total);
-        return 1;
-    }
+    size_t need = 0;
+    if (cv_text_line_index_bytes(len, max_lines, &need)) return 1;
+    if (!cv_workspace_ok("cv_parse_tensor_text_dev", workspace_dev, workspace_bytes, need)) return 1;
     hipStream_t st = (hipStream_t)stream;
     const int64_t *line_end = nullptr;
     if (cv_text_line_index(text_dev, len, max_lines, workspace_dev, info_dev, &line_end, st)) return 1;
     const int shift = (int)((uintptr_t)text_dev & 15);
     const uint4 *gran = (const uint4 *)(text_dev - shift);
-    const int64_t ntiles = len > 0 && max_lines > 0 ? L.ntiles_max : 0;
-    if (ntiles > 0) {
+    if (len > 0 && max_lines > 0) {
         const int64_t blocks = (max_lines + PARSE_WAVES - 1) / PARSE_WAVES;
         hipLaunchKernelGGL(tp_parse_rows, dim3((int)(blocks < PARSE_GRID ? blocks : PARSE_GRID)), dim3(PARSE_WAVES * WAVE), 0, st,
                            gran, shift, line_end, info_dev, x_dev, meta_dev, status_dev);
     }
-    TP_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -473,7 +478,7 @@ extern "C" int cv_text_gather_rows(const float *x_dev, const int64_t *index_dev,
     const int64_t blocks = (nrows * (NV / 4) + 255) / 256;
     hipLaunchKernelGGL(tp_gather_rows, dim3((int)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
                        (const float4 *)x_dev, index_dev, nrows, (float4 *)out_dev);
-    TP_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -500,7 +505,7 @@ extern "C" int cv_text_find_newline_dev(const char *text_dev, int64_t len, const
         hipLaunchKernelGGL(tp_find_newline, dim3((int)(ntiles < FIND_GRID ? ntiles : FIND_GRID)), dim3(TILE_THREADS), 0, st,
                            (const uint4 *)(text_dev - shift), shift, len, q, k, out_dev);
     }
-    TP_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -518,6 +523,6 @@ extern "C" int cv_text_gather_tokens(const char *text_dev, const int64_t *meta_d
     const int64_t blocks = (nrows + 255) / 256;
     hipLaunchKernelGGL(tp_token_copy, dim3((int)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
                        (const uint8_t *)text_dev, meta_dev, index_dev, nrows, (const int64_t *)meta_out_dev, bytes_dev, bytes_cap);
-    TP_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }

@@ -7,7 +7,7 @@
 //                    row before" (row 0: always), flag "sequence token holds ':' or a byte >= 0x80"
 //   hipcub InclusiveSum over the run-start flags -> run[r] = index of the row's contig run inside the slab
 //   ts_join          one thread per row: contig id of its run (a table the host filled from the run-start tokens), the
-//                    BED test of _Intervals.hit (upper bound on the sorted begins + running maximum of the ends), the
+//                    BED test of _Intervals.hit (cvb::stab: upper bound on the sorted begins + running maximum of the ends), the
 //                    index of (contig id, position) in the truth table
 //
 //   once, over all rows in arrival order:
@@ -24,32 +24,20 @@
 #include <stdint.h>
 #include "../../include/clairvoyante_amd.h"
 
-void cv_set_error(const char *fmt, ...);
-
-#define TS_HIP(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) {                                                                        \
-            cv_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-            return 1;                                                                                  \
-        }                                                                                              \
-    } while (0)
+#include "cv_dev_scan.hpp"
+#include "cv_beditems_core.hpp"
 
 namespace {
 
 constexpr int NV = CV_INPUT_H * CV_INPUT_W * CV_INPUT_C;     // 528
 constexpr int CENTRE = CV_INPUT_H / 2;                       // 16: the 17th character of the sequence token
 constexpr int THREADS = 256;
-constexpr int MAX_GRID = 4096;
 constexpr uint64_t KEY_DROPPED = ~(uint64_t)0;
-
-inline int grid_for(int64_t n) { const int64_t b = (n + THREADS - 1) / THREADS; return (int)(b < 1 ? 1 : b < MAX_GRID ? b : MAX_GRID); }
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 __global__ __launch_bounds__(THREADS) void ts_tokens(const uint8_t *text, const int64_t *meta, const int64_t *idx, int64_t nrows,
                                                      int64_t *pos, uint8_t *digits, uint8_t *centre, uint8_t *flags, int32_t *start)
 {
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+    CV_GRID_STRIDE(r, nrows) {
         const int64_t *m = meta + (idx ? idx[r] : r) * 6;
         uint8_t f = 0;
         // coordinate: canonical decimal = digits only, no leading zero unless it is "0", at most 12 digits
@@ -92,18 +80,7 @@ __global__ __launch_bounds__(THREADS) void ts_tokens(const uint8_t *text, const 
 __global__ __launch_bounds__(THREADS) void ts_run_index(int32_t *run, int64_t nrows)
 {
     // inclusive count of run starts -> index of the run (row 0 starts run 0)
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * blockDim.x) run[r] -= 1;
-}
-
-// number of elements of the sorted a[0, n) that are <= v
-__device__ __forceinline__ int64_t upper_bound(const int64_t *a, int64_t n, int64_t v)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a[mid] <= v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+    CV_GRID_STRIDE(r, nrows) run[r] -= 1;
 }
 
 __global__ __launch_bounds__(THREADS) void ts_join(int64_t nrows, const int32_t *run, const int32_t *run_ctg, int64_t nruns,
@@ -111,7 +88,7 @@ __global__ __launch_bounds__(THREADS) void ts_join(int64_t nrows, const int32_t 
                                                    const int64_t *bed_begin, const int64_t *bed_emax, const int64_t *truth_off,
                                                    const int64_t *truth_pos, int32_t *ctg, uint8_t *keep, int32_t *truth)
 {
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+    CV_GRID_STRIDE(r, nrows) {
         const int32_t k = run[r];
         const int32_t c = k >= 0 && k < nruns ? run_ctg[k] : -1;
         const int64_t p = pos[r];
@@ -121,14 +98,13 @@ __global__ __launch_bounds__(THREADS) void ts_join(int64_t nrows, const int32_t 
             kp = false;
             if (tabled) {
                 const int64_t lo = bed_off[c], n = bed_off[c + 1] - lo;
-                const int64_t u = upper_bound(bed_begin + lo, n, p);
-                kp = u > 0 && bed_emax[lo + u - 1] > p;
+                kp = cvb::stab(bed_begin + lo, bed_emax + lo, n, p);
             }
         }
         int32_t t = -1;
         if (tabled && truth_off) {
             const int64_t lo = truth_off[c], n = truth_off[c + 1] - lo;
-            const int64_t u = upper_bound(truth_pos + lo, n, p);
+            const int64_t u = cvb::upper_bound(truth_pos + lo, n, p);
             if (u > 0 && truth_pos[lo + u - 1] == p) t = (int32_t)(lo + u - 1);
         }
         ctg[r] = c;
@@ -143,7 +119,7 @@ __device__ const int64_t ts_pow10[13] = {1ll, 10ll, 100ll, 1000ll, 10000ll, 1000
 __global__ __launch_bounds__(THREADS) void ts_keys(int64_t nrows, const int32_t *ctg, const int64_t *pos, const uint8_t *digits,
                                                    const uint8_t *keep, const int32_t *rank, int32_t nctg, uint64_t *key, int64_t *val)
 {
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+    CV_GRID_STRIDE(r, nrows) {
         const int32_t c = ctg[r];
         const int d = digits[r];
         uint64_t k = KEY_DROPPED;
@@ -156,14 +132,14 @@ __global__ __launch_bounds__(THREADS) void ts_keys(int64_t nrows, const int32_t 
 
 __global__ __launch_bounds__(THREADS) void ts_heads(int64_t nrows, const uint64_t *key, int32_t *head)
 {
-    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j <= nrows; j += (int64_t)gridDim.x * blockDim.x)
+    CV_GRID_STRIDE(j, nrows + 1)
         head[j] = j < nrows && key[j] != KEY_DROPPED && (j == 0 || key[j] != key[j - 1]) ? 1 : 0;   // (slot nrows: its scanned value is the total)
 }
 
 __global__ __launch_bounds__(THREADS) void ts_entries(int64_t nrows, const uint64_t *key, const int64_t *val, const int32_t *head,
                                                       const int32_t *before, int64_t *src, int64_t *first, int64_t *total)
 {
-    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nrows; j += (int64_t)gridDim.x * blockDim.x) {
+    CV_GRID_STRIDE(j, nrows) {
         if (key[j] == KEY_DROPPED) continue;
         const int64_t e = (int64_t)before[j] + head[j] - 1;          // the entry this sorted slot belongs to
         if (head[j]) first[e] = val[j];                              // (stable sort: the lowest arrival index comes first)
@@ -177,7 +153,7 @@ __global__ __launch_bounds__(THREADS) void ts_labels(const int32_t *before, int6
                                                      int64_t ntruth, float *y)
 {
     const int64_t total = before[nrows];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total * 16; i += (int64_t)gridDim.x * blockDim.x) {
+    CV_GRID_STRIDE(i, total * 16) {
         const int64_t e = i >> 4;
         const int k = (int)(i & 15);
         const int32_t t = truth[src[e]];
@@ -194,7 +170,7 @@ __global__ __launch_bounds__(THREADS) void ts_gather(const float4 *x_all, const 
                                                      int64_t total, float4 *x_out, float4 *y_out)
 {
     constexpr int XQ = NV / 4, Q = XQ + 4;                   // 16-byte pieces of one item: its row and its label
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total * Q; e += (int64_t)gridDim.x * blockDim.x) {
+    CV_GRID_STRIDE(e, total * Q) {
         const int64_t r = e / Q;
         const int c = (int)(e - r * Q);
         const int64_t from = perm ? perm[r] : r;
@@ -203,38 +179,44 @@ __global__ __launch_bounds__(THREADS) void ts_gather(const float4 *x_all, const 
     }
 }
 
-struct finish_layout {
-    size_t key_in, key_out, val_in, val_out, head, before, first, tmp, tmp_bytes, total;
+struct finish_ws {
+    uint64_t *key_in, *key_out;
+    int64_t *val_in, *val_out;
+    int32_t *head, *before;
+    int64_t *first;
+    void *tmp;
+    size_t tmp_bytes;
 };
 
-int finish_plan(int64_t nrows, finish_layout *L)
+int finish_plan(cv_carver &c, int64_t nrows, finish_ws *W)
 {
     const size_t n = (size_t)(nrows > 0 ? nrows : 1);
-    size_t o = 0;
-    L->key_in = o; o = up256(o + n * 8);
-    L->key_out = o; o = up256(o + n * 8);
-    L->val_in = o; o = up256(o + n * 8);
-    L->val_out = o; o = up256(o + n * 8);
-    L->head = o; o = up256(o + (n + 1) * 4);
-    L->before = o; o = up256(o + (n + 1) * 4);
-    L->first = o; o = up256(o + n * 8);
     size_t a = 0, b = 0;
-    TS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, a, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const int64_t *)nullptr,
-                                              (int64_t *)nullptr, (int)n, 0, 64, (hipStream_t)0));
-    TS_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t *)nullptr, (int32_t *)nullptr, (int)(n + 1), (hipStream_t)0));
-    L->tmp = o; L->tmp_bytes = a > b ? a : b; o = up256(o + L->tmp_bytes);
-    L->total = o;
+    W->key_in = c.take<uint64_t>(n);
+    W->key_out = c.take<uint64_t>(n);
+    W->val_in = c.take<int64_t>(n);
+    W->val_out = c.take<int64_t>(n);
+    W->head = c.take<int32_t>(n + 1);
+    W->before = c.take<int32_t>(n + 1);
+    W->first = c.take<int64_t>(n);
+    if (cv_sort_pairs_temp_bytes<uint64_t, int64_t>(n, &a) || cv_scan_temp_bytes<int32_t>(n + 1, &b)) return 1;
+    W->tmp_bytes = a > b ? a : b;
+    W->tmp = c.take_bytes(W->tmp_bytes);
     return 0;
 }
 
-int tokens_plan(int64_t nrows, size_t *start, size_t *tmp, size_t *tmp_bytes, size_t *total)
+struct tokens_ws {
+    int32_t *start;
+    void *tmp;
+    size_t tmp_bytes;
+};
+
+int tokens_plan(cv_carver &c, int64_t nrows, tokens_ws *W)
 {
     const size_t n = (size_t)(nrows > 0 ? nrows : 1);
-    size_t o = 0, a = 0;
-    *start = o; o = up256(o + n * 4);
-    TS_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, a, (const int32_t *)nullptr, (int32_t *)nullptr, (int)n, (hipStream_t)0));
-    *tmp = o; *tmp_bytes = a; o = up256(o + a);
-    *total = o;
+    W->start = c.take<int32_t>(n);
+    if (cv_inclusive_sum_temp_bytes<int32_t>(n, &W->tmp_bytes)) return 1;
+    W->tmp = c.take_bytes(W->tmp_bytes);
     return 0;
 }
 
@@ -253,9 +235,10 @@ extern "C" int cv_trainset_tokens_workspace(int64_t nrows, int64_t *bytes)
 {
     if (!bytes) { cv_set_error("cv_trainset_tokens_workspace: null argument"); return 1; }
     if (!rows_ok("cv_trainset_tokens_workspace", nrows)) return 1;
-    size_t s, t, tb, total;
-    if (tokens_plan(nrows, &s, &t, &tb, &total)) return 1;
-    *bytes = (int64_t)total;
+    cv_carver c;
+    tokens_ws W;
+    if (tokens_plan(c, nrows, &W)) return 1;
+    *bytes = (int64_t)c.total();
     return 0;
 }
 
@@ -269,25 +252,22 @@ extern "C" int cv_trainset_tokens(const char *text_dev, const int64_t *meta_dev,
         cv_set_error("cv_trainset_tokens: null argument");
         return 1;
     }
-    if (((uintptr_t)meta_dev & 7) || ((uintptr_t)index_dev & 7) || ((uintptr_t)pos_dev & 7) || ((uintptr_t)run_dev & 3) ||
-        ((uintptr_t)workspace_dev & 255)) {
-        cv_set_error("cv_trainset_tokens: meta / index / pos must be 8-byte, run 4-byte, the workspace 256-byte aligned");
+    if (((uintptr_t)meta_dev & 7) || ((uintptr_t)index_dev & 7) || ((uintptr_t)pos_dev & 7) || ((uintptr_t)run_dev & 3)) {
+        cv_set_error("cv_trainset_tokens: meta / index / pos must be 8-byte, run 4-byte aligned");
         return 1;
     }
-    size_t s, t, tb, total;
-    if (tokens_plan(nrows, &s, &t, &tb, &total)) return 1;
-    if (workspace_bytes < (int64_t)total) {
-        cv_set_error("cv_trainset_tokens: workspace holds %lld bytes, need %lld", (long long)workspace_bytes, (long long)total);
-        return 1;
-    }
+    cv_carver c(workspace_dev);
+    tokens_ws W;
+    if (tokens_plan(c, nrows, &W)) return 1;
+    if (!cv_workspace_ok("cv_trainset_tokens", workspace_dev, workspace_bytes, c.total())) return 1;
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace_dev;
-    int32_t *start = (int32_t *)(ws + s);
-    hipLaunchKernelGGL(ts_tokens, dim3(grid_for(nrows)), dim3(THREADS), 0, st, (const uint8_t *)text_dev, meta_dev, index_dev, nrows,
+    int32_t *start = W.start;
+    size_t tb = W.tmp_bytes;
+    hipLaunchKernelGGL(ts_tokens, dim3(cv_grid_for(nrows)), dim3(THREADS), 0, st, (const uint8_t *)text_dev, meta_dev, index_dev, nrows,
                        pos_dev, digits_dev, centre_dev, flags_dev, start);
-    TS_HIP(hipcub::DeviceScan::InclusiveSum(ws + t, tb, (const int32_t *)start, run_dev, (int)nrows, st));
-    hipLaunchKernelGGL(ts_run_index, dim3(grid_for(nrows)), dim3(THREADS), 0, st, run_dev, nrows);
-    TS_HIP(hipGetLastError());
+    CV_HIP(hipcub::DeviceScan::InclusiveSum(W.tmp, tb, (const int32_t *)start, run_dev, (int)nrows, st));
+    hipLaunchKernelGGL(ts_run_index, dim3(cv_grid_for(nrows)), dim3(THREADS), 0, st, run_dev, nrows);
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -307,10 +287,10 @@ extern "C" int cv_trainset_join(int64_t nrows, const int32_t *run_dev, const int
         return 1;
     }
     if (truth_off_dev && !truth_pos_dev) { cv_set_error("cv_trainset_join: truth_off_dev without truth_pos_dev"); return 1; }
-    hipLaunchKernelGGL(ts_join, dim3(grid_for(nrows)), dim3(THREADS), 0, (hipStream_t)stream, nrows, run_dev, run_ctg_dev, nruns,
+    hipLaunchKernelGGL(ts_join, dim3(cv_grid_for(nrows)), dim3(THREADS), 0, (hipStream_t)stream, nrows, run_dev, run_ctg_dev, nruns,
                        pos_dev, ntab, has_bed, bed_off_dev, bed_begin_dev, bed_emax_dev, truth_off_dev, truth_pos_dev, ctg_dev,
                        keep_dev, truth_dev);
-    TS_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -318,9 +298,10 @@ extern "C" int cv_trainset_finish_workspace(int64_t nrows, int64_t *bytes)
 {
     if (!bytes) { cv_set_error("cv_trainset_finish_workspace: null argument"); return 1; }
     if (!rows_ok("cv_trainset_finish_workspace", nrows)) return 1;
-    finish_layout L;
-    if (finish_plan(nrows, &L)) return 1;
-    *bytes = (int64_t)L.total;
+    cv_carver c;
+    finish_ws W;
+    if (finish_plan(c, nrows, &W)) return 1;
+    *bytes = (int64_t)c.total();
     return 0;
 }
 
@@ -335,7 +316,7 @@ extern "C" int cv_trainset_finish(int64_t nrows, const int32_t *ctg_dev, const i
     hipStream_t st = (hipStream_t)stream;
     if (nrows == 0) {
         hipLaunchKernelGGL(ts_zero_total, dim3(1), dim3(64), 0, st, total_dev);
-        TS_HIP(hipGetLastError());
+        CV_HIP(hipGetLastError());
         return 0;
     }
     if (!ctg_dev || !pos_dev || !digits_dev || !centre_dev || !keep_dev || !truth_dev || !rank_dev || !src_dev || !y_dev ||
@@ -343,33 +324,30 @@ extern "C" int cv_trainset_finish(int64_t nrows, const int32_t *ctg_dev, const i
         cv_set_error("cv_trainset_finish: null argument, or contig / truth counts out of range (1 .. %d contigs)", CV_TRAINSET_MAX_CONTIGS);
         return 1;
     }
-    if (((uintptr_t)pos_dev & 7) || ((uintptr_t)src_dev & 7) || ((uintptr_t)y_dev & 3) || ((uintptr_t)workspace_dev & 255)) {
-        cv_set_error("cv_trainset_finish: pos / src must be 8-byte, y 4-byte, the workspace 256-byte aligned");
+    if (((uintptr_t)pos_dev & 7) || ((uintptr_t)src_dev & 7) || ((uintptr_t)y_dev & 3)) {
+        cv_set_error("cv_trainset_finish: pos / src must be 8-byte, y 4-byte aligned");
         return 1;
     }
-    finish_layout L;
-    if (finish_plan(nrows, &L)) return 1;
-    if (workspace_bytes < (int64_t)L.total) {
-        cv_set_error("cv_trainset_finish: workspace holds %lld bytes, need %lld", (long long)workspace_bytes, (long long)L.total);
-        return 1;
-    }
-    char *ws = (char *)workspace_dev;
-    uint64_t *key_in = (uint64_t *)(ws + L.key_in), *key_out = (uint64_t *)(ws + L.key_out);
-    int64_t *val_in = (int64_t *)(ws + L.val_in), *val_out = (int64_t *)(ws + L.val_out), *first = (int64_t *)(ws + L.first);
-    int32_t *head = (int32_t *)(ws + L.head), *before = (int32_t *)(ws + L.before);
-    const int grid = grid_for(nrows + 1);
+    cv_carver c(workspace_dev);
+    finish_ws W;
+    if (finish_plan(c, nrows, &W)) return 1;
+    if (!cv_workspace_ok("cv_trainset_finish", workspace_dev, workspace_bytes, c.total())) return 1;
+    uint64_t *key_in = W.key_in, *key_out = W.key_out;
+    int64_t *val_in = W.val_in, *val_out = W.val_out, *first = W.first;
+    int32_t *head = W.head, *before = W.before;
+    const int grid = cv_grid_for(nrows + 1);
     hipLaunchKernelGGL(ts_keys, dim3(grid), dim3(THREADS), 0, st, nrows, ctg_dev, pos_dev, digits_dev, keep_dev, rank_dev, nctg, key_in, val_in);
-    size_t tb = L.tmp_bytes;
-    TS_HIP(hipcub::DeviceRadixSort::SortPairs(ws + L.tmp, tb, (const uint64_t *)key_in, key_out, (const int64_t *)val_in, val_out,
+    size_t tb = W.tmp_bytes;
+    CV_HIP(hipcub::DeviceRadixSort::SortPairs(W.tmp, tb, (const uint64_t *)key_in, key_out, (const int64_t *)val_in, val_out,
                                               (int)nrows, 0, 64, st));
     hipLaunchKernelGGL(ts_heads, dim3(grid), dim3(THREADS), 0, st, nrows, (const uint64_t *)key_out, head);
-    tb = L.tmp_bytes;
-    TS_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.tmp, tb, (const int32_t *)head, before, (int)(nrows + 1), st));
+    tb = W.tmp_bytes;
+    CV_HIP(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, (const int32_t *)head, before, (int)(nrows + 1), st));
     hipLaunchKernelGGL(ts_entries, dim3(grid), dim3(THREADS), 0, st, nrows, (const uint64_t *)key_out, (const int64_t *)val_out,
                        (const int32_t *)head, (const int32_t *)before, src_dev, first, total_dev);
-    hipLaunchKernelGGL(ts_labels, dim3(grid_for(nrows * 16)), dim3(THREADS), 0, st, (const int32_t *)before, nrows,
+    hipLaunchKernelGGL(ts_labels, dim3(cv_grid_for(nrows * 16)), dim3(THREADS), 0, st, (const int32_t *)before, nrows,
                        (const int64_t *)src_dev, (const int64_t *)first, truth_dev, centre_dev, labels_dev, ntruth, y_dev);
-    TS_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -384,8 +362,8 @@ extern "C" int cv_trainset_gather(const float *x_all_dev, const float *y_dev, co
         cv_set_error("cv_trainset_gather: the tensors must be 16-byte, the index lists 8-byte aligned");
         return 1;
     }
-    hipLaunchKernelGGL(ts_gather, dim3(grid_for(total * (NV / 4 + 4))), dim3(THREADS), 0, (hipStream_t)stream, (const float4 *)x_all_dev,
+    hipLaunchKernelGGL(ts_gather, dim3(cv_grid_for(total * (NV / 4 + 4))), dim3(THREADS), 0, (hipStream_t)stream, (const float4 *)x_all_dev,
                        (const float4 *)y_dev, src_dev, perm_dev, total, (float4 *)x_out_dev, (float4 *)y_out_dev);
-    TS_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }

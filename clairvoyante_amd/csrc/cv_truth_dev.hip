@@ -6,7 +6,8 @@
 //   per slab (cv_truth_lines_dev):
 //   newline index       cv_text_line_index of cv_textparse.hip
 //   tl_verdicts         one thread per line: the core's status and the contig token's span
-//   tl_flags            "this ROW's contig token differs byte for byte from the line before" (or that line is no ROW)
+//   run-start flags     cv_text_run_flags of cv_textparse.hip: "this ROW's contig token differs byte for byte from the line
+//                       before" (or that line is no ROW)
 //   hipcub ExclusiveSum over the ROW flags and over the run-start flags -> row index, run index
 //   tl_rows             the core again for the ROW lines: fields at their row index, run-start token spans at their run index,
 //                       the counters
@@ -18,7 +19,7 @@
 //
 //   once over the truth rows of all slabs (cv_truth_tables_dev):
 //   one stable sort by (contig id, position); the tail of each run of equal keys is the dict's "last row wins"; the BED
-//   verdict as ts_join of cv_trainset.hip computes it; hipcub ExclusiveSum over "tail" and over "tail and kept";
+//   verdict is cvb::stab, as in ts_join of cv_trainset.hip; hipcub ExclusiveSum over "tail" and over "tail and kept";
 //   the offsets per contig from a lower bound on the sorted keys.
 //
 // Integer and byte kernels; every output slot has exactly one writer and the counters are integer sums, so no result
@@ -29,28 +30,15 @@
 #include <string.h>
 #include "../../include/clairvoyante_amd.h"
 #include "cv_internal.hpp"
+#include "cv_dev_scan.hpp"
+#include "cv_beditems_core.hpp"
 #include "cv_truth_core.hpp"
-
-#define TT_HIP(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) {                                                                        \
-            cv_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-            return 1;                                                                                  \
-        }                                                                                              \
-    } while (0)
 
 namespace {
 
 constexpr int THREADS = 256;
-constexpr int MAX_GRID = 4096;
 constexpr int POS_BITS = 40;                                  // a canonical coordinate has 12 digits at most: < 2^40
 constexpr int END_BITS = 41;                                  // end + 1 of a BED interval: 0 .. 10^12
-
-inline int grid_for(int64_t n) { const int64_t b = (n + THREADS - 1) / THREADS; return (int)(b < 1 ? 1 : b < MAX_GRID ? b : MAX_GRID); }
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-#define GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
 // ---- the line pass ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void tl_verdicts(const uint8_t *text, const int64_t *line_end, const int64_t *index_info,
@@ -58,7 +46,7 @@ __global__ __launch_bounds__(THREADS) void tl_verdicts(const uint8_t *text, cons
                                                        int32_t *isrow, int64_t *info)
 {
     const int64_t lines = index_info[1];
-    GRID_STRIDE(i, max_lines + 1) {
+    CV_GRID_STRIDE(i, max_lines + 1) {
         int row = 0;
         if (i < lines) {
             const int64_t start = i ? line_end[i - 1] + 1 : 0;
@@ -74,27 +62,13 @@ __global__ __launch_bounds__(THREADS) void tl_verdicts(const uint8_t *text, cons
     }
 }
 
-__global__ __launch_bounds__(THREADS) void tl_flags(const uint8_t *text, const int64_t *span, const int32_t *isrow, int64_t max_lines,
-                                                    int32_t *flag)
-{
-    GRID_STRIDE(i, max_lines + 1) {
-        int f = 0;
-        if (i < max_lines && isrow[i]) {
-            f = i == 0 || !isrow[i - 1] || span[2 * i + 1] != span[2 * i - 1];
-            const uint8_t *a = text + span[2 * i], *b = f ? a : text + span[2 * i - 2];
-            for (int64_t k = 0; !f && k < span[2 * i + 1]; ++k) f = a[k] != b[k];
-        }
-        flag[i] = f;
-    }
-}
-
 __global__ __launch_bounds__(THREADS) void tl_rows(const uint8_t *text, const int64_t *line_end, const int64_t *index_info,
                                                    int64_t max_lines, int format, const cvt::Filter filter, const int32_t *isrow, const int32_t *rowidx,
                                                    const int32_t *flag, const int32_t *runidx, const int64_t *span, int64_t *pos,
                                                    int64_t *end, float *label, int32_t *run, int64_t *tok, int64_t *info)
 {
     const int64_t lines = index_info[1];
-    GRID_STRIDE(i, lines) {
+    CV_GRID_STRIDE(i, lines) {
         if (!isrow[i]) continue;
         const int64_t start = i ? line_end[i - 1] + 1 : 0;
         cvt::Line L;
@@ -115,26 +89,30 @@ __global__ __launch_bounds__(THREADS) void tl_rows(const uint8_t *text, const in
     }
 }
 
-struct lines_layout {
-    size_t index, index_info, status, span, isrow, rowidx, flag, runidx, tmp, tmp_bytes, total;
+struct lines_ws {
+    void *index;
+    int64_t *index_info, *span;
+    uint8_t *status;
+    int32_t *isrow, *rowidx, *flag, *runidx;
+    void *tmp;
+    size_t tmp_bytes;
 };
 
-int lines_plan(int64_t len, int64_t max_lines, lines_layout *L)
+int lines_plan(cv_carver &c, int64_t len, int64_t max_lines, lines_ws *W)
 {
     const size_t n = (size_t)max_lines + 1;
-    size_t o = 0, ib = 0, sb = 0;
+    size_t ib = 0;
     if (cv_text_line_index_bytes(len, max_lines, &ib)) return 1;
-    L->index = o; o = up256(o + ib);
-    L->index_info = o; o = up256(o + 4 * 8);
-    L->status = o; o = up256(o + n);
-    L->span = o; o = up256(o + n * 16);
-    L->isrow = o; o = up256(o + n * 4);
-    L->rowidx = o; o = up256(o + n * 4);
-    L->flag = o; o = up256(o + n * 4);
-    L->runidx = o; o = up256(o + n * 4);
-    TT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, (const int32_t *)nullptr, (int32_t *)nullptr, (int)n, (hipStream_t)0));
-    L->tmp = o; L->tmp_bytes = sb; o = up256(o + sb);
-    L->total = o;
+    W->index = c.take_bytes(ib);
+    W->index_info = c.take<int64_t>(4);
+    W->status = c.take<uint8_t>(n);
+    W->span = c.take<int64_t>(2 * n);
+    W->isrow = c.take<int32_t>(n);
+    W->rowidx = c.take<int32_t>(n);
+    W->flag = c.take<int32_t>(n);
+    W->runidx = c.take<int32_t>(n);
+    if (cv_scan_temp_bytes<int32_t>(n, &W->tmp_bytes)) return 1;
+    W->tmp = c.take_bytes(W->tmp_bytes);
     return 0;
 }
 
@@ -172,43 +150,21 @@ __device__ __forceinline__ uint64_t ctg_of(const int32_t *run, const int32_t *ru
     return (uint64_t)(c >= 0 && c < CV_TRAINSET_MAX_CONTIGS ? c : 0);
 }
 
-// first slot of the sorted a[0, n) whose value is >= v
-__device__ __forceinline__ int64_t lower_bound(const uint64_t *a, int64_t n, uint64_t v)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// number of elements of the sorted a[0, n) that are <= v
-__device__ __forceinline__ int64_t upper_bound(const int64_t *a, int64_t n, int64_t v)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a[mid] <= v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(THREADS) void bt_end_keys(int64_t n, const int64_t *end, uint64_t *key, int64_t *val)
 {
-    GRID_STRIDE(i, n) { key[i] = (uint64_t)(end[i] + 1); val[i] = i; }
+    CV_GRID_STRIDE(i, n) { key[i] = (uint64_t)(end[i] + 1); val[i] = i; }
 }
 
 __global__ __launch_bounds__(THREADS) void bt_begin_keys(int64_t n, const int64_t *by_end, const int64_t *begin, const int32_t *run,
                                                          const int32_t *run_ctg, int64_t nruns, uint64_t *key)
 {
-    GRID_STRIDE(j, n) { const int64_t i = by_end[j]; key[j] = ctg_of(run, run_ctg, nruns, i) << POS_BITS | (uint64_t)begin[i]; }
+    CV_GRID_STRIDE(j, n) { const int64_t i = by_end[j]; key[j] = ctg_of(run, run_ctg, nruns, i) << POS_BITS | (uint64_t)begin[i]; }
 }
 
 __global__ __launch_bounds__(THREADS) void bt_gather(int64_t n, const uint64_t *key, const int64_t *order, const int64_t *end,
                                                      int64_t *bed_begin, uint64_t *packed)
 {
-    GRID_STRIDE(j, n) {
+    CV_GRID_STRIDE(j, n) {
         bed_begin[j] = (int64_t)(key[j] & (((uint64_t)1 << POS_BITS) - 1));
         packed[j] = (key[j] >> POS_BITS) << END_BITS | (uint64_t)(end[order[j]] + 1);
     }
@@ -217,49 +173,51 @@ __global__ __launch_bounds__(THREADS) void bt_gather(int64_t n, const uint64_t *
 __global__ __launch_bounds__(THREADS) void bt_finish(int64_t n, const uint64_t *key, const uint64_t *packed_max, int32_t nctg,
                                                      int64_t *bed_emax, int64_t *bed_off)
 {
-    GRID_STRIDE(j, n) bed_emax[j] = (int64_t)(packed_max[j] & (((uint64_t)1 << END_BITS) - 1)) - 1;
-    GRID_STRIDE(c, (int64_t)nctg + 1) bed_off[c] = c == nctg ? n : lower_bound(key, n, (uint64_t)c << POS_BITS);
+    CV_GRID_STRIDE(j, n) bed_emax[j] = (int64_t)(packed_max[j] & (((uint64_t)1 << END_BITS) - 1)) - 1;
+    CV_GRID_STRIDE(c, (int64_t)nctg + 1) bed_off[c] = c == nctg ? n : cvb::lower_bound(key, n, (uint64_t)c << POS_BITS);
 }
 
-struct bed_layout { size_t key_a, key_b, val_a, val_b, tmp, tmp_bytes, total; };
+struct bed_ws {
+    uint64_t *key_a, *key_b;
+    int64_t *val_a, *val_b;
+    void *tmp;
+    size_t tmp_bytes;
+};
 
-int bed_plan(int64_t n, bed_layout *L)
+int bed_plan(cv_carver &c, int64_t n, bed_ws *W)
 {
     const size_t m = (size_t)(n > 0 ? n : 1);
-    size_t o = 0, a = 0, b = 0;
-    L->key_a = o; o = up256(o + m * 8);
-    L->key_b = o; o = up256(o + m * 8);
-    L->val_a = o; o = up256(o + m * 8);
-    L->val_b = o; o = up256(o + m * 8);
-    TT_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, a, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const int64_t *)nullptr,
-                                              (int64_t *)nullptr, (int)m, 0, 64, (hipStream_t)0));
-    TT_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, b, (const uint64_t *)nullptr, (uint64_t *)nullptr, hipcub::Max(), (int)m, (hipStream_t)0));
-    L->tmp = o; L->tmp_bytes = a > b ? a : b; o = up256(o + L->tmp_bytes);
-    L->total = o;
+    size_t a = 0, b = 0;
+    W->key_a = c.take<uint64_t>(m);
+    W->key_b = c.take<uint64_t>(m);
+    W->val_a = c.take<int64_t>(m);
+    W->val_b = c.take<int64_t>(m);
+    if (cv_sort_pairs_temp_bytes<uint64_t, int64_t>(m, &a) || cv_max_scan_temp_bytes<uint64_t>(m, &b)) return 1;
+    W->tmp_bytes = a > b ? a : b;
+    W->tmp = c.take_bytes(W->tmp_bytes);
     return 0;
 }
 
 __global__ __launch_bounds__(THREADS) void tt_keys(int64_t n, const int64_t *pos, const int32_t *run, const int32_t *run_ctg,
                                                    int64_t nruns, uint64_t *key, int64_t *val)
 {
-    GRID_STRIDE(i, n) { key[i] = ctg_of(run, run_ctg, nruns, i) << POS_BITS | (uint64_t)pos[i]; val[i] = i; }
+    CV_GRID_STRIDE(i, n) { key[i] = ctg_of(run, run_ctg, nruns, i) << POS_BITS | (uint64_t)pos[i]; val[i] = i; }
 }
 
 __global__ __launch_bounds__(THREADS) void tt_tails(int64_t n, const uint64_t *key, int32_t nctg, int has_bed, const int64_t *bed_off,
                                                     const int64_t *bed_begin, const int64_t *bed_emax, int32_t *every, int32_t *kept)
 {
-    GRID_STRIDE(j, n + 1) {
+    CV_GRID_STRIDE(j, n + 1) {
         int tail = 0, kp = 0;
         if (j < n && (j + 1 == n || key[j + 1] != key[j])) {
             tail = 1;
             kp = 1;
-            if (has_bed) {                                       // _Intervals.hit, as ts_join of cv_trainset.hip
+            if (has_bed) {                                       // _Intervals.hit
                 const int64_t c = (int64_t)(key[j] >> POS_BITS), p = (int64_t)(key[j] & (((uint64_t)1 << POS_BITS) - 1));
                 kp = 0;
                 if (c < nctg) {
                     const int64_t lo = bed_off[c], m = bed_off[c + 1] - lo;
-                    const int64_t u = upper_bound(bed_begin + lo, m, p);
-                    kp = u > 0 && bed_emax[lo + u - 1] > p;
+                    kp = cvb::stab(bed_begin + lo, bed_emax + lo, m, p);
                 }
             }
         }
@@ -273,7 +231,7 @@ __global__ __launch_bounds__(THREADS) void tt_emit(int64_t n, const uint64_t *ke
                                                    const float4 *label, int32_t nctg, int64_t *truth_off, int64_t *truth_pos,
                                                    float4 *labels_out, int64_t *every_off, int64_t *every_pos, int64_t *counts)
 {
-    GRID_STRIDE(j, n) {
+    CV_GRID_STRIDE(j, n) {
         if (!every[j]) continue;
         const int64_t p = (int64_t)(key[j] & (((uint64_t)1 << POS_BITS) - 1));
         every_pos[every_at[j]] = p;
@@ -283,33 +241,37 @@ __global__ __launch_bounds__(THREADS) void tt_emit(int64_t n, const uint64_t *ke
             for (int q = 0; q < 4; ++q) labels_out[t * 4 + q] = label[i * 4 + q];
         }
     }
-    GRID_STRIDE(c, (int64_t)nctg + 1) {
-        const int64_t lb = c == nctg ? n : lower_bound(key, n, (uint64_t)c << POS_BITS);
+    CV_GRID_STRIDE(c, (int64_t)nctg + 1) {
+        const int64_t lb = c == nctg ? n : cvb::lower_bound(key, n, (uint64_t)c << POS_BITS);
         truth_off[c] = kept_at[lb];
         every_off[c] = every_at[lb];
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) { counts[0] = kept_at[n]; counts[1] = every_at[n]; }
 }
 
-struct tables_layout { size_t key_a, key_b, val_a, val_b, every, every_at, kept, kept_at, tmp, tmp_bytes, total; };
+struct tables_ws {
+    uint64_t *key_a, *key_b;
+    int64_t *val_a, *val_b;
+    int32_t *every, *every_at, *kept, *kept_at;
+    void *tmp;
+    size_t tmp_bytes;
+};
 
-int tables_plan(int64_t n, tables_layout *L)
+int tables_plan(cv_carver &c, int64_t n, tables_ws *W)
 {
     const size_t m = (size_t)(n > 0 ? n : 1);
-    size_t o = 0, a = 0, b = 0;
-    L->key_a = o; o = up256(o + m * 8);
-    L->key_b = o; o = up256(o + m * 8);
-    L->val_a = o; o = up256(o + m * 8);
-    L->val_b = o; o = up256(o + m * 8);
-    L->every = o; o = up256(o + (m + 1) * 4);
-    L->every_at = o; o = up256(o + (m + 1) * 4);
-    L->kept = o; o = up256(o + (m + 1) * 4);
-    L->kept_at = o; o = up256(o + (m + 1) * 4);
-    TT_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, a, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const int64_t *)nullptr,
-                                              (int64_t *)nullptr, (int)m, 0, 64, (hipStream_t)0));
-    TT_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t *)nullptr, (int32_t *)nullptr, (int)(m + 1), (hipStream_t)0));
-    L->tmp = o; L->tmp_bytes = a > b ? a : b; o = up256(o + L->tmp_bytes);
-    L->total = o;
+    size_t a = 0, b = 0;
+    W->key_a = c.take<uint64_t>(m);
+    W->key_b = c.take<uint64_t>(m);
+    W->val_a = c.take<int64_t>(m);
+    W->val_b = c.take<int64_t>(m);
+    W->every = c.take<int32_t>(m + 1);
+    W->every_at = c.take<int32_t>(m + 1);
+    W->kept = c.take<int32_t>(m + 1);
+    W->kept_at = c.take<int32_t>(m + 1);
+    if (cv_sort_pairs_temp_bytes<uint64_t, int64_t>(m, &a) || cv_scan_temp_bytes<int32_t>(m + 1, &b)) return 1;
+    W->tmp_bytes = a > b ? a : b;
+    W->tmp = c.take_bytes(W->tmp_bytes);
     return 0;
 }
 
@@ -329,9 +291,10 @@ extern "C" int cv_truth_lines_workspace(int64_t len, int64_t max_lines, int64_t 
 {
     if (!bytes) { cv_set_error("cv_truth_lines_workspace: null argument"); return 1; }
     if (!lines_args_ok("cv_truth_lines_workspace", len, CV_TRUTH_FORMAT_VAR, max_lines)) return 1;
-    lines_layout L;
-    if (lines_plan(len, max_lines, &L)) return 1;
-    *bytes = (int64_t)L.total;
+    cv_carver c;
+    lines_ws W;
+    if (lines_plan(c, len, max_lines, &W)) return 1;
+    *bytes = (int64_t)c.total();
     return 0;
 }
 
@@ -349,38 +312,31 @@ extern "C" int cv_truth_lines_dev(const char *text_dev, int64_t len, int format,
         return 1;
     }
     if (((uintptr_t)pos_dev & 7) || ((uintptr_t)end_dev & 7) || ((uintptr_t)label_dev & 3) || ((uintptr_t)run_dev & 3) ||
-        ((uintptr_t)tok_dev & 7) || ((uintptr_t)info_dev & 7) || ((uintptr_t)workspace_dev & 255)) {
-        cv_set_error("cv_truth_lines_dev: pos / end / tok / info must be 8-byte, label / run 4-byte, the workspace 256-byte aligned");
+        ((uintptr_t)tok_dev & 7) || ((uintptr_t)info_dev & 7)) {
+        cv_set_error("cv_truth_lines_dev: pos / end / tok / info must be 8-byte, label / run 4-byte aligned");
         return 1;
     }
-    lines_layout L;
-    if (lines_plan(len, max_lines, &L)) return 1;
-    if (workspace_bytes < (int64_t)L.total) {
-        cv_set_error("cv_truth_lines_dev: workspace holds %lld bytes, need %lld", (long long)workspace_bytes, (long long)L.total);
-        return 1;
-    }
+    cv_carver c(workspace_dev);
+    lines_ws W;
+    if (lines_plan(c, len, max_lines, &W)) return 1;
+    if (!cv_workspace_ok("cv_truth_lines_dev", workspace_dev, workspace_bytes, c.total())) return 1;
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace_dev;
-    int64_t *index_info = (int64_t *)(ws + L.index_info), *span = (int64_t *)(ws + L.span);
-    uint8_t *status = (uint8_t *)(ws + L.status);
-    int32_t *isrow = (int32_t *)(ws + L.isrow), *rowidx = (int32_t *)(ws + L.rowidx), *flag = (int32_t *)(ws + L.flag),
-            *runidx = (int32_t *)(ws + L.runidx);
     const int64_t *line_end = nullptr;
-    TT_HIP(hipMemsetAsync(info_dev, 0, 8 * sizeof(int64_t), st));
-    if (cv_text_line_index(text_dev, len, max_lines, ws + L.index, index_info, &line_end, st)) return 1;
+    CV_HIP(hipMemsetAsync(info_dev, 0, 8 * sizeof(int64_t), st));
+    if (cv_text_line_index(text_dev, len, max_lines, W.index, W.index_info, &line_end, st)) return 1;
     const uint8_t *text = (const uint8_t *)text_dev;
-    const int grid = grid_for(max_lines + 1);
-    hipLaunchKernelGGL(tl_verdicts, dim3(grid), dim3(THREADS), 0, st, text, line_end, (const int64_t *)index_info, max_lines, format,
-                       filter, status, span, isrow, info_dev);
-    hipLaunchKernelGGL(tl_flags, dim3(grid), dim3(THREADS), 0, st, text, (const int64_t *)span, (const int32_t *)isrow, max_lines, flag);
-    size_t tb = L.tmp_bytes;
-    TT_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.tmp, tb, (const int32_t *)isrow, rowidx, (int)(max_lines + 1), st));
-    tb = L.tmp_bytes;
-    TT_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.tmp, tb, (const int32_t *)flag, runidx, (int)(max_lines + 1), st));
-    hipLaunchKernelGGL(tl_rows, dim3(grid), dim3(THREADS), 0, st, text, line_end, (const int64_t *)index_info, max_lines, format,
-                       filter, (const int32_t *)isrow, (const int32_t *)rowidx, (const int32_t *)flag, (const int32_t *)runidx,
-                       (const int64_t *)span, pos_dev, end_dev, label_dev, run_dev, tok_dev, info_dev);
-    TT_HIP(hipGetLastError());
+    const int grid = cv_grid_for(max_lines + 1);
+    hipLaunchKernelGGL(tl_verdicts, dim3(grid), dim3(THREADS), 0, st, text, line_end, (const int64_t *)W.index_info, max_lines, format,
+                       filter, W.status, W.span, W.isrow, info_dev);
+    cv_text_run_flags(text, W.span, W.isrow, max_lines, W.flag, st);
+    size_t tb = W.tmp_bytes;
+    CV_HIP(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, (const int32_t *)W.isrow, W.rowidx, (int)(max_lines + 1), st));
+    tb = W.tmp_bytes;
+    CV_HIP(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, (const int32_t *)W.flag, W.runidx, (int)(max_lines + 1), st));
+    hipLaunchKernelGGL(tl_rows, dim3(grid), dim3(THREADS), 0, st, text, line_end, (const int64_t *)W.index_info, max_lines, format,
+                       filter, (const int32_t *)W.isrow, (const int32_t *)W.rowidx, (const int32_t *)W.flag, (const int32_t *)W.runidx,
+                       (const int64_t *)W.span, pos_dev, end_dev, label_dev, run_dev, tok_dev, info_dev);
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -408,9 +364,10 @@ extern "C" int cv_bed_table_workspace(int64_t n, int64_t *bytes)
 {
     if (!bytes) { cv_set_error("cv_bed_table_workspace: null argument"); return 1; }
     if (!table_args_ok("cv_bed_table_workspace", n, 0, 1)) return 1;
-    bed_layout L;
-    if (bed_plan(n, &L)) return 1;
-    *bytes = (int64_t)L.total;
+    cv_carver c;
+    bed_ws W;
+    if (bed_plan(c, n, &W)) return 1;
+    *bytes = (int64_t)c.total();
     return 0;
 }
 
@@ -424,40 +381,37 @@ extern "C" int cv_bed_table_dev(int64_t n, const int64_t *begin_dev, const int64
         return 1;
     }
     if (((uintptr_t)begin_dev & 7) || ((uintptr_t)end_dev & 7) || ((uintptr_t)run_dev & 3) || ((uintptr_t)run_ctg_dev & 3) ||
-        ((uintptr_t)bed_off_dev & 7) || ((uintptr_t)bed_begin_dev & 7) || ((uintptr_t)bed_emax_dev & 7) || ((uintptr_t)workspace_dev & 255)) {
-        cv_set_error("cv_bed_table_dev: the int64 arrays must be 8-byte, run / run_ctg 4-byte, the workspace 256-byte aligned");
+        ((uintptr_t)bed_off_dev & 7) || ((uintptr_t)bed_begin_dev & 7) || ((uintptr_t)bed_emax_dev & 7)) {
+        cv_set_error("cv_bed_table_dev: the int64 arrays must be 8-byte, run / run_ctg 4-byte aligned");
         return 1;
     }
-    bed_layout L;
-    if (bed_plan(n, &L)) return 1;
-    if (workspace_bytes < (int64_t)L.total) {
-        cv_set_error("cv_bed_table_dev: workspace holds %lld bytes, need %lld", (long long)workspace_bytes, (long long)L.total);
-        return 1;
-    }
+    cv_carver c(workspace_dev);
+    bed_ws W;
+    if (bed_plan(c, n, &W)) return 1;
+    if (!cv_workspace_ok("cv_bed_table_dev", workspace_dev, workspace_bytes, c.total())) return 1;
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace_dev;
-    uint64_t *key_a = (uint64_t *)(ws + L.key_a), *key_b = (uint64_t *)(ws + L.key_b);
-    int64_t *val_a = (int64_t *)(ws + L.val_a), *val_b = (int64_t *)(ws + L.val_b);
-    const int grid = grid_for(n > nctg ? n : nctg + 1);
+    uint64_t *key_a = W.key_a, *key_b = W.key_b;
+    int64_t *val_a = W.val_a, *val_b = W.val_b;
+    const int grid = cv_grid_for(n > nctg ? n : nctg + 1);
     if (n > 0) {
         hipLaunchKernelGGL(bt_end_keys, dim3(grid), dim3(THREADS), 0, st, n, end_dev, key_a, val_a);
-        size_t tb = L.tmp_bytes;
-        TT_HIP(hipcub::DeviceRadixSort::SortPairs(ws + L.tmp, tb, (const uint64_t *)key_a, key_b, (const int64_t *)val_a, val_b, (int)n, 0,
+        size_t tb = W.tmp_bytes;
+        CV_HIP(hipcub::DeviceRadixSort::SortPairs(W.tmp, tb, (const uint64_t *)key_a, key_b, (const int64_t *)val_a, val_b, (int)n, 0,
                                                   END_BITS, st));
         hipLaunchKernelGGL(bt_begin_keys, dim3(grid), dim3(THREADS), 0, st, n, (const int64_t *)val_b, begin_dev, run_dev, run_ctg_dev,
                            nruns, key_a);
-        tb = L.tmp_bytes;
-        TT_HIP(hipcub::DeviceRadixSort::SortPairs(ws + L.tmp, tb, (const uint64_t *)key_a, key_b, (const int64_t *)val_b, val_a, (int)n, 0,
+        tb = W.tmp_bytes;
+        CV_HIP(hipcub::DeviceRadixSort::SortPairs(W.tmp, tb, (const uint64_t *)key_a, key_b, (const int64_t *)val_b, val_a, (int)n, 0,
                                                   POS_BITS + 16, st));
         // key_b: (contig, begin) ascending, val_a: the interval at each slot; key_a <- contig << 41 | end + 1, then its running maximum
         hipLaunchKernelGGL(bt_gather, dim3(grid), dim3(THREADS), 0, st, n, (const uint64_t *)key_b, (const int64_t *)val_a, end_dev,
                            bed_begin_dev, key_a);
-        tb = L.tmp_bytes;
-        TT_HIP(hipcub::DeviceScan::InclusiveScan(ws + L.tmp, tb, (const uint64_t *)key_a, (uint64_t *)val_b, hipcub::Max(), (int)n, st));
+        tb = W.tmp_bytes;
+        CV_HIP(hipcub::DeviceScan::InclusiveScan(W.tmp, tb, (const uint64_t *)key_a, (uint64_t *)val_b, hipcub::Max(), (int)n, st));
     }
     hipLaunchKernelGGL(bt_finish, dim3(grid), dim3(THREADS), 0, st, n, (const uint64_t *)key_b, (const uint64_t *)val_b, nctg,
                        bed_emax_dev, bed_off_dev);
-    TT_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
@@ -465,9 +419,10 @@ extern "C" int cv_truth_tables_workspace(int64_t n, int64_t *bytes)
 {
     if (!bytes) { cv_set_error("cv_truth_tables_workspace: null argument"); return 1; }
     if (!table_args_ok("cv_truth_tables_workspace", n, 0, 1)) return 1;
-    tables_layout L;
-    if (tables_plan(n, &L)) return 1;
-    *bytes = (int64_t)L.total;
+    cv_carver c;
+    tables_ws W;
+    if (tables_plan(c, n, &W)) return 1;
+    *bytes = (int64_t)c.total();
     return 0;
 }
 
@@ -487,40 +442,35 @@ extern "C" int cv_truth_tables_dev(int64_t n, const int64_t *pos_dev, const floa
     if (((uintptr_t)pos_dev & 7) || ((uintptr_t)label_dev & 15) || ((uintptr_t)run_dev & 3) || ((uintptr_t)run_ctg_dev & 3) ||
         ((uintptr_t)bed_off_dev & 7) || ((uintptr_t)bed_begin_dev & 7) || ((uintptr_t)bed_emax_dev & 7) || ((uintptr_t)truth_off_dev & 7) ||
         ((uintptr_t)truth_pos_dev & 7) || ((uintptr_t)labels_dev & 15) || ((uintptr_t)every_off_dev & 7) || ((uintptr_t)every_pos_dev & 7) ||
-        ((uintptr_t)counts_dev & 7) || ((uintptr_t)workspace_dev & 255)) {
-        cv_set_error("cv_truth_tables_dev: the int64 arrays must be 8-byte, the labels 16-byte, run / run_ctg 4-byte, the workspace "
-                     "256-byte aligned");
+        ((uintptr_t)counts_dev & 7)) {
+        cv_set_error("cv_truth_tables_dev: the int64 arrays must be 8-byte, the labels 16-byte, run / run_ctg 4-byte aligned");
         return 1;
     }
-    tables_layout L;
-    if (tables_plan(n, &L)) return 1;
-    if (workspace_bytes < (int64_t)L.total) {
-        cv_set_error("cv_truth_tables_dev: workspace holds %lld bytes, need %lld", (long long)workspace_bytes, (long long)L.total);
-        return 1;
-    }
+    cv_carver c(workspace_dev);
+    tables_ws W;
+    if (tables_plan(c, n, &W)) return 1;
+    if (!cv_workspace_ok("cv_truth_tables_dev", workspace_dev, workspace_bytes, c.total())) return 1;
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace_dev;
-    uint64_t *key_a = (uint64_t *)(ws + L.key_a), *key_b = (uint64_t *)(ws + L.key_b);
-    int64_t *val_a = (int64_t *)(ws + L.val_a), *val_b = (int64_t *)(ws + L.val_b);
-    int32_t *every = (int32_t *)(ws + L.every), *every_at = (int32_t *)(ws + L.every_at), *kept = (int32_t *)(ws + L.kept),
-            *kept_at = (int32_t *)(ws + L.kept_at);
-    const int grid = grid_for(n > nctg ? n + 1 : nctg + 1);
+    uint64_t *key_a = W.key_a, *key_b = W.key_b;
+    int64_t *val_a = W.val_a, *val_b = W.val_b;
+    int32_t *every = W.every, *every_at = W.every_at, *kept = W.kept, *kept_at = W.kept_at;
+    const int grid = cv_grid_for(n > nctg ? n + 1 : nctg + 1);
     if (n > 0) {
         hipLaunchKernelGGL(tt_keys, dim3(grid), dim3(THREADS), 0, st, n, pos_dev, run_dev, run_ctg_dev, nruns, key_a, val_a);
-        size_t tb = L.tmp_bytes;
-        TT_HIP(hipcub::DeviceRadixSort::SortPairs(ws + L.tmp, tb, (const uint64_t *)key_a, key_b, (const int64_t *)val_a, val_b, (int)n, 0,
+        size_t tb = W.tmp_bytes;
+        CV_HIP(hipcub::DeviceRadixSort::SortPairs(W.tmp, tb, (const uint64_t *)key_a, key_b, (const int64_t *)val_a, val_b, (int)n, 0,
                                                   POS_BITS + 16, st));
     }
     hipLaunchKernelGGL(tt_tails, dim3(grid), dim3(THREADS), 0, st, n, (const uint64_t *)key_b, nctg, has_bed, bed_off_dev, bed_begin_dev,
                        bed_emax_dev, every, kept);
-    size_t tb = L.tmp_bytes;
-    TT_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.tmp, tb, (const int32_t *)every, every_at, (int)(n + 1), st));
-    tb = L.tmp_bytes;
-    TT_HIP(hipcub::DeviceScan::ExclusiveSum(ws + L.tmp, tb, (const int32_t *)kept, kept_at, (int)(n + 1), st));
+    size_t tb = W.tmp_bytes;
+    CV_HIP(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, (const int32_t *)every, every_at, (int)(n + 1), st));
+    tb = W.tmp_bytes;
+    CV_HIP(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, (const int32_t *)kept, kept_at, (int)(n + 1), st));
     hipLaunchKernelGGL(tt_emit, dim3(grid), dim3(THREADS), 0, st, n, (const uint64_t *)key_b, (const int64_t *)val_b,
                        (const int32_t *)every, (const int32_t *)every_at, (const int32_t *)kept, (const int32_t *)kept_at,
                        (const float4 *)label_dev, nctg, truth_off_dev, truth_pos_dev, (float4 *)labels_dev, every_off_dev, every_pos_dev,
                        counts_dev);
-    TT_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }

@@ -14,18 +14,9 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include "../../include/clairvoyante_amd.h"
+#include "cv_dev_scan.hpp"
 #include "cv_vcf_core.hpp"
 
-void cv_set_error(const char *fmt, ...);
-
-#define VCF_HIP(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) {                                                                        \
-            cv_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-            return 1;                                                                                  \
-        }                                                                                              \
-    } while (0)
 
 static_assert(CV_VCF_NONE == cvv::NONE && CV_VCF_DEVICE == cvv::DEVICE && CV_VCF_HOST == cvv::HOST, "the header's status words");
 
@@ -82,14 +73,18 @@ __global__ __launch_bounds__(THREADS) void vcf_write(Batch b, int64_t n, const i
     cvv::record(cand_of(b, i), s, &why);
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+// the workspace: the record lengths (n + 1 int64) | hipcub's
+struct records_ws {
+    int64_t *len;
+    void *tmp;
+    size_t tmp_bytes;
+};
 
-int plan(int64_t n, size_t *tmp, size_t *tmp_bytes, size_t *total)
+int plan(cv_carver &c, int64_t n, records_ws *W)
 {
-    size_t o = up256((size_t)(n + 1) * 8), a = 0;
-    VCF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, a, (const int64_t *)nullptr, (int64_t *)nullptr, (int)(n + 1), (hipStream_t)0));
-    *tmp = o; *tmp_bytes = a;
-    *total = up256(o + a);
+    W->len = c.take<int64_t>((size_t)(n + 1));
+    if (cv_scan_temp_bytes<int64_t>(n + 1, &W->tmp_bytes)) return 1;
+    W->tmp = c.take_bytes(W->tmp_bytes);
     return 0;
 }
 
@@ -123,9 +118,10 @@ extern "C" int cv_vcf_records_workspace(int64_t n, int64_t *bytes)
 {
     if (!bytes) { cv_set_error("cv_vcf_records_workspace: null argument"); return 1; }
     if (!n_ok("cv_vcf_records_workspace", n)) return 1;
-    size_t t, tb, total;
-    if (plan(n, &t, &tb, &total)) return 1;
-    *bytes = (int64_t)total;
+    cv_carver c;
+    records_ws W;
+    if (plan(c, n, &W)) return 1;
+    *bytes = (int64_t)c.total();
     return 0;
 }
 
@@ -139,24 +135,21 @@ extern "C" int cv_vcf_records_dev(const int32_t *call_dev, const float *qual_dev
     if (n == 0) return 0;
     const Batch b{call_dev, qual_dev, x_dev, xrow_dev, pos_buf_dev, pos_meta_dev, pos_row_dev, show_ref, has_qual, qual_min};
     if (!batch_ok(who, b, off_dev, status_dev, info_dev, text_cap)) return 1;
-    if (!workspace || ((uintptr_t)workspace & 255)) { cv_set_error("%s: the workspace must be there and 256-byte aligned", who); return 1; }
-    size_t t, tb, total;
-    if (plan(n, &t, &tb, &total)) return 1;
-    if (workspace_bytes < (int64_t)total) {
-        cv_set_error("%s: workspace holds %lld bytes, need %lld", who, (long long)workspace_bytes, (long long)total);
-        return 1;
-    }
+    cv_carver c(workspace);
+    records_ws W;
+    if (plan(c, n, &W)) return 1;
+    if (!cv_workspace_ok(who, workspace, workspace_bytes, c.total())) return 1;
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    int64_t *len = (int64_t *)ws;
-    VCF_HIP(hipMemsetAsync(info_dev, 0, 32, st));
+    int64_t *len = W.len;
+    size_t tb = W.tmp_bytes;
+    CV_HIP(hipMemsetAsync(info_dev, 0, 32, st));
     hipLaunchKernelGGL(vcf_len, dim3((unsigned)((n + 1 + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, b, n, len, status_dev,
                        (unsigned long long *)info_dev);
-    VCF_HIP(hipGetLastError());
-    VCF_HIP(hipcub::DeviceScan::ExclusiveSum(ws + t, tb, (const int64_t *)len, off_dev, (int)(n + 1), st));
+    CV_HIP(hipGetLastError());
+    CV_HIP(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, (const int64_t *)len, off_dev, (int)(n + 1), st));
     hipLaunchKernelGGL(vcf_write, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, b, n, (const int64_t *)off_dev,
                        (const uint8_t *)status_dev, info_dev, text_dev, text_cap);
-    VCF_HIP(hipGetLastError());
+    CV_HIP(hipGetLastError());
     return 0;
 }
 
