@@ -360,3 +360,24 @@ def check(rc):
     if rc != 0:
         msg = load().cv_last_error()
         raise CvError(msg.decode("utf-8", "replace") if msg else "clairvoyante_amd call failed")
+
+
+def ptr(t):
+    """the data pointer of a tensor as an argument; None for None and for an empty tensor"""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+
+def stream_arg(device_or_stream):
+    """a torch stream, or the current stream of a device, as an argument"""
+    s = device_or_stream
+    if not hasattr(s, "cuda_stream"):
+        import torch
+        s = torch.cuda.current_stream(s)
+    return ctypes.c_void_p(s.cuda_stream)
+
+
+def workspace(query, *args):
+    """one cv_*_workspace size query -> bytes"""
+    need = ctypes.c_int64()
+    check(query(*(args + (ctypes.byref(need),))))
+    return need.value

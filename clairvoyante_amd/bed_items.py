@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _lib, draws
 from . import utils_v2
-from .utils_v2 import TRUTH_FORMAT_BED, _Intervals, _TruthHandOver, _TruthReader, _gpu_present, _read_bed_truth, _truth_chunks
+from .utils_v2 import _Intervals, _SlabWalk, _TruthHandOver, _TruthReader, _gpu_present, _read_bed_truth, _truth_chunks, _while_table_full
 
 SAMPLE_TILE = 1 << 24               # positions per call of the sampler: its workspace takes 8 bytes per position
 SAMPLE_FIRST_CAP = None             # tests: room for kept positions in the first try of every tile (None: from prob)
@@ -207,75 +207,53 @@ class _ItemWalk(object):
         import torch
         self.torch, self.device, self.out = torch, device, out
         self.rd = _TruthReader(device)
-        self.lib, self.P = self.rd.lib, self.rd._p
-        self.st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        self.lib, self.st = self.rd.lib, _lib.stream_arg(device)
         self.total = self.kept = 0
         self.bytes_per_line = 16.0                           # sizes the line table: the slab before says what to expect
         self.pinned = None
-        E = lambda n, dt=torch.int64: torch.empty(n, dtype=dt, device=device)
-        self.E = E
-        need = ctypes.c_int64()
-        (begin, end, run, run_ctg, nruns), = self.rd.read(bed_fn, TRUTH_FORMAT_BED)
-        nb, self.nctg = int(begin.numel()), len(self.rd.names)
-        self.bed_off, self.bed_begin, self.bed_emax = E(self.nctg + 1), E(nb), E(nb)
-        _lib.check(self.lib.cv_bed_table_workspace(nb, ctypes.byref(need)))
-        ws = E(max(need.value, 1), torch.uint8)
-        _lib.check(self.lib.cv_bed_table_dev(nb, self.P(begin), self.P(end), self.P(run), self.P(run_ctg), nruns, self.nctg,
-                                             self.P(self.bed_off), self.P(self.bed_begin), self.P(self.bed_emax), self.P(ws),
-                                             need.value, self.st))
+        self.E = lambda n, dt=torch.int64: torch.empty(n, dtype=dt, device=device)
+        self.bed_off, self.bed_begin, self.bed_emax, _nb, self.nctg = self.rd.bed_table(bed_fn)
         torch.cuda.current_stream(device).synchronize()       # (the workspace and the rows may go)
-
-    def _run_ids(self, buf, at, n, tok, runs):
-        """the BED contig id of each run from its start token, -1 for a contig the BED lacks"""
-        t = tok[:runs].cpu().numpy()
-        idx = np.repeat(t[:, 0] - np.cumsum(np.concatenate(([0], t[:-1, 1]))), t[:, 1]) + np.arange(int(t[:, 1].sum()))
-        raw = buf[at:at + n][self.torch.from_numpy(idx).to(self.device)].cpu().numpy().tobytes()
-        ids, k = [], 0
-        for ln in t[:, 1].tolist():
-            ids.append(self.rd.ids.get(raw[k:k + ln], -1))
-            k += ln
-        return self.torch.from_numpy(np.array(ids, dtype=np.int32)).to(self.device)
 
     def slab(self, buf, lo, hi, padded_end):
         """the two passes over buf[lo:hi], again while the line table is full -> bytes consumed.  padded_end: the offset
-        behind a newline this reader appended to the file's last line (None: there is none): that byte is not written"""
-        torch, lib, P, E = self.torch, self.lib, self.P, self.E
+        behind a newline the walk appended to the file's last line (None: there is none): that byte is not written"""
+        torch, lib, P, E = self.torch, self.lib, _lib.ptr, self.E
         want_text = 1 if self.out is not None else 0
-        done = 0
-        need = ctypes.c_int64()
-        while lo + done < hi:
-            at, n = lo + done, hi - lo - done
+
+        def line_pass(at, n, max_lines):
             text_ptr = ctypes.c_void_p(buf.data_ptr() + at)
-            max_lines = min(int(n / self.bytes_per_line * 1.25) + 1024, n)
-            _lib.check(lib.cv_item_lines_workspace(n, max_lines, ctypes.byref(need)))
-            ws = E(need.value, torch.uint8)
+            need = _lib.workspace(lib.cv_item_lines_workspace, n, max_lines)
+            ws = E(need, torch.uint8)
             pos, run, off, ln = E(max_lines), E(max_lines, torch.int32), E(max_lines), E(max_lines)
             tok, info_dev = E((max_lines, 2)), E(8)
             with _Timer(torch, "lines") as tm:
                 _lib.check(lib.cv_item_lines_dev(text_ptr, n, max_lines, P(pos), P(run), P(off), P(ln), P(tok), P(info_dev), P(ws),
-                                                 need.value, self.st))
+                                                 need, self.st))
             used, lines, rows, _skipped, host, runs = info_dev.cpu().tolist()[:6]
             tm.read()
             if host:
                 raise _RestToHost(at, "%d line(s) only the host loop defines the result for (a blank line, fewer than two tokens, "
                                       "a position that is not canonical decimal, '\\r', bytes outside printable ASCII, ...)" % host)
             if rows:
-                run_ctg = self._run_ids(buf, at, n, tok, runs)
-                _lib.check(lib.cv_items_keep_workspace(rows, ctypes.byref(need)))
-                ws = E(need.value, torch.uint8)
+                # the BED contig id of each run from its start token, -1 for a contig the BED lacks
+                ids = [self.rd.ids.get(name, -1) for name in self.rd.run_names(buf, at, n, tok, runs)]
+                run_ctg = torch.from_numpy(np.array(ids, dtype=np.int32)).to(self.device)
+                need = _lib.workspace(lib.cv_items_keep_workspace, rows)
+                ws = E(need, torch.uint8)
                 text_out = E(used, torch.uint8) if want_text else None
                 cnt = E(4)
                 with _Timer(torch, "keep") as tm:
                     _lib.check(lib.cv_items_keep_dev(text_ptr, n, rows, P(pos), P(run), P(off), P(ln), P(run_ctg), runs, self.nctg,
                                                      P(self.bed_off), P(self.bed_begin), P(self.bed_emax), want_text, P(text_out),
-                                                     used if want_text else 0, P(cnt), P(ws), need.value, self.st))
+                                                     used if want_text else 0, P(cnt), P(ws), need, self.st))
                     last = None
                     if want_text and padded_end is not None and at + used == padded_end:
-                        # is the file's last line kept?  Then the newline this reader gave it stays behind
+                        # is the file's last line kept?  Then the newline the walk gave it stays behind
                         last = E(4)
                         _lib.check(lib.cv_items_keep_dev(text_ptr, n, 1, P(pos[rows - 1:]), P(run[rows - 1:]), P(off[rows - 1:]),
                                                          P(ln[rows - 1:]), P(run_ctg), runs, self.nctg, P(self.bed_off),
-                                                         P(self.bed_begin), P(self.bed_emax), 0, None, 0, P(last), P(ws), need.value,
+                                                         P(self.bed_begin), P(self.bed_emax), 0, None, 0, P(last), P(ws), need,
                                                          self.st))
                 _rows, kept, nbytes, _zero = cnt.cpu().tolist()
                 tm.read()
@@ -289,75 +267,22 @@ class _ItemWalk(object):
                 self.kept += kept
             self.total += lines
             _counts["device_lines"] += lines
-            done += used
             if lines:
                 self.bytes_per_line = max(used / float(lines), 2.0)
-            if lines < max_lines:
-                break
-        return done
+            return used, lines
+
+        return _while_table_full(lo, hi, lambda n: min(int(n / self.bytes_per_line * 1.25) + 1024, n), line_pass)
 
     def walk(self, input_fn):
         """every slab of the file; _RestToHost / _TruthHandOver with .blocks = the bytes the host continues over"""
-        import warnings
-        torch = self.torch
         slab_bytes = max(int(utils_v2.TRUTH_SLAB_BYTES), 1)
-        carry = torch.empty(0, dtype=torch.uint8, device=self.device)
-        chunks = _truth_chunks(input_fn, slab_bytes)
+        walk = _SlabWalk(self.torch, self.device, _truth_chunks(input_fn, slab_bytes), slab_bytes, self.rd._inflate,
+                         pad_always=False, join_unbroken=True, whole_lines=True, keep_open=(_RestToHost, _TruthHandOver))
         try:
-            kind, piece = next(chunks, (None, None))
-            while kind is not None:
-                nxt = next(chunks, (None, None))
-                last, head = nxt[0] is None, int(carry.numel())
-                if kind == "host" and not last and not (np.asarray(piece) == 10).any():
-                    # no line ends in this piece: it joins the unfinished line without a pass of its own
-                    with warnings.catch_warnings():
-                        warnings.simplefilter("ignore")
-                        carry = torch.cat((carry, torch.from_numpy(piece).to(self.device)))
-                    kind, piece = nxt
-                    continue
-                if kind == "bgzf":
-                    buf = self.rd._inflate(piece, head)
-                    n = head + piece.n
-                else:
-                    n = head + len(piece)
-                    buf = torch.empty(n + 1, dtype=torch.uint8, device=self.device)
-                    with warnings.catch_warnings():
-                        warnings.simplefilter("ignore")              # (a read-only source: the memory map, a bytes object)
-                        buf[head:n].copy_(torch.from_numpy(piece))
-                if head:
-                    buf[:head].copy_(carry)
-                # a last line without a newline is a line: it gets one here, which is not written; behind a newline
-                # nothing is added (a blank line is the definition's IndexError)
-                padded_end = None
-                if last and n and int(buf[n - 1]) != 10:
-                    buf[n:n + 1].fill_(10)
-                    n += 1
-                    padded_end = n
-                lo, hi = 0, min(head + slab_bytes, n)
-                # several windows over one buffer (BGZF members overshoot the slab; slabs shorter than a line): where the
-                # lines end says which windows are worth a pass at all
-                ends = (buf[:n] == 10).nonzero().flatten().cpu().numpy() + 1 if hi < n else None
-                try:
-                    while True:
-                        stop = hi
-                        if ends is not None:
-                            k = int(np.searchsorted(ends, hi, side="right"))
-                            stop = int(ends[k - 1]) if k else 0
-                        if stop > lo:
-                            lo += self.slab(buf, lo, stop, padded_end)
-                        if hi >= n:
-                            break
-                        hi = min(hi + slab_bytes, n)
-                except _RestToHost as e:
-                    e.blocks = itertools.chain([buf[e.at:n - (padded_end is not None)].cpu().numpy().tobytes()],
-                                               _host_blocks(itertools.chain([nxt], chunks)))
-                    raise
-                carry = buf[lo:n].clone()
-                kind, piece = nxt
-        except (_RestToHost, _TruthHandOver):
-            raise
-        except BaseException:
-            chunks.close()
+            walk.run(self.slab)
+        except _RestToHost as e:
+            rest, chunks = walk.rest(e.at)
+            e.blocks = itertools.chain([rest], _host_blocks(chunks))
             raise
 
 
@@ -430,18 +355,17 @@ def sample_positions_device(ctg, start, end, prob, intervals, seed, device=None)
         return np.zeros(0, dtype=np.int64)
     device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
     lib = _lib.load()
-    P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    P = _lib.ptr
     out = []
     with torch.cuda.device(device):
-        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        st = _lib.stream_arg(device)
         nbed, b_dev, e_dev = 0, None, None
         if intervals is not None:
             b, emax = _table_of(intervals)
             nbed, b_dev, e_dev = len(b), torch.from_numpy(b).to(device), torch.from_numpy(emax).to(device)
         tile = max(int(SAMPLE_TILE), 1)
-        need = ctypes.c_int64()
-        _lib.check(lib.cv_sample_positions_workspace(min(tile, end - start), ctypes.byref(need)))
-        ws = torch.empty(need.value, dtype=torch.uint8, device=device)
+        need = _lib.workspace(lib.cv_sample_positions_workspace, min(tile, end - start))
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
         cnt = torch.empty(2, dtype=torch.int64, device=device)
         h = draws.fnv1a32(ctg)
         for first in range(start, end, tile):
@@ -452,7 +376,7 @@ def sample_positions_device(ctg, start, end, prob, intervals, seed, device=None)
                 pos = torch.empty(cap, dtype=torch.int64, device=device)
                 with _Timer(torch, "sample") as tm:
                     _lib.check(lib.cv_sample_positions_dev(int(seed), h, first, count, float(prob), nbed, P(b_dev), P(e_dev), P(pos), cap,
-                                                           P(cnt), P(ws), need.value, st))
+                                                           P(cnt), P(ws), need, st))
                 wrote, would = cnt.cpu().tolist()
                 tm.read()
                 if wrote == would:

@@ -435,11 +435,10 @@ def enqueue_records(args, m, fetcher, num, xd, pos, call, qual):
             tok, tmeta = _packed_tokens(buf, np.ascontiguousarray(meta[:n], dtype=np.int64))
             block, offs, stage = fetcher.upload([tmeta, tok])
             calls.append((start, n, block.data_ptr() + offs[1], block.data_ptr() + offs[0], None, int(tmeta[:, 1].max()), (block, stage)))
-    need = ctypes.c_int64()
     parts = []
     for start, n, text_ptr, meta_ptr, keep, longest, held in calls:
-        _lib.check(lib.cv_vcf_records_workspace(n, ctypes.byref(need)))
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        need = _lib.workspace(lib.cv_vcf_records_workspace, n)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
         small = torch.empty(4 + n + 1, dtype=torch.int64, device=dev)            # info | off
         status = torch.empty(n, dtype=torch.uint8, device=dev)
         cap = n * (longest + 160)
@@ -449,7 +448,7 @@ def enqueue_records(args, m, fetcher, num, xd, pos, call, qual):
             ctypes.c_void_p(xd.data_ptr() + start * 2112), None, ctypes.c_void_p(text_ptr), ctypes.c_void_p(meta_ptr),
             ctypes.c_void_p(keep.data_ptr()) if keep is not None else None, 1 if args.showRef else 0, 0 if args.qual is None else 1,
             0 if args.qual is None else int(args.qual), ctypes.c_void_p(small.data_ptr() + 32), ctypes.c_void_p(status.data_ptr()),
-            ctypes.c_void_p(small.data_ptr()), ctypes.c_void_p(text.data_ptr()), cap, ctypes.c_void_p(ws.data_ptr()), need.value,
+            ctypes.c_void_p(small.data_ptr()), ctypes.c_void_p(text.data_ptr()), cap, ctypes.c_void_p(ws.data_ptr()), need,
             m._stream()))
         parts.append({"info": small[:4], "text": text, "held": (ws, small, status, held)})
     return parts

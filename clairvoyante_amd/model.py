@@ -104,7 +104,7 @@ class Clairvoyante(object):
 
     # ---- helpers --------------------------------------------------------------
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream_arg(self.device)
 
     accepts_device_batches = True      # train/getLoss/predict take torch tensors that already live on self.device
 

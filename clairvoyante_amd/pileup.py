@@ -89,8 +89,7 @@ class Pileup(object):
     __del__ = close
 
     def _stream(self):
-        import torch
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream_arg(self.device)
 
     def set_reference(self, seq, first_pos0=0):
         """seq: the bases `samtools faidx` printed (str/bytes); seq[0] is 0-based position first_pos0"""
@@ -295,7 +294,7 @@ class Pileup(object):
         for k in ("digits", "centre", "acgt", "cflag", "row"):
             col[k] = torch.empty(n, dtype=torch.uint8, device=self.device)
         u8 = touched.to(torch.uint8)
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if n else None
+        p = _lib.ptr
         _lib.check(self.lib.cv_bamtrain_columns(self.h, p(depth), p(u8), int(minCoverage), p(col["pos"]), p(col["digits"]),
                                                 p(col["centre"]), p(col["acgt"]), p(col["cflag"]), p(col["row"]),
                                                 self._stream()))
@@ -315,12 +314,11 @@ class Pileup(object):
             raise _lib.CvError("call_columns: %d flags for %d centres" % (touched.numel(), n))
         with torch.cuda.device(self.device):
             u8 = touched.contiguous().view(torch.uint8) if touched.dtype == torch.bool else touched.to(torch.uint8).contiguous()
-            need = ctypes.c_int64(0)
-            _lib.check(self.lib.cv_call_columns_workspace(n, ctypes.byref(need)))
+            need = _lib.workspace(self.lib.cv_call_columns_workspace, n)
             cap = len(cb) + CALL_COLUMNS_ROW_TEXT * n
             # info [4] | index [n] | meta [n,6] | text: the meta and the text are neighbours, so one copy fetches both
             block = torch.empty(32 + 8 * n + 48 * n + cap + 8, dtype=torch.uint8, device=self.device)
-            ws = torch.empty(max(need.value, 256), dtype=torch.uint8, device=self.device)
+            ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
             base = block.data_ptr()
             _lib.check(self.lib.cv_pileup_call_columns(self.h, cb, len(cb), ctypes.c_void_p(u8.data_ptr()) if n else None,
                                                        ctypes.c_void_p(base + 32), ctypes.c_void_p(base + 32 + 8 * n),
@@ -423,10 +421,9 @@ def format_rows_device(ctg, centers, ref_seq, ref_shift, tensors_dev, batch=ROWT
         else:
             ref_dev = torch.frombuffer(bytearray(host_ref) or bytearray(1), dtype=torch.uint8).to(dev)[:len(host_ref)]
         ref_len = int(ref_dev.numel())
-        need = ctypes.c_int64(0)
-        _lib.check(lib.cv_tensor_rows_text_workspace(min(batch, max(k, 1)), ctypes.byref(need)))
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        need = _lib.workspace(lib.cv_tensor_rows_text_workspace, min(batch, max(k, 1)))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        stream = _lib.stream_arg(dev)
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())
         for s in range(0, k, batch):
             n = min(batch, k - s)
@@ -437,7 +434,7 @@ def format_rows_device(ctg, centers, ref_seq, ref_shift, tensors_dev, batch=ROWT
 
             def call(text, cap):
                 _lib.check(lib.cv_tensor_rows_text_dev(cb, len(cb), ptr(cen), n, ptr(ref_dev) if ref_len else None, int(ref_shift),
-                                                       ref_len, ptr(cnt), ptr(off), ptr(status), text, cap, ptr(ws), need.value,
+                                                       ref_len, ptr(cnt), ptr(off), ptr(status), text, cap, ptr(ws), need,
                                                        stream))
             call(None, 0)                                   # lengths and status: the text is sized exactly
             total, host_rows = (int(v) for v in torch.stack((off[n], status.sum(dtype=torch.int64))).tolist())

@@ -1393,7 +1393,7 @@ class _TextSlabDevice(object):
             stage = [self._to_device(comp[:len(slab.comp)], slab.comp), self._to_device(table.view(torch.uint8).reshape(-1), slab.table.view(np.uint8).reshape(-1))]
             _lib.check(self.lib.cv_inflate_bgzf_dev(ctypes.c_void_p(comp.data_ptr()), ctypes.c_void_p(table.data_ptr()), m,
                                                     ctypes.c_void_p(text.data_ptr() + head), slab.n, ctypes.c_void_p(status.data_ptr()),
-                                                    ctypes.c_void_p(self.copy_stream.cuda_stream)))
+                                                    _lib.stream_arg(self.copy_stream)))
             if k:
                 self._find_newlines(text, head, slab, back.data_ptr() + mpad, self.copy_stream)
             if slab.last:
@@ -1407,7 +1407,7 @@ class _TextSlabDevice(object):
         """enqueues cv_text_find_newline_dev for slab.queries over the slab's inflated text; int64 results at out_ptr"""
         q = (ctypes.c_int64 * len(slab.queries))(*slab.queries)
         _lib.check(self.lib.cv_text_find_newline_dev(ctypes.c_void_p(text.data_ptr() + head), slab.n, q, len(slab.queries),
-                                                     ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream.cuda_stream)))
+                                                     ctypes.c_void_p(out_ptr), _lib.stream_arg(stream)))
 
     def settle(self, up, slab, head):
         """waits for the slab's inflate; members the device left to the host are inflated there and copied into place.
@@ -1447,7 +1447,7 @@ class _TextSlabDevice(object):
         (cv_gzip_crc_dev), chunks, window (of the slab that follows)."""
         torch, lib, np_ = self.torch, self.lib, np
         nb = len(comp)
-        s = ctypes.c_void_p(self.copy_stream.cuda_stream)
+        s = _lib.stream_arg(self.copy_stream)
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())
         with torch.cuda.device(self.device), torch.cuda.stream(self.copy_stream):
             cdev = torch.empty(nb + 8, dtype=torch.uint8, device=self.device)
@@ -1569,7 +1569,7 @@ class _TextSlabDevice(object):
             out = torch.empty(k * 48 + total + 8, dtype=torch.uint8, device=self.device)
             _lib.check(self.lib.cv_text_gather_tokens(
                 ctypes.c_void_p(job["text_ptr"]), ctypes.c_void_p(job["meta_ptr"]), ctypes.c_void_p(idx.data_ptr()), k,
-                ctypes.c_void_p(out.data_ptr() + k * 48), total, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(self.stream.cuda_stream)))
+                ctypes.c_void_p(out.data_ptr() + k * 48), total, ctypes.c_void_p(out.data_ptr()), _lib.stream_arg(self.stream)))
             host = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)
             host.copy_(out, non_blocking=True)
         self.stream.synchronize()
@@ -1581,20 +1581,19 @@ class _TextSlabDevice(object):
         torch = self.torch
         text, n, ev, _stage = up
         cap, length = self.cap, n - start
-        need = ctypes.c_int64()
-        _lib.check(self.lib.cv_parse_tensor_text_dev_workspace(length, cap, ctypes.byref(need)))
+        need = _lib.workspace(self.lib.cv_parse_tensor_text_dev_workspace, length, cap)
         with torch.cuda.device(self.device):
             x = torch.empty((cap, _NV), dtype=torch.float32, device=self.device)
             self.stream.wait_stream(torch.cuda.current_stream(self.device))    # (a recycled block: its last reader)
             with torch.cuda.stream(self.stream):
                 self.stream.wait_event(ev)
-                ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+                ws = torch.empty(need, dtype=torch.uint8, device=self.device)
                 out = torch.empty(32 + cap * 48 + cap, dtype=torch.uint8, device=self.device)   # info | meta | status
                 p = out.data_ptr()
                 _lib.check(self.lib.cv_parse_tensor_text_dev(
                     ctypes.c_void_p(text.data_ptr() + start), length, cap, ctypes.c_void_p(x.data_ptr()),
                     ctypes.c_void_p(p + 32), ctypes.c_void_p(p + 32 + cap * 48), ctypes.c_void_p(p),
-                    ctypes.c_void_p(ws.data_ptr()), need.value, ctypes.c_void_p(self.stream.cuda_stream)))
+                    ctypes.c_void_p(ws.data_ptr()), need, _lib.stream_arg(self.stream)))
                 host = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)
                 host.copy_(out, non_blocking=True)
         return {"x": x, "host": host, "keep": (text, ws), "out": out, "text_ptr": text.data_ptr() + start, "meta_ptr": p + 32}
@@ -1629,7 +1628,7 @@ class _TextSlabDevice(object):
                 idx = torch.from_numpy(np.ascontiguousarray(index, dtype=np.int64)).to(self.device)
                 _lib.check(self.lib.cv_text_gather_rows(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(idx.data_ptr()),
                                                         len(index), ctypes.c_void_p(out.data_ptr()),
-                                                        ctypes.c_void_p(self.stream.cuda_stream)))
+                                                        _lib.stream_arg(self.stream)))
             self.stream.synchronize()
             return out.reshape((len(index),) + _SHAPE)
 
@@ -2176,6 +2175,28 @@ def contig_token_ok(tok):
     return b":" not in tok and b"\0" not in tok and tok.isascii()
 
 
+class _ContigIds(object):
+    """contig names (bytes) and their ids in order of first appearance.  A new name is refused with the owner's exception
+    `error` and its own words: `bad_token` (None: the owner takes any token; {name!r} stands for the name) when
+    contig_token_ok refuses it, then prefix + "more than %d contigs" past TRAINSET_MAX_CONTIGS"""
+
+    def __init__(self, error, prefix="", bad_token=None, names=()):
+        self.error, self.prefix, self.bad_token = error, prefix, bad_token
+        self.names = list(names)
+        self.ids = {n: i for i, n in enumerate(self.names)}
+
+    def id_of(self, name):
+        cid = self.ids.get(name)
+        if cid is None:
+            if self.bad_token is not None and not contig_token_ok(name):
+                raise self.error(self.prefix + self.bad_token.format(name=name))
+            if len(self.names) >= TRAINSET_MAX_CONTIGS:
+                raise self.error(self.prefix + "more than %d contigs" % TRAINSET_MAX_CONTIGS)
+            cid = self.ids[name] = len(self.names)
+            self.names.append(name)
+        return cid
+
+
 def shuffled_indices(total):
     """random.shuffle of range(total): the permutation random.shuffle applies to ANY list of that length under the same
     generator state (it draws from the length alone), so item p[r] of the sorted keys is item r of the shuffled ones"""
@@ -2342,30 +2363,122 @@ def _truth_chunks(fn, want):
         gz.close()
 
 
+class _SlabWalk(object):
+    """The text of _truth_chunks slab by slab in one buffer on `device`: every piece is uploaded (inflate(piece, head) for
+    BGZF members) behind the carry, the unfinished line of the piece before; the file's last piece gets its newline; then
+    run() hands consume(buf, lo, hi, padded_end) windows of slab_bytes over the buffer (BGZF members overshoot the slab,
+    slabs are shorter than a line), which answers with the bytes it consumed.  padded_end: the offset behind a newline
+    this walk appended (None: there is none).  Stream and device are the caller's: nothing here asks torch.cuda.
+      pad_always      True: the last piece always gets a newline (truth lists and BED files: a blank line is skipped);
+                      False: only a last line that lacks one (item files: a blank line is the definition's IndexError)
+      join_unbroken   a host piece without a newline joins the carry without a pass (item files: a tensor row spans many
+                      small slabs; the truth reader does not scan every piece on the host for that)
+      whole_lines     only windows that end a line are passed, cut back to that end (item files: as above; the truth
+                      reader spends no pass over the buffer to find the ends)
+      keep_open       exceptions that leave the chunk generator open: rest() continues over it"""
+
+    def __init__(self, torch, device, chunks, slab_bytes, inflate, pad_always, join_unbroken=False, whole_lines=False,
+                 keep_open=()):
+        self.torch, self.device, self.chunks, self.slab_bytes, self.inflate = torch, device, chunks, slab_bytes, inflate
+        self.pad_always, self.join_unbroken, self.whole_lines, self.keep_open = pad_always, join_unbroken, whole_lines, keep_open
+
+    def _host(self, piece):
+        import warnings
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")                  # (a read-only source: the memory map, a bytes object)
+            return self.torch.from_numpy(piece)
+
+    def run(self, consume):
+        torch, chunks, slab_bytes = self.torch, self.chunks, self.slab_bytes
+        carry = torch.empty(0, dtype=torch.uint8, device=self.device)
+        try:
+            kind, piece = next(chunks, (None, None))
+            while kind is not None:
+                self.nxt = nxt = next(chunks, (None, None))
+                last, head = nxt[0] is None, int(carry.numel())
+                if self.join_unbroken and kind == "host" and not last and not (np.asarray(piece) == 10).any():
+                    carry = torch.cat((carry, self._host(piece).to(self.device)))
+                    kind, piece = nxt
+                    continue
+                if kind == "bgzf":
+                    buf = self.inflate(piece, head)
+                    n = head + piece.n
+                else:
+                    n = head + len(piece)
+                    buf = torch.empty(n + 1, dtype=torch.uint8, device=self.device)
+                    buf[head:n].copy_(self._host(piece))
+                if head:
+                    buf[:head].copy_(carry)
+                padded_end = None
+                if last and (self.pad_always or (n and int(buf[n - 1]) != 10)):
+                    buf[n:n + 1].fill_(10)
+                    n += 1
+                    padded_end = n
+                self.buf, self.n, self.padded_end = buf, n, padded_end
+                lo, hi = 0, min(head + slab_bytes, n)
+                ends = (buf[:n] == 10).nonzero().flatten().cpu().numpy() + 1 if self.whole_lines and hi < n else None
+                while True:
+                    stop = hi
+                    if ends is not None:
+                        k = int(np.searchsorted(ends, hi, side="right"))
+                        stop = int(ends[k - 1]) if k else 0
+                    if stop > lo:
+                        lo += consume(buf, lo, stop, padded_end)
+                    if hi >= n:
+                        break
+                    hi = min(hi + slab_bytes, n)
+                carry = buf[lo:n].clone()
+                kind, piece = nxt
+        except BaseException as e:
+            if not isinstance(e, self.keep_open):
+                chunks.close()
+            raise
+        chunks.close()
+
+    def rest(self, at):
+        """after an exception from consume: (the buffer from offset `at` on as bytes, without the appended newline; the
+        chunks still to come)"""
+        import itertools
+        return (self.buf[at:self.n - (self.padded_end is not None)].cpu().numpy().tobytes(),
+                itertools.chain([self.nxt], self.chunks))
+
+
+def _while_table_full(lo, hi, max_lines_of, line_pass):
+    """line_pass(at, n, max_lines) -> (bytes used, lines) over buf[lo:hi], from where the pass before stopped, again while
+    the line table (max_lines_of(n) lines for n bytes) came back full -> bytes consumed"""
+    done = 0
+    while lo + done < hi:
+        n = hi - lo - done
+        max_lines = max_lines_of(n)
+        used, lines = line_pass(lo + done, n, max_lines)
+        done += used
+        if lines < max_lines:
+            break
+    return done
+
+
 class _TruthReader(object):
     """the device side of truth_tables: the line pass over one file slab by slab, the rows of all slabs, the contig ids"""
 
     def __init__(self, device):
         import torch
         self.torch, self.device, self.lib = torch, device, _lib.load()
-        self.names, self.ids = [], {}
-
-    def _p(self, t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        # (any token is a truth contig here: only the sources of a truth VCF are held to contig_token_ok, by their caller)
+        self.contigs = _ContigIds(_TruthHandOver)
+        self.names, self.ids = self.contigs.names, self.contigs.ids
 
     def _inflate(self, slab, head):
         """a group of BGZF members inflated behind `head` free bytes -> the text buffer (members the device leaves to the
         host are inflated there)"""
-        torch = self.torch
+        torch, P = self.torch, _lib.ptr
         m = len(slab.table)
         text = torch.empty(head + slab.n + 1, dtype=torch.uint8, device=self.device)
         comp = torch.zeros(len(slab.comp) + 8, dtype=torch.uint8, device=self.device)
         comp[:len(slab.comp)].copy_(torch.from_numpy(np.array(slab.comp)))
         table = torch.from_numpy(slab.table).to(self.device)
         status = torch.zeros(m, dtype=torch.uint8, device=self.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self.lib.cv_inflate_bgzf_dev(self._p(comp), self._p(table), m, ctypes.c_void_p(text.data_ptr() + head), slab.n,
-                                                self._p(status), st))
+        _lib.check(self.lib.cv_inflate_bgzf_dev(P(comp), P(table), m, ctypes.c_void_p(text.data_ptr() + head), slab.n, P(status),
+                                                _lib.stream_arg(self.device)))
         for i in np.flatnonzero(status.cpu().numpy() != 1):                # CV_BGZF_OK
             try:
                 out = slab.inflate_member(int(i))
@@ -2381,43 +2494,12 @@ class _TruthReader(object):
         within (the BED's: a contig outside them is the definition's KeyError).  filters (format VCF): (contig bytes,
         lower, upper) per source, bounds None for none; the file is read ONCE, every slab passes once per source, and the
         runs of a source carry no contig id yet (run_ctg is None: they are all the source's contig)"""
-        import warnings
         torch = self.torch
         slab_bytes = max(int(TRUTH_SLAB_BYTES), 1)
         passes = [{"filter": f, "cols": ([], [], []), "run_ctg": []} for f in (filters if filters is not None else [None])]
-        carry = torch.empty(0, dtype=torch.uint8, device=self.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        chunks = _truth_chunks(fn, slab_bytes)
-        try:
-            kind, piece = next(chunks, (None, None))
-            while kind is not None:
-                nxt = next(chunks, (None, None))
-                last, head = nxt[0] is None, int(carry.numel())
-                if kind == "bgzf":
-                    buf = self._inflate(piece, head)
-                    n = head + piece.n
-                else:
-                    n = head + len(piece)
-                    buf = torch.empty(n + 1, dtype=torch.uint8, device=self.device)
-                    with warnings.catch_warnings():
-                        warnings.simplefilter("ignore")              # (a read-only source: the memory map, a bytes object)
-                        buf[head:n].copy_(torch.from_numpy(piece))
-                if head:
-                    buf[:head].copy_(carry)
-                if last:                       # a last line without newline is a line; behind a newline this adds a blank one
-                    buf[n:n + 1].fill_(10)
-                    n += 1
-                lo, hi = 0, min(head + slab_bytes, n)
-                while True:
-                    if hi > lo:
-                        lo += self._slab(buf, lo, hi, fmt, known, passes, st)
-                    if hi >= n:
-                        break
-                    hi = min(hi + slab_bytes, n)
-                carry = buf[lo:n].clone()
-                kind, piece = nxt
-        finally:
-            chunks.close()
+        st = _lib.stream_arg(self.device)
+        walk = _SlabWalk(torch, self.device, _truth_chunks(fn, slab_bytes), slab_bytes, self._inflate, pad_always=True)
+        walk.run(lambda buf, lo, hi, _padded_end: self._slab(buf, lo, hi, fmt, known, passes, st))
         bed = fmt == TRUTH_FORMAT_BED
         cat = lambda parts, dt, shape: torch.cat(parts) if parts else torch.empty(shape, dtype=dt, device=self.device)
         out = []
@@ -2429,27 +2511,21 @@ class _TruthReader(object):
 
     def _slab(self, buf, lo, hi, fmt, known, passes, st):
         """the line pass over buf[lo:hi], once per entry of `passes`, again while the line table is full -> bytes consumed"""
-        torch, lib = self.torch, self.lib
-        done = 0
-        while lo + done < hi:
-            n = hi - lo - done
-            text_ptr = buf.data_ptr() + lo + done
-            max_lines = n // 6 + 16
-            need = ctypes.c_int64()
-            _lib.check(lib.cv_truth_lines_workspace(n, max_lines, ctypes.byref(need)))
-            ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
-            bed = fmt == TRUTH_FORMAT_BED
+        torch, lib, P = self.torch, self.lib, _lib.ptr
+        bed = fmt == TRUTH_FORMAT_BED
+        E = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+
+        def line_pass(at, n, max_lines):
+            need = _lib.workspace(lib.cv_truth_lines_workspace, n, max_lines)
+            ws = E(need, torch.uint8)
             for p in passes:
-                pos = torch.empty(max_lines, dtype=torch.int64, device=self.device)
-                end = torch.empty(max_lines, dtype=torch.int64, device=self.device) if bed else None
-                label = None if bed else torch.empty((max_lines, 16), dtype=torch.float32, device=self.device)
-                run = torch.empty(max_lines, dtype=torch.int32, device=self.device)
-                tok = torch.empty((max_lines, 2), dtype=torch.int64, device=self.device)
-                info_dev = torch.empty(8, dtype=torch.int64, device=self.device)
+                pos, end = E(max_lines, torch.int64), E(max_lines, torch.int64) if bed else None
+                label = None if bed else E((max_lines, 16), torch.float32)
+                run, tok, info_dev = E(max_lines, torch.int32), E((max_lines, 2), torch.int64), E(8, torch.int64)
                 ctg, lower, upper = p["filter"] if p["filter"] is not None else (None, None, None)
-                _lib.check(lib.cv_truth_lines_dev(ctypes.c_void_p(text_ptr), n, fmt, ctg, len(ctg or b""), int(lower is not None),
-                                                  lower or 0, upper or 0, max_lines, self._p(pos), self._p(end), self._p(label),
-                                                  self._p(run), self._p(tok), self._p(info_dev), self._p(ws), need.value, st))
+                _lib.check(lib.cv_truth_lines_dev(ctypes.c_void_p(buf.data_ptr() + at), n, fmt, ctg, len(ctg or b""),
+                                                  int(lower is not None), lower or 0, upper or 0, max_lines, P(pos), P(end), P(label),
+                                                  P(run), P(tok), P(info_dev), P(ws), need, st))
                 used, lines, rows, skipped, host, runs = info_dev.cpu().tolist()[:6]
                 _truth_counts["device_lines"] += rows + skipped
                 _truth_counts["host_lines"] += host
@@ -2460,36 +2536,46 @@ class _TruthReader(object):
                 if runs and p["filter"] is not None:
                     p["run_ctg"] += [-1] * runs                      # (every run of a source is the source's contig)
                 elif runs:
-                    t = tok[:runs].cpu().numpy()
-                    idx = np.repeat(t[:, 0] - np.cumsum(np.concatenate(([0], t[:-1, 1]))), t[:, 1]) + np.arange(int(t[:, 1].sum()))
-                    raw = buf[lo + done:lo + done + n][torch.from_numpy(idx).to(self.device)].cpu().numpy().tobytes()
-                    at = 0
-                    for ln in t[:, 1].tolist():
-                        name = raw[at:at + ln]
-                        at += ln
-                        p["run_ctg"].append(self.contig_id(name, known))
+                    p["run_ctg"] += [self.contig_id(name, known) for name in self.run_names(buf, at, n, tok, runs)]
                 if rows:
                     p["cols"][0].append(pos[:rows].clone())
                     p["cols"][1].append((end if bed else label)[:rows].clone())
                     p["cols"][2].append(run[:rows] + (len(p["run_ctg"]) - runs))
-            done += used
-            if lines < max_lines:
-                break
-        return done
+            return used, lines
+
+        return _while_table_full(lo, hi, lambda n: n // 6 + 16, line_pass)
+
+    def run_names(self, buf, at, n, tok, runs):
+        """the contig token each run of a line pass over buf[at:at + n] starts with (tok: offset and length per run), read
+        on the host -> list of bytes"""
+        t = tok[:runs].cpu().numpy()
+        idx = np.repeat(t[:, 0] - np.cumsum(np.concatenate(([0], t[:-1, 1]))), t[:, 1]) + np.arange(int(t[:, 1].sum()))
+        raw = buf[at:at + n][self.torch.from_numpy(idx).to(self.device)].cpu().numpy().tobytes()
+        ends = np.cumsum(t[:, 1]).tolist()
+        return [raw[e - ln:e] for e, ln in zip(ends, t[:, 1].tolist())]
+
+    def bed_table(self, bed_fn):
+        """the BED file read and its intervals sorted per contig on the device (the launches are queued on the current
+        stream) -> (bed_off, bed_begin, bed_emax, number of intervals, number of BED contigs)"""
+        torch, P = self.torch, _lib.ptr
+        E = lambda n, dt=torch.int64: torch.empty(n, dtype=dt, device=self.device)
+        (begin, end, run, run_ctg, nruns), = self.read(bed_fn, TRUTH_FORMAT_BED)
+        nb, nctg = int(begin.numel()), len(self.names)
+        bed_off, bed_begin, bed_emax = E(nctg + 1), E(nb), E(nb)
+        need = _lib.workspace(self.lib.cv_bed_table_workspace, nb)
+        ws = E(max(need, 1), torch.uint8)
+        _lib.check(self.lib.cv_bed_table_dev(nb, P(begin), P(end), P(run), P(run_ctg), nruns, nctg, P(bed_off), P(bed_begin),
+                                             P(bed_emax), P(ws), need, _lib.stream_arg(self.device)))
+        return bed_off, bed_begin, bed_emax, nb, nctg
 
     def contig_id(self, name, known):
         """the id of a truth contig: its BED id (known = number of BED contigs; absent = the definition's KeyError), else
         ids in order of first appearance"""
         cid = self.ids.get(name)
-        if cid is None or (known is not None and cid >= known):
-            if known is not None:
-                raise _TruthHandOver("the truth contig %r is absent from the BED file (the host loop's KeyError)"
-                                     % name.decode("ascii", "replace"))
-            if len(self.names) >= TRAINSET_MAX_CONTIGS:
-                raise _TruthHandOver("more than %d contigs" % TRAINSET_MAX_CONTIGS)
-            cid = self.ids[name] = len(self.names)
-            self.names.append(name)
-        return cid
+        if known is not None and (cid is None or cid >= known):
+            raise _TruthHandOver("the truth contig %r is absent from the BED file (the host loop's KeyError)"
+                                 % name.decode("ascii", "replace"))
+        return self.contigs.id_of(name)
 
 
 def vcf_source_filters(sources):
@@ -2506,21 +2592,13 @@ def _truth_tables_device(var_fn, bed_fn, device, want_every, vcf_fn=None, source
     import torch
     device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
     rd = _TruthReader(device)
-    lib, P = rd.lib, rd._p
+    lib, P = rd.lib, _lib.ptr
     E = lambda n, dt=torch.int64: torch.empty(n, dtype=dt, device=device)
     with torch.cuda.device(device):
-        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        need = ctypes.c_int64()
+        st = _lib.stream_arg(device)
         has_bed = bed_fn is not None
-        nb = 0
         if has_bed:
-            (begin, end, run, run_ctg, nruns), = rd.read(bed_fn, TRUTH_FORMAT_BED)
-            nb, nbed_ctg = int(begin.numel()), len(rd.names)
-            bed_off, bed_begin, bed_emax = E(nbed_ctg + 1), E(nb), E(nb)
-            _lib.check(lib.cv_bed_table_workspace(nb, ctypes.byref(need)))
-            ws = E(need.value, torch.uint8)
-            _lib.check(lib.cv_bed_table_dev(nb, P(begin), P(end), P(run), P(run_ctg), nruns, nbed_ctg, P(bed_off), P(bed_begin),
-                                            P(bed_emax), P(ws), need.value, st))
+            bed_off, bed_begin, bed_emax, _nb, _nbed_ctg = rd.bed_table(bed_fn)
         n, known = 0, (len(rd.names) if has_bed else None)
         if var_fn is not None:
             (pos, label, run, run_ctg, nruns), = rd.read(var_fn, TRUTH_FORMAT_VAR, known=known)
@@ -2550,11 +2628,11 @@ def _truth_tables_device(var_fn, bed_fn, device, want_every, vcf_fn=None, source
         truth_pos, every_pos, labels = E(n), E(n), E((n, 16), torch.float32)
         counts = torch.zeros(2, dtype=torch.int64, device=device)
         if var_fn is not None or vcf_fn is not None:
-            _lib.check(lib.cv_truth_tables_workspace(n, ctypes.byref(need)))
-            ws = E(need.value, torch.uint8)
+            need = _lib.workspace(lib.cv_truth_tables_workspace, n)
+            ws = E(need, torch.uint8)
             _lib.check(lib.cv_truth_tables_dev(n, P(pos), P(label), P(run), P(run_ctg), nruns, nctg, 1 if has_bed else 0, P(bed_off),
                                                P(bed_begin), P(bed_emax), P(truth_off), P(truth_pos), P(labels), P(every_off),
-                                               P(every_pos), P(counts), P(ws), need.value, st))
+                                               P(every_pos), P(counts), P(ws), need, st))
         nt, ne = counts.cpu().tolist()                        # (synchronises: the workspaces may go)
         tables = {"bed_off": bed_off, "bed_begin": bed_begin, "bed_emax": bed_emax, "truth_off": truth_off,
                   "truth_pos": truth_pos[:nt], "labels": labels[:nt]}
@@ -2769,7 +2847,8 @@ class _TrainsetBuilder(object):
     def __init__(self, device, names, tables, has_bed, rows_hint):
         import torch
         self.torch, self.device, self.lib = torch, torch.device(device), _lib.load()
-        self.names, self.ids = list(names), {n: i for i, n in enumerate(names)}
+        self.contigs = _ContigIds(*self._REFUSAL, names=names)
+        self.names, self.ids = self.contigs.names, self.contigs.ids
         self.ntab, self.has_bed = len(names), has_bed
         with torch.cuda.device(self.device):
             self.tab = {k: (v if torch.is_tensor(v) else torch.from_numpy(v)).to(self.device) for k, v in tables.items()}
@@ -2778,6 +2857,7 @@ class _TrainsetBuilder(object):
         self._grow(max(int(rows_hint), 1024))
 
     _COLS = (("pos", "int64"), ("ctg", "int32"), ("truth", "int32"), ("digits", "uint8"), ("centre", "uint8"), ("keep", "uint8"))
+    _REFUSAL = (_TrainsetFallback, "", "a contig token with ':', NUL or a byte >= 0x80")       # how _ContigIds refuses a contig
 
     def _grow(self, cap):
         torch = self.torch
@@ -2790,9 +2870,6 @@ class _TrainsetBuilder(object):
                     cols[k][:self.n].copy_(self.cols[k][:self.n])
         self.x, self.cols, self.cap = x, cols, cap
 
-    def _p(self, t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-
     def add(self, c, x, pos):
         """one batch of GetTensorDevice: its rows behind the ones before, the tokens pass, the run-start tokens compared
         on the host, the join pass"""
@@ -2804,7 +2881,7 @@ class _TrainsetBuilder(object):
             cs = torch.cuda.current_stream(self.device)
             if d["stream"] is not None:
                 cs.wait_stream(d["stream"])
-            st = ctypes.c_void_p(cs.cuda_stream)
+            st = _lib.stream_arg(cs)
             self.x[lo:hi].copy_(x.reshape(c, _NV))
             pieces = pos.pieces()
             if d["merged"]:      # the meta of host-parsed lines: only the host copy holds it
@@ -2813,15 +2890,14 @@ class _TrainsetBuilder(object):
             else:
                 meta_ptr = d["meta_ptr"]
                 idx = None if d["keep"] is None else torch.from_numpy(np.ascontiguousarray(d["keep"], dtype=np.int64)).to(self.device)
-            need = ctypes.c_int64()
-            _lib.check(lib.cv_trainset_tokens_workspace(c, ctypes.byref(need)))
-            ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            need = _lib.workspace(lib.cv_trainset_tokens_workspace, c)
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             flags = torch.empty(c, dtype=torch.uint8, device=self.device)
             run = torch.empty(c, dtype=torch.int32, device=self.device)
             col = {k: v[lo:hi] for k, v in self.cols.items()}
-            _lib.check(lib.cv_trainset_tokens(ctypes.c_void_p(d["text_ptr"]), ctypes.c_void_p(meta_ptr), self._p(idx), c,
-                                              self._p(col["pos"]), self._p(col["digits"]), self._p(col["centre"]), self._p(flags),
-                                              self._p(run), self._p(ws), need.value, st))
+            _lib.check(lib.cv_trainset_tokens(ctypes.c_void_p(d["text_ptr"]), ctypes.c_void_p(meta_ptr), _lib.ptr(idx), c,
+                                              _lib.ptr(col["pos"]), _lib.ptr(col["digits"]), _lib.ptr(col["centre"]), _lib.ptr(flags),
+                                              _lib.ptr(run), _lib.ptr(ws), need, st))
             fl = flags.cpu().numpy()                         # (synchronises: the slab's text may go after this)
             if (fl & (TRAINSET_BAD_COORD | TRAINSET_BAD_SEQ)).any():
                 raise _TrainsetFallback("a coordinate that is not canonical decimal, or a sequence token with ':' / a byte >= 0x80")
@@ -2831,21 +2907,13 @@ class _TrainsetBuilder(object):
             for k, j in enumerate(starts.tolist()):          # a handful per file: the only contig tokens the host reads
                 pc = int(np.searchsorted(first, j, side="right")) - 1
                 buf, m = pieces[pc][2], pieces[pc][3][j - int(first[pc])]
-                name = bytes(buf[m[0]:m[0] + m[1]])
-                if name not in self.ids:
-                    if not contig_token_ok(name):
-                        raise _TrainsetFallback("a contig token with ':', NUL or a byte >= 0x80")
-                    if len(self.names) >= TRAINSET_MAX_CONTIGS:
-                        raise _TrainsetFallback("more than %d contigs" % TRAINSET_MAX_CONTIGS)
-                    self.ids[name] = len(self.names)
-                    self.names.append(name)
-                run_ctg[k] = self.ids[name]
+                run_ctg[k] = self.contigs.id_of(bytes(buf[m[0]:m[0] + m[1]]))
             run_ctg_dev = torch.from_numpy(run_ctg).to(self.device)
             t = self.tab
-            _lib.check(lib.cv_trainset_join(c, self._p(run), self._p(run_ctg_dev), len(starts), self._p(col["pos"]), self.ntab,
-                                            1 if self.has_bed else 0, self._p(t["bed_off"]), self._p(t["bed_begin"]), self._p(t["bed_emax"]),
-                                            self._p(t["truth_off"]) if t["truth_pos"].numel() else None, self._p(t["truth_pos"]),
-                                            self._p(col["ctg"]), self._p(col["keep"]), self._p(col["truth"]), st))
+            _lib.check(lib.cv_trainset_join(c, _lib.ptr(run), _lib.ptr(run_ctg_dev), len(starts), _lib.ptr(col["pos"]), self.ntab,
+                                            1 if self.has_bed else 0, _lib.ptr(t["bed_off"]), _lib.ptr(t["bed_begin"]), _lib.ptr(t["bed_emax"]),
+                                            _lib.ptr(t["truth_off"]) if t["truth_pos"].numel() else None, _lib.ptr(t["truth_pos"]),
+                                            _lib.ptr(col["ctg"]), _lib.ptr(col["keep"]), _lib.ptr(col["truth"]), st))
         self.n = hi
 
     def finish(self, shuffle):
@@ -2853,28 +2921,27 @@ class _TrainsetBuilder(object):
         import time
         torch, lib, n = self.torch, self.lib, self.n
         with torch.cuda.device(self.device):
-            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            st = _lib.stream_arg(self.device)
             rank = torch.from_numpy(contig_ranks(self.names) if self.names else np.zeros(1, np.int32)).to(self.device)
-            need = ctypes.c_int64()
-            _lib.check(lib.cv_trainset_finish_workspace(n, ctypes.byref(need)))
-            ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            need = _lib.workspace(lib.cv_trainset_finish_workspace, n)
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             src = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
             ys = torch.empty((max(n, 1), 16), dtype=torch.float32, device=self.device)
             total_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
             c = self.cols
-            _lib.check(lib.cv_trainset_finish(n, self._p(c["ctg"][:n]), self._p(c["pos"][:n]), self._p(c["digits"][:n]),
-                                              self._p(c["centre"][:n]), self._p(c["keep"][:n]), self._p(c["truth"][:n]),
-                                              self._p(rank), max(len(self.names), 1), self._p(self.tab["labels"]),
-                                              int(self.tab["labels"].shape[0]), self._p(src), self._p(ys), self._p(total_dev),
-                                              self._p(ws), need.value, st))
+            _lib.check(lib.cv_trainset_finish(n, _lib.ptr(c["ctg"][:n]), _lib.ptr(c["pos"][:n]), _lib.ptr(c["digits"][:n]),
+                                              _lib.ptr(c["centre"][:n]), _lib.ptr(c["keep"][:n]), _lib.ptr(c["truth"][:n]),
+                                              _lib.ptr(rank), max(len(self.names), 1), _lib.ptr(self.tab["labels"]),
+                                              int(self.tab["labels"].shape[0]), _lib.ptr(src), _lib.ptr(ys), _lib.ptr(total_dev),
+                                              _lib.ptr(ws), need, st))
             total = int(total_dev.item())
             t0 = time.time()
             perm = torch.from_numpy(np.array(shuffled_indices(total), dtype=np.int64)).to(self.device) if shuffle else None
             t_shuffle = time.time() - t0
             X = torch.empty((total,) + _SHAPE, dtype=torch.float32, device=self.device)
             Y = torch.empty((total, 16), dtype=torch.float32, device=self.device)
-            _lib.check(lib.cv_trainset_gather(self._p(self.x), self._p(ys), self._p(src), self._p(perm), total,
-                                              self._p(X), self._p(Y), st))
+            _lib.check(lib.cv_trainset_gather(_lib.ptr(self.x), _lib.ptr(ys), _lib.ptr(src), _lib.ptr(perm), total,
+                                              _lib.ptr(X), _lib.ptr(Y), st))
             final = src[:total] if perm is None else src[:total][perm]
             key_ctg, key_pos = c["ctg"][:n][final], c["pos"][:n][final]
             torch.cuda.current_stream(self.device).synchronize()
@@ -2937,36 +3004,31 @@ class _BamTrainsetBuilder(_TrainsetBuilder):
     run of one contig; before the finish pass the pairing with non-variants over the rows of all sources"""
 
     _COLS = _TrainsetBuilder._COLS + (("acgt", "uint8"), ("cflag", "uint8"))
+    _REFUSAL = (_lib.CvError, "GetTrainingSetFromBam: ", "contig name {name!r} holds ':', NUL or a byte >= 0x80")
 
     def add_source(self, name, x, col):
         """the c rows CreateTensor would print for one source (ascending position): x [c,33,4,4], col: their columns"""
         torch, lib = self.torch, self.lib
         c = int(x.shape[0])
-        if name not in self.ids:
-            if not contig_token_ok(name):
-                raise _lib.CvError("GetTrainingSetFromBam: contig name %r holds ':', NUL or a byte >= 0x80" % (name,))
-            if len(self.names) >= TRAINSET_MAX_CONTIGS:
-                raise _lib.CvError("GetTrainingSetFromBam: more than %d contigs" % TRAINSET_MAX_CONTIGS)
-            self.ids[name] = len(self.names)
-            self.names.append(name)
+        cid = self.contigs.id_of(name)
         if c == 0:
             return
         if self.n + c > self.cap:
             self._grow(max(2 * self.cap, self.n + c))
         lo, hi = self.n, self.n + c
         with torch.cuda.device(self.device):
-            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            st = _lib.stream_arg(self.device)
             self.x[lo:hi].copy_(x.reshape(c, _NV))
             for k in ("pos", "digits", "centre", "acgt", "cflag"):
                 self.cols[k][lo:hi].copy_(col[k])
             mine = {k: v[lo:hi] for k, v in self.cols.items()}
             run = torch.zeros(c, dtype=torch.int32, device=self.device)
-            run_ctg = torch.tensor([self.ids[name]], dtype=torch.int32, device=self.device)
+            run_ctg = torch.tensor([cid], dtype=torch.int32, device=self.device)
             t = self.tab
-            _lib.check(lib.cv_trainset_join(c, self._p(run), self._p(run_ctg), 1, self._p(mine["pos"]), self.ntab,
-                                            1 if self.has_bed else 0, self._p(t["bed_off"]), self._p(t["bed_begin"]), self._p(t["bed_emax"]),
-                                            self._p(t["truth_off"]) if t["truth_pos"].numel() else None, self._p(t["truth_pos"]),
-                                            self._p(mine["ctg"]), self._p(mine["keep"]), self._p(mine["truth"]), st))
+            _lib.check(lib.cv_trainset_join(c, _lib.ptr(run), _lib.ptr(run_ctg), 1, _lib.ptr(mine["pos"]), self.ntab,
+                                            1 if self.has_bed else 0, _lib.ptr(t["bed_off"]), _lib.ptr(t["bed_begin"]), _lib.ptr(t["bed_emax"]),
+                                            _lib.ptr(t["truth_off"]) if t["truth_pos"].numel() else None, _lib.ptr(t["truth_pos"]),
+                                            _lib.ptr(mine["ctg"]), _lib.ptr(mine["keep"]), _lib.ptr(mine["truth"]), st))
         self.n = hi
 
     def pair(self, seed, amp):
@@ -2975,7 +3037,7 @@ class _BamTrainsetBuilder(_TrainsetBuilder):
         from . import draws
         torch, lib, n = self.torch, self.lib, self.n
         with torch.cuda.device(self.device):
-            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            st = _lib.stream_arg(self.device)
             h = np.array([draws.fnv1a32(nm) for nm in self.names] or [0], dtype=np.uint32).view(np.int32)
             h_dev = torch.from_numpy(h).to(self.device)
             counts = torch.zeros(4, dtype=torch.int64, device=self.device)
@@ -2983,9 +3045,9 @@ class _BamTrainsetBuilder(_TrainsetBuilder):
             c = self.cols
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
             ev[0].record()
-            _lib.check(lib.cv_bamtrain_pair(n, self._p(c["ctg"][:n]), self._p(c["pos"][:n]), self._p(c["cflag"][:n]),
-                                            self._p(c["acgt"][:n]), self._p(h_dev), max(len(self.names), 1), int(seed), float(amp),
-                                            self._p(c["keep"][:n]), self._p(counts), self._p(r), st))
+            _lib.check(lib.cv_bamtrain_pair(n, _lib.ptr(c["ctg"][:n]), _lib.ptr(c["pos"][:n]), _lib.ptr(c["cflag"][:n]),
+                                            _lib.ptr(c["acgt"][:n]), _lib.ptr(h_dev), max(len(self.names), 1), int(seed), float(amp),
+                                            _lib.ptr(c["keep"][:n]), _lib.ptr(counts), _lib.ptr(r), st))
             ev[1].record()
             v, cc, picked, kept = counts.cpu().tolist()
             self.pair_ms = ev[0].elapsed_time(ev[1])
@@ -3441,7 +3503,7 @@ def DecompressArrayDevice(array, start, num, maximum, device=None):
             state = bufs.get("state", ns + 16 + n * 16)     # stream status | lens int64[n] | status int32[n]
             lens_at = (ns + 15) & ~15
             st_at = lens_at + 8 * n
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            stream = _lib.stream_arg(None)
             base = comp.data_ptr()
             _lib.check(lib.cv_blosc_decode_dev(base, comp_bytes, base + tab_at, ns, scratch.data_ptr(), scratch_bytes,
                                                state.data_ptr(), stream))
@@ -3639,7 +3701,7 @@ def pack_blocks_device(X_dev, blocksize=None):
         bufs = _bin_pack_buffers.get(dev.index)
         if bufs is None:
             bufs = _bin_pack_buffers[dev.index] = _BinDecodeBuffers(dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        stream = _lib.stream_arg(None)
         envelopes = {}                                  # per item count: the full chunks' and the partial one's
         for lo, chunks, items in pieces:
             hi = lo + chunks * items
