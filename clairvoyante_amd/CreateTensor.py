@@ -66,7 +66,114 @@ def load_reference(args, refStart, refEnd):
     return seq
 
 
+_CAN_KEYS = ("host_calls", "device_calls", "handed_over_calls", "device_lines")
+_can_counts = dict.fromkeys(_CAN_KEYS, 0)
+CAN_TIMES = None                    # the probe: a dict that receives the milliseconds of the device calls by name (HIP events)
+
+
+def candidate_list_counts(reset=False):
+    """calls of read_candidates per side so far, the calls the device route began and gave to the host loop, and the lines
+    the device read"""
+    out = dict(_can_counts)
+    if reset:
+        _can_counts.update(dict.fromkeys(_CAN_KEYS, 0))
+    return out
+
+
+def candidate_list_route(can_fn):
+    """"host" or "device": CV_CANDIDATE_LIST when it is set (any other value raises), else the host; PIPE and a run
+    without a GPU are always "host" """
+    import os
+    forced = os.environ.get("CV_CANDIDATE_LIST")
+    if forced not in (None, "", "host", "device"):
+        raise ValueError("CV_CANDIDATE_LIST must be 'host' or 'device', got %r" % forced)
+    if forced != "device" or can_fn == "PIPE":
+        return "host"
+    from .utils_v2 import _gpu_present
+    return "device" if _gpu_present() else "host"
+
+
 def read_candidates(args, ctgStart, ctgEnd):
+    """GetCandidate :56-62: 1-based positions of this contig inside [ctgStart, ctgEnd], ascending and unique -- by the
+    host loop read_candidates_host (the definition), or with CV_CANDIDATE_LIST=device by the device's line pass
+    (read_candidates_device), which hands the whole call to the host loop when it meets a line it does not vouch for"""
+    if candidate_list_route(args.can_fn) == "device":
+        from .utils_v2 import _TruthHandOver
+        try:
+            got = read_candidates_device(args, ctgStart, ctgEnd)
+            _can_counts["device_calls"] += 1
+            return got
+        except _TruthHandOver:
+            _can_counts["handed_over_calls"] += 1
+    _can_counts["host_calls"] += 1
+    return read_candidates_host(args, ctgStart, ctgEnd)
+
+
+def read_candidates_device(args, ctgStart, ctgEnd, device=None):
+    """read_candidates on the device: the file in slabs through utils_v2._SlabWalk (plain text memory-mapped, BGZF
+    inflated on the device, an ordinary .gz inflated natively on the host), cv_item_lines_dev for position, contig run
+    and the run-start tokens, which the host compares with --ctgName; the positions of the contig's runs inside the
+    bounds are kept on the device, sorted and made unique there.  Raises utils_v2._TruthHandOver for a file or a line
+    only the host loop answers (a blank line, one token, "007", "+5", "1_0", '\\r', a byte outside printable ASCII)."""
+    import ctypes
+    import torch
+    from . import _lib, utils_v2
+    from .utils_v2 import _SlabWalk, _TruthHandOver, _TruthReader, _truth_chunks, _while_table_full
+    device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+    name = args.ctgName.encode()
+    kept = []
+    with torch.cuda.device(device):
+        rd = _TruthReader(device)
+        lib, st, P = rd.lib, _lib.stream_arg(device), _lib.ptr
+        E = lambda n, dt=torch.int64: torch.empty(n, dtype=dt, device=device)
+        state = {"bytes_per_line": 16.0}
+
+        def slab(buf, lo, hi, _padded_end):
+            def line_pass(at, n, max_lines):
+                need = _lib.workspace(lib.cv_item_lines_workspace, n, max_lines)
+                ws = E(need, torch.uint8)
+                pos, run, off, ln = E(max_lines), E(max_lines, torch.int32), E(max_lines), E(max_lines)
+                tok, info_dev = E((max_lines, 2)), E(8)
+                if CAN_TIMES is not None:
+                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                    ev[0].record()
+                _lib.check(lib.cv_item_lines_dev(ctypes.c_void_p(buf.data_ptr() + at), n, max_lines, P(pos), P(run), P(off), P(ln),
+                                                 P(tok), P(info_dev), P(ws), need, st))
+                if CAN_TIMES is not None:
+                    ev[1].record()
+                used, lines, rows, _skipped, host, runs = info_dev.cpu().tolist()[:6]
+                if CAN_TIMES is not None:
+                    CAN_TIMES["lines"] = CAN_TIMES.get("lines", 0.0) + ev[0].elapsed_time(ev[1])
+                if host:
+                    raise _TruthHandOver("%d line(s) only the host loop defines the result for" % host)
+                if rows:
+                    # which runs are the contig's: the host compares their start tokens
+                    mine = [t == name for t in rd.run_names(buf, at, n, tok, runs)]
+                    if any(mine):
+                        p = pos[:rows]
+                        keep = torch.tensor(mine, dtype=torch.bool, device=device)[run[:rows].long()]
+                        if ctgStart is not None:
+                            keep &= p >= ctgStart
+                        if ctgEnd is not None:
+                            keep &= p <= ctgEnd
+                        kept.append(p[keep])
+                _can_counts["device_lines"] += lines
+                if lines:
+                    state["bytes_per_line"] = max(used / float(lines), 2.0)
+                return used, lines
+
+            return _while_table_full(lo, hi, lambda n: min(int(n / state["bytes_per_line"] * 1.25) + 1024, n), line_pass)
+
+        slab_bytes = max(int(utils_v2.TRUTH_SLAB_BYTES), 1)
+        walk = _SlabWalk(torch, device, _truth_chunks(args.can_fn, slab_bytes), slab_bytes, rd._inflate, pad_always=False,
+                         join_unbroken=True, whole_lines=True)
+        walk.run(slab)
+        if not kept:
+            return np.zeros(0, dtype=np.int64)
+        return torch.unique(torch.cat(kept), sorted=True).cpu().numpy()
+
+
+def read_candidates_host(args, ctgStart, ctgEnd):
     """GetCandidate :56-62: 1-based positions of this contig inside [ctgStart, ctgEnd]"""
     if args.can_fn != "PIPE":
         f = subprocess.Popen(shlex.split("gzip -fdc %s" % args.can_fn), stdout=subprocess.PIPE, bufsize=8388608)

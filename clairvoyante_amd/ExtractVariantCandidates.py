@@ -11,7 +11,9 @@ reference recommends for this script, and of CPython >= 3.7).  Rows come in the 
 positions before the last read's POS ascending, then its final loop (:215-241).  --gen4Training
 subsamples with an unseeded RNG exactly like the reference (:203-205) and is therefore not reproducible;
 with --seed N (not in the reference) the rows are kept by the keyed draws of clairvoyante_amd/draws.py instead: the
-same rows for the same seed, whatever the order.
+same rows for the same seed, whatever the order.  With --bgzf (not in the reference either) --can_fn is written as BGZF
+members, the same bytes once inflated.  CV_CANDIDATE_ROWS=device makes the rows in HBM (csrc/cv_candrows_dev.hip, opt-in):
+the same bytes, the host loop candidate_rows stays the definition.
 """
 import os
 import random
@@ -26,7 +28,7 @@ if __package__ in (None, ""):      # run as `python <dir>/ExtractVariantCandidat
     _sys.path[0] = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
     import clairvoyante_amd  # noqa: F401
     __package__ = "clairvoyante_amd"
-from . import param
+from . import param, pileup
 from .CreateTensor import READ_CHUNK, load_reference, region_of
 from .pileup import Pileup
 
@@ -111,7 +113,52 @@ def stream_alignments(args, pl, ctgStart, ctgEnd, source=None):
         pl.add_sam(chunk)
 
 
+def candidate_row_counts(reset=False):
+    """rows MakeCandidates wrote since the start (or the last reset) per side: {"host": n, "device": n} -- the host loop
+    candidate_rows, or the kernels of csrc/cv_candrows_dev.hip (a batch the device hands back counts as the host's)"""
+    return pileup.candidate_row_counts(reset)
+
+
+def candidate_rows_route(args):
+    """"host" or "device" for this run: CV_CANDIDATE_ROWS (pileup.candidate_rows_route; any value but host / device
+    raises, no GPU is "host"); --gen4Training without --seed stays on the host loop whatever the switch says, because
+    Python's unseeded generator is consumed in row order"""
+    route = pileup.candidate_rows_route()
+    if args.gen4Training and getattr(args, "seed", None) is None:
+        return "host"
+    return route
+
+
+class _CandidateOutput(object):
+    """--can_fn: standard output for PIPE, BGZF members with --bgzf (utils_v2.BgzfWriter), else the `gzip -c` child"""
+
+    def __init__(self, args):
+        self.fpo = self.fp = self.bgzf = None
+        if args.can_fn == "PIPE":
+            self.out = sys.stdout.buffer
+        elif getattr(args, "bgzf", False):
+            from .utils_v2 import BgzfWriter
+            self.out = self.bgzf = BgzfWriter(args.can_fn)
+        else:
+            self.fpo = open(args.can_fn, "wb")
+            self.fp = subprocess.Popen(shlex.split("gzip -c"), stdin=subprocess.PIPE, stdout=self.fpo, stderr=sys.stderr,
+                                       bufsize=8388608)
+            self.out = self.fp.stdin
+
+    def close(self):
+        if self.bgzf is not None:
+            self.bgzf.close()
+        elif self.fp is not None:
+            self.fp.stdin.close()
+            self.fp.wait()
+            self.fpo.close()
+        else:
+            self.out.flush()
+
+
 def MakeCandidates(args):
+    """-> the rows written: their list (str, without newlines) on the host route, their NUMBER on the device route
+    (CV_CANDIDATE_ROWS=device: the rows are made in HBM and never exist as Python strings)"""
     if args.gen4Training:
         args.minCoverage = 0
         args.threshold = 0
@@ -119,6 +166,7 @@ def MakeCandidates(args):
     if not os.path.isfile("%s.fai" % args.ref_fn):
         sys.stderr.write("Fasta index %s.fai doesn't exist.\n" % args.ref_fn)
         sys.exit(1)
+    route = candidate_rows_route(args)
     ctgStart, ctgEnd, refStart, refEnd = region_of(args)
     ref_seq = load_reference(args, refStart, refEnd)
     shift = 0 if refStart is None else refStart - 1
@@ -126,33 +174,39 @@ def MakeCandidates(args):
     pl = Pileup(evc=True, evc_minMQ=args.minMQ, contig=args.ctgName, minMQ=1 << 30)   # tensor pass switched off
     pl.set_reference(ref_seq, shift)
     stream_alignments(args, pl, ctgStart, ctgEnd)
-    res = pl.extract_candidates(args.threshold, args.minCoverage, (ctgStart, ctgEnd) if ctgStart is not None else None, bed)
-    pl.close()
-    rows = candidate_rows(args.ctgName, res, ref_seq, shift)
-    if args.gen4Training and getattr(args, "seed", None) is not None:
-        from . import draws
-        order = candidate_order(res)                                    # row k is entry order[k]
-        u = draws.draws(draws.resolve_seed(args.seed, "ExtractVariantCandidates"), draws.SAMPLE, args.ctgName,
-                        res["pos0"][order] + 1, res["late"][order])
-        rows = [r for r, ui in zip(rows, u) if not ui > args.outputProb]
-    elif args.gen4Training:
-        rows = [r for r in rows if not random.uniform(0, 1) > args.outputProb]
-    if args.can_fn != "PIPE":
-        fpo = open(args.can_fn, "wb")
-        fp = subprocess.Popen(shlex.split("gzip -c"), stdin=subprocess.PIPE, stdout=fpo, stderr=sys.stderr, bufsize=8388608)
-        out = fp.stdin
+    region = (ctgStart, ctgEnd) if ctgStart is not None else None
+    if route == "device":
+        # the selection stays in HBM (with --gen4Training --seed only the entries the keyed draws keep), the order and the
+        # text are made there; what comes to the host is one block of bytes per batch
+        if args.gen4Training:
+            from . import draws
+            pl.sample_candidates(draws.resolve_seed(args.seed, "ExtractVariantCandidates"), args.outputProb, region, bed)
+        else:
+            pl.select_candidates(args.threshold, args.minCoverage, region, bed)
+        res = pl.selected_device()
+        rows = int(res["pos0"].numel())
+        out = _CandidateOutput(args)
+        for block in pileup.candidate_row_blocks(args.ctgName, res, ref_seq, shift, candidate_rows):
+            out.out.write(block)
+        pl.close()
     else:
-        fpo = fp = None
-        out = sys.stdout.buffer
-    for r in rows:
-        out.write(r.encode())
-        out.write(b"\n")
-    if fp is not None:
-        fp.stdin.close()
-        fp.wait()
-        fpo.close()
-    else:
-        out.flush()
+        res = pl.extract_candidates(args.threshold, args.minCoverage, region, bed)
+        pl.close()
+        rows = candidate_rows(args.ctgName, res, ref_seq, shift)
+        if args.gen4Training and getattr(args, "seed", None) is not None:
+            from . import draws
+            order = candidate_order(res)                                    # row k is entry order[k]
+            u = draws.draws(draws.resolve_seed(args.seed, "ExtractVariantCandidates"), draws.SAMPLE, args.ctgName,
+                            res["pos0"][order] + 1, res["late"][order])
+            rows = [r for r, ui in zip(rows, u) if not ui > args.outputProb]
+        elif args.gen4Training:
+            rows = [r for r in rows if not random.uniform(0, 1) > args.outputProb]
+        out = _CandidateOutput(args)
+        for r in rows:
+            out.out.write(r.encode())
+            out.out.write(b"\n")
+        pileup._cand_row_counts["host"] += len(rows)
+    out.close()
     if res["reads"] == 0:
         sys.stderr.write("No read has been process, either the genome region you specified has no read cover, or please "
                          "check the correctness of your BAM input (%s).\n" % args.bam_fn)
@@ -191,6 +245,9 @@ def build_parser():
     parser.add_argument("--gen4Training", type=param.str2bool, nargs="?", const=True, default=False,
                         help="Output all genome positions as candidate for model training (Set --threshold to 0, "
                              "--minCoverage to 0), default: %(default)s")
+    parser.add_argument("--bgzf", type=param.str2bool, nargs="?", const=True, default=False,
+                        help="Write --can_fn as BGZF (independent gzip members, as bgzip writes them; any gzip reads it, "
+                             "CreateTensor inflates it on the GPU) instead of through `gzip -c`, default: %(default)s")
     return parser
 
 

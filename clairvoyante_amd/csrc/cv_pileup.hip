@@ -1189,12 +1189,13 @@ static int fetch_selected(cv_pileup *p, hipStream_t st)
     return 0;
 }
 
-extern "C" int cv_pileup_extract_candidates(cv_pileup *p, double threshold, double min_coverage, int has_region,
-                                            int64_t ctg_start, int64_t ctg_end, const int64_t *bed_begin,
-                                            const int64_t *bed_end, int64_t nbed, void *stream, int64_t *n_out)
+// the select of cv_pileup_extract_candidates / cv_pileup_select_candidates: the entries stay in sel_dev / nsel_dev
+static int evc_select(const char *who, cv_pileup *p, double threshold, double min_coverage, int has_region, int64_t ctg_start,
+                      int64_t ctg_end, const int64_t *bed_begin, const int64_t *bed_end, int64_t nbed, void *stream,
+                      int64_t *n_out)
 {
-    if (!p || !n_out) { cv_set_error("cv_pileup_extract_candidates: null argument"); return 1; }
-    if (!p->evc) { cv_set_error("cv_pileup_extract_candidates: option 'evc' was not set"); return 1; }
+    if (!p || !n_out) { cv_set_error("%s: null argument", who); return 1; }
+    if (!p->evc) { cv_set_error("%s: option 'evc' was not set", who); return 1; }
     if (cv_pileup_flush(p, stream)) return 1;
     CV_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
@@ -1206,10 +1207,62 @@ extern "C" int cv_pileup_extract_candidates(cv_pileup *p, double threshold, doub
     if (bed_upload(bed, bed_begin, bed_end, nbed)) return 1;
     evc_pred pred{p->pos_cnt, p->ref_dev, p->ref_first, threshold, min_coverage, has_region, ctg_start, ctg_end,
                   bed.bb, bed.be, bed.n};
-    if (select_entries(p, pred, st) || fetch_selected(p, st)) return 1;
-    hipFree(p->sel_dev); p->sel_dev = nullptr;             // (this route works from the host copy)
+    if (select_entries(p, pred, st)) return 1;
     *n_out = p->nsel_dev;
+    return 0;
+}
+
+extern "C" int cv_pileup_extract_candidates(cv_pileup *p, double threshold, double min_coverage, int has_region,
+                                            int64_t ctg_start, int64_t ctg_end, const int64_t *bed_begin,
+                                            const int64_t *bed_end, int64_t nbed, void *stream, int64_t *n_out)
+{
+    if (evc_select("cv_pileup_extract_candidates", p, threshold, min_coverage, has_region, ctg_start, ctg_end, bed_begin,
+                   bed_end, nbed, stream, n_out)) return 1;
+    if (!p->sel_dev) return 0;
+    if (fetch_selected(p, (hipStream_t)stream)) return 1;
+    hipFree(p->sel_dev); p->sel_dev = nullptr;             // (this route works from the host copy)
     p->nsel_dev = 0;
+    return 0;
+}
+
+extern "C" int cv_pileup_select_candidates(cv_pileup *p, double threshold, double min_coverage, int has_region,
+                                           int64_t ctg_start, int64_t ctg_end, const int64_t *bed_begin,
+                                           const int64_t *bed_end, int64_t nbed, void *stream, int64_t *n_out)
+{
+    if (evc_select("cv_pileup_select_candidates", p, threshold, min_coverage, has_region, ctg_start, ctg_end, bed_begin,
+                   bed_end, nbed, stream, n_out)) return 1;
+    p->sel_host_stale = p->sel_dev != nullptr;
+    return 0;
+}
+
+__global__ void evc_entries(const int64_t *__restrict__ sel, int64_t n, int64_t ref_first, int64_t *__restrict__ pos0,
+                            int32_t *__restrict__ late)
+{
+    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const int64_t j = sel[t];
+    if (pos0) pos0[t] = ref_first + (j >> 1);
+    if (late) late[t] = (int32_t)(j & 1);
+}
+
+extern "C" int cv_pileup_selected_dev(cv_pileup *p, int64_t *pos0_dev, int32_t *late_dev, int32_t *counts7_dev, int64_t info[2],
+                                      void *stream)
+{
+    if (!p) { cv_set_error("cv_pileup_selected_dev: null handle"); return 1; }
+    if (info) { info[0] = p->evc_reads; info[1] = p->evc_prev_pos; }
+    const int64_t n = p->sel_dev ? p->nsel_dev : 0;
+    if (n == 0) return 0;
+    CV_HIP(hipSetDevice(p->device));
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    if (pos0_dev || late_dev) {
+        evc_entries<<<blocks, 256, 0, st>>>(p->sel_dev, n, p->ref_first, pos0_dev, late_dev);
+        CV_HIP(hipGetLastError());
+    }
+    if (counts7_dev) {
+        evc_gather<<<blocks, 256, 0, st>>>(p->sel_dev, n, p->pos_cnt, counts7_dev);
+        CV_HIP(hipGetLastError());
+    }
     return 0;
 }
 

@@ -263,6 +263,33 @@ class Pileup(object):
         self._nsel = n.value
         return n.value
 
+    def select_candidates(self, threshold=0.125, minCoverage=4, region=None, bed=None):
+        """extract_candidates' selection with the entries left in HBM (as sample_candidates leaves them) -> their number;
+        selected_device() gathers them there, extracted() fetches them"""
+        if self._tail:
+            self.add_sam(b"", final=True)
+        n = ctypes.c_int64(0)
+        bb, be, nbed = self._bed_arrays(bed)
+        _lib.check(self.lib.cv_pileup_select_candidates(
+            self.h, float(threshold), float(minCoverage), int(region is not None), int(region[0]) if region else 0,
+            int(region[1]) if region else 0, bb.ctypes.data_as(ctypes.c_void_p), be.ctypes.data_as(ctypes.c_void_p), nbed,
+            self._stream(), ctypes.byref(n)))
+        self._nsel = n.value
+        return n.value
+
+    def selected_device(self):
+        """the entries of the last select_candidates() / sample_candidates() as device tensors, nothing fetched:
+        dict(pos0 int64 [n], late int32 [n], counts int32 [n,7], reads, last_pos)"""
+        import torch
+        k = self._nsel
+        with torch.cuda.device(self.device):
+            pos0 = torch.empty(k, dtype=torch.int64, device=self.device)
+            late = torch.empty(k, dtype=torch.int32, device=self.device)
+            c7 = torch.empty((k, 7), dtype=torch.int32, device=self.device)
+            info = (ctypes.c_int64 * 2)()
+            _lib.check(self.lib.cv_pileup_selected_dev(self.h, _lib.ptr(pos0), _lib.ptr(late), _lib.ptr(c7), info, self._stream()))
+        return {"pos0": pos0, "late": late, "counts": c7, "reads": info[0], "last_pos": info[1]}
+
     def extracted(self):
         """the entries of the last extract_candidates() / sample_candidates(): dict(pos0, late, counts [n,7] in
         A,C,G,T,I,D,N order, reads, last_pos)"""
@@ -469,3 +496,130 @@ def format_row_blocks(ctg, centers, ref_seq, ref_shift, tensors, batch=ROWTEXT_B
         for row in rows:
             yield row
             yield b"\n"
+
+
+# ---- ExtractVariantCandidates' rows written on the device (csrc/cv_candrows_dev.hip) ------------------------------------
+# CV_CANDIDATE_ROWS=device selects the route; unset or "host" is the host loop (ExtractVariantCandidates.candidate_rows,
+# the definition).  The route is opt-in: profiles/r21/candidate_list_device.txt holds what was measured, no floor follows
+# from it yet.
+CANDROWS_BATCH = 32768          # rows per block of text
+CANDROWS_TIMES = None           # the probe: a dict that receives the milliseconds of the device calls by name (HIP events)
+_cand_row_counts = {"host": 0, "device": 0}
+
+
+def candidate_row_counts(reset=False):
+    """candidate rows formatted since the start (or the last reset) per side: {"host": n, "device": n}"""
+    out = dict(_cand_row_counts)
+    if reset:
+        _cand_row_counts["host"] = _cand_row_counts["device"] = 0
+    return out
+
+
+def candidate_rows_route():
+    """"host" or "device": CV_CANDIDATE_ROWS when it is set (any other value raises), else the host; always "host"
+    without a GPU"""
+    forced = os.environ.get("CV_CANDIDATE_ROWS")
+    if forced not in (None, "", "host", "device"):
+        raise ValueError("CV_CANDIDATE_ROWS must be 'host' or 'device', got %r" % forced)
+    if forced != "device":
+        return "host"
+    import torch
+    return "device" if torch.cuda.is_available() else "host"
+
+
+class _CandTimer(object):
+    """HIP events around device calls when CANDROWS_TIMES is a dict; read() behind the caller's next synchronisation"""
+
+    def __init__(self, torch, name):
+        self.name, self.on = name, CANDROWS_TIMES is not None
+        if self.on:
+            self.a, self.b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            self.a.record()
+
+    def stop(self):
+        if self.on:
+            self.b.record()
+
+    def read(self):
+        if self.on:
+            self.b.synchronize()
+            CANDROWS_TIMES[self.name] = CANDROWS_TIMES.get(self.name, 0.0) + self.a.elapsed_time(self.b)
+
+
+def candidate_order_device(sel):
+    """candidate_order on the device: sel = Pileup.selected_device() -> int64 tensor of the entry indices in the
+    reference's output order"""
+    import torch
+    lib = _lib.load()
+    pos0, late = sel["pos0"], sel["late"]
+    n, dev = int(pos0.numel()), pos0.device
+    with torch.cuda.device(dev):
+        order = torch.empty(n, dtype=torch.int64, device=dev)
+        need = _lib.workspace(lib.cv_candidate_order_workspace, n)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        tm = _CandTimer(torch, "order")
+        _lib.check(lib.cv_candidate_order_dev(_lib.ptr(pos0), _lib.ptr(late), n, int(sel["last_pos"]), _lib.ptr(order),
+                                              ctypes.c_void_p(ws.data_ptr()), need, _lib.stream_arg(dev)))
+        tm.stop()
+        torch.cuda.current_stream(dev).synchronize()        # (the workspace may go)
+        tm.read()
+    return order
+
+
+def candidate_row_blocks(ctg, sel, ref_seq, ref_shift, host_rows, batch=None):
+    """the rows of ExtractVariantCandidates for the entries sel = Pileup.selected_device(), in the reference's order:
+    yields, per batch of at most CANDROWS_BATCH rows, ONE block of bytes -- the rows, each followed by "\\n" -- through one
+    pinned copy.  ref_seq bytes / str: the loaded reference, ref_seq[0] at 0-based position ref_shift.  A batch with a row
+    the device does not vouch for (cv_candidate_rows_dev: status CV_CANDROWS_HOST) is formatted whole by
+    host_rows(ctg, res, ref_seq, ref_shift) -> list of str (ExtractVariantCandidates.candidate_rows) from a fetch of just
+    that batch's entries; candidate_row_counts() tells which side took what."""
+    import torch
+    lib = _lib.load()
+    batch = int(batch if batch is not None else CANDROWS_BATCH)
+    pos0, late, c7 = sel["pos0"], sel["late"], sel["counts"]
+    k, dev = int(pos0.numel()), pos0.device
+    if k == 0:
+        return
+    cb = ctg.encode()
+    host_ref = ref_seq.encode() if isinstance(ref_seq, str) else bytes(ref_seq)
+    with torch.cuda.device(dev):
+        order = candidate_order_device(sel)
+        ref_dev = torch.frombuffer(bytearray(host_ref) or bytearray(1), dtype=torch.uint8).to(dev)[:len(host_ref)]
+        ref_len = int(ref_dev.numel())
+        need = _lib.workspace(lib.cv_candidate_rows_workspace, min(batch, k))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        stream = _lib.stream_arg(dev)
+        P = _lib.ptr
+        for s in range(0, k, batch):
+            n = min(batch, k - s)
+            off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            status = torch.empty(n, dtype=torch.uint8, device=dev)
+
+            def call(text, cap):
+                _lib.check(lib.cv_candidate_rows_dev(cb, len(cb), ctypes.c_void_p(order.data_ptr() + 8 * s), n, k, P(pos0), P(late),
+                                                     P(c7), P(ref_dev), int(ref_shift), ref_len, P(off), P(status), text, cap,
+                                                     ctypes.c_void_p(ws.data_ptr()), need, stream))
+            tm = _CandTimer(torch, "lengths")
+            call(None, 0)                                   # lengths and status: the text is sized exactly
+            tm.stop()
+            total, host_n = (int(v) for v in torch.stack((off[n], status.sum(dtype=torch.int64))).tolist())
+            tm.read()
+            if host_n:
+                idx = order[s:s + n]
+                res = {"pos0": pos0[idx].cpu().numpy(), "late": late[idx].cpu().numpy(), "counts": c7[idx].cpu().numpy(),
+                       "last_pos": sel["last_pos"]}     # (already in output order: candidate_order leaves it as it is)
+                rows = host_rows(ctg, res, host_ref, ref_shift)
+                _cand_row_counts["host"] += n
+                rows.append("")
+                yield "\n".join(rows).encode()
+                continue
+            text = torch.empty(total, dtype=torch.uint8, device=dev)
+            tm = _CandTimer(torch, "rows")
+            call(P(text), total)
+            tm.stop()
+            pin = _pinned_bytes(total)
+            pin[:total].copy_(text, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+            tm.read()
+            _cand_row_counts["device"] += n
+            yield pin.numpy()[:total].tobytes()

@@ -852,6 +852,48 @@ int cv_tensor_rows_text_dev(const char *ctg, int64_t ctg_len, const int64_t *cen
                             int64_t *off_dev, uint8_t *status_dev, char *text_dev, int64_t text_cap,
                             void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The rows of ExtractVariantCandidates.py written in HBM (csrc/cv_candrows_dev.hip, cv_candrows_core.hpp); the host loop
+ * candidate_rows of clairvoyante_amd/ExtractVariantCandidates.py stays the definition.
+ *
+ * cv_pileup_select_candidates: cv_pileup_extract_candidates' predicate and arguments, but the entries stay in HBM (as
+ *   cv_pileup_sample_candidates leaves them) and only *n_out comes back; cv_pileup_get_extracted fetches them when asked.
+ * cv_pileup_selected_dev: the n_out resident entries of the last cv_pileup_select_candidates / _sample_candidates gathered
+ *   into the caller's device arrays (any may be NULL): pos0_dev[n] int64 0-based position, late_dev[n] int32, counts7_dev
+ *   [n,7] int32 in A,C,G,T,I,D,N order; info (host) as cv_pileup_get_extracted fills it.  Nothing is copied to the host.
+ * cv_candidate_order_dev: order_dev[n] int64 = the reference's output order of n ascending entries (candidate_order): the
+ *   indices of the entries with late == 0 and pos0 < last_pos, ascending, then those of all others, ascending.
+ * cv_candidate_rows_dev: output row r < rows is entry e = order_dev[r] (order_dev NULL: e = r) of the n entries:
+ *     "<ctg> <pos0[e] + 1> <ref byte> <total> <S1> <c1> ... <S7> <c7>\n"
+ *   total = the seven counts summed in 64 bits, the pairs by descending count, ties in the order A,C,G,T,I,D,N; the byte
+ *   is ref_dev[pos0[e] - ref_first0] as it is.  The rows stand end to end at text_dev + off_dev[r]; off_dev[rows + 1]
+ *   int64, off_dev[rows] = bytes in all.  text_dev = NULL: lengths and status only.  A row that would end behind text_cap
+ *   is not written; nothing behind off_dev[rows] is.  The device vouches for a row only if e lies in [0, n), the position
+ *   in [0, 2^63 - 2] and inside the window [ref_first0, ref_first0 + ref_len), the byte is below 0x80 and no count is
+ *   negative: any other row gets status_dev[r] = CV_CANDROWS_HOST and length 0; a contig name of more than 255 bytes makes
+ *   every row CV_CANDROWS_HOST.  late_dev is not read (a late entry differs in its counts alone) and may be NULL.  ctg is
+ *   host memory; order / pos0 / off 8-byte, counts7 4-byte, the workspace 256-byte aligned; at most 2^30 rows and entries.
+ * cv_candidate_rows_host_form: the same core on the CPU over HOST pointers.
+ * The _dev calls are asynchronous on `stream`: no allocation, no synchronisation.                                      */
+#define CV_CANDROWS_DEVICE 0
+#define CV_CANDROWS_HOST 1
+int cv_pileup_select_candidates(cv_pileup *p, double threshold, double min_coverage, int has_region, int64_t ctg_start,
+                                int64_t ctg_end, const int64_t *bed_begin, const int64_t *bed_end, int64_t nbed,
+                                void *stream, int64_t *n_out);
+int cv_pileup_selected_dev(cv_pileup *p, int64_t *pos0_dev, int32_t *late_dev, int32_t *counts7_dev, int64_t info[2],
+                           void *stream);
+int cv_candidate_order_workspace(int64_t n, int64_t *bytes);
+int cv_candidate_order_dev(const int64_t *pos0_dev, const int32_t *late_dev, int64_t n, int64_t last_pos, int64_t *order_dev,
+                           void *workspace, int64_t workspace_bytes, void *stream);
+int cv_candidate_rows_workspace(int64_t rows, int64_t *bytes);
+int cv_candidate_rows_dev(const char *ctg, int64_t ctg_len, const int64_t *order_dev, int64_t rows, int64_t n,
+                          const int64_t *pos0_dev, const int32_t *late_dev, const int32_t *counts7_dev,
+                          const uint8_t *ref_dev, int64_t ref_first0, int64_t ref_len, int64_t *off_dev, uint8_t *status_dev,
+                          char *text_dev, int64_t text_cap, void *workspace, int64_t workspace_bytes, void *stream);
+int cv_candidate_rows_host_form(const char *ctg, int64_t ctg_len, const int64_t *order, int64_t rows, int64_t n,
+                                const int64_t *pos0, const int32_t *late, const int32_t *counts7, const uint8_t *ref,
+                                int64_t ref_first0, int64_t ref_len, int64_t *off, uint8_t *status, char *text,
+                                int64_t text_cap);
+
 /* callVarBam's columns written in HBM (csrc/cv_callcols_dev.hip, cv_callcols_core.hpp): which of the n candidate centres
  * give a row for the call loop, and the tokens of those rows.  Centre i (1-based, ri = centre - 1 - ref_first inside
  * the reference bytes ref[0, ref_len) whose first byte is 0-based position ref_first >= 0) is kept iff touched[i], ri - 16
