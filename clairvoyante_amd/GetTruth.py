@@ -5,7 +5,8 @@
 
 Row: "<ctg> <pos> <ref> <alt> <gt1> <gt2>"; the genotype comes from the last column, a 1/2 call with several
 ALT alleles is reduced to 0/1 on the shortest ALT (:66-76).  Uses `tabix` for a region when the VCF has an
-index and tabix is installed, otherwise streams the file through `gzip -fdc` (:45-51).
+index and tabix is installed, otherwise streams the file through `gzip -fdc` (:45-51); where the index is there and
+the binary is not, the region's lines come through the index all the same (vcf_merge.fetch).
 """
 import argparse
 import os
@@ -46,8 +47,38 @@ def open_vcf(vcf_fn, ctgName, ctgStart, ctgEnd):
             return subprocess.Popen(shlex.split("tabix -f -p vcf %s %s:%s-%s" % (vcf_fn, ctgName, ctgStart, ctgEnd)),
                                     stdout=subprocess.PIPE, bufsize=8388608)
         except subprocess.CalledProcessError:
-            pass
+            got = _fetch_stream(vcf_fn, ctgName, ctgStart, ctgEnd)
+            if got is not None:
+                return got
     return subprocess.Popen(shlex.split("gzip -fdc %s" % vcf_fn), stdout=subprocess.PIPE, bufsize=8388608)
+
+
+class _Lines(object):
+    """lines in the shape of a finished child process: .stdout iterates them, close() and wait() do nothing"""
+
+    def __init__(self, lines):
+        self.stdout = self
+        self.lines = lines
+
+    def __iter__(self):
+        return iter(self.lines)
+
+    def close(self):
+        pass
+
+    def wait(self):
+        return 0
+
+
+def _fetch_stream(vcf_fn, ctgName, ctgStart, ctgEnd):
+    """the region's lines through VCF.tbi without the tabix binary (vcf_merge.fetch: only the BGZF members the index
+    names are inflated); None when the index or the file does not read cleanly -- the caller then streams the whole file"""
+    from . import vcf_merge
+    try:
+        index = vcf_merge.TabixIndex.read("%s.tbi" % vcf_fn)
+        return _Lines(list(vcf_merge.fetch(vcf_fn, ctgName, ctgStart - 1, ctgEnd, index=index)))
+    except Exception:
+        return None
 
 
 def OutputVariant(args):

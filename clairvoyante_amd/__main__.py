@@ -8,7 +8,7 @@ import sys
 SUBMODULES = ("callVarBamParallel", "callVarBam", "callVar", "calTrainDevDiff", "evaluateListOfModels", "evaluate",
               "tensor2Bin", "trainNonstop", "train", "trainWithoutValidationNonstop", "CreateTensor",
               "ExtractVariantCandidates", "GetTruth", "PairWithNonVariants", "ChooseItemInBed", "CountNumInBed",
-              "RandomSampling", "CombineMultipleDatasetsForTraining")
+              "RandomSampling", "CombineMultipleDatasetsForTraining", "MergeVcf")
 NOT_BUILT = ("demoRun", "getEmbedding", "getTensorAndLayerPNG")
 
 

@@ -4,7 +4,9 @@ per reference chunk (default 10 Mbp) of every major contig in REF.fai, skipping 
 interval -- plus `--run`, which executes the chunks here instead of printing them: one process per GPU
 (`torchrun --nproc-per-node N -m clairvoyante_amd.callVarBamParallel --run ...`), chunk k goes to rank
 k mod N, the model is loaded once per rank, no collective is needed (chunks are independent; the
-per-chunk VCFs are concatenated afterwards exactly as with the reference, README.md:197).
+per-chunk VCFs are concatenated afterwards exactly as with the reference, README.md:197).  `--merged_fn
+OUT.vcf.gz` does that last step here: rank 0 merges the chunk files into one sorted, tabix-indexed VCF
+(vcf_merge.py), behind one all-reduce of a failure flag when there are several ranks.
 """
 import argparse
 import os
@@ -118,16 +120,51 @@ def Run(args):
         if not (a.ctgStart is not None and a.ctgEnd is not None and int(a.ctgStart) <= int(a.ctgEnd)):
             a.ctgStart = a.ctgEnd = None
     depth = max(1, int(args.prefetch))
-    with ThreadPoolExecutor(max_workers=depth) as pool:
-        pending = [pool.submit(fetch, a) for a in jobs[:depth]]
-        for i, a in enumerate(jobs):
-            text = pending[i].result()
-            pending[i] = None
-            if i + depth < len(jobs):
-                pending.append(pool.submit(fetch, jobs[i + depth]))
-            callVarBam.Run(a, model=m, source=text)
+    failure = None
+    try:
+        with ThreadPoolExecutor(max_workers=depth) as pool:
+            pending = [pool.submit(fetch, a) for a in jobs[:depth]]
+            for i, a in enumerate(jobs):
+                text = pending[i].result()
+                pending[i] = None
+                if i + depth < len(jobs):
+                    pending.append(pool.submit(fetch, jobs[i + depth]))
+                callVarBam.Run(a, model=m, source=text)
+    except BaseException as e:
+        if args.merged_fn is None or ws <= 1:
+            raise
+        failure = e                    # (--merged_fn under ranks: the others must not wait for a rank that died)
+    if args.merged_fn is not None:
+        merge_chunks(args, todo, rank, ws, failure, m)
     m.close()
     return todo
+
+
+def merge_chunks(args, todo, rank, ws, failure=None, model=None):
+    """--merged_fn: once every rank has written its chunks, rank 0 merges the chunk files that exist (a chunk without
+    candidates may have written none) into one sorted, indexed VCF (vcf_merge.merge, contig order of REF.fai).  Under
+    several ranks every rank first learns whether all of them finished (MAX of a flag, as callVar.TestSharded does): a
+    failed rank means no merged file."""
+    from . import vcf_merge
+    if ws > 1:
+        import torch
+        import torch.distributed as dist
+        flag = torch.tensor([1 if failure is not None else 0], dtype=torch.int32,
+                            device=model.device if model is not None and dist.get_backend() == "nccl" else "cpu")
+        dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+        if failure is not None:
+            raise failure
+        if int(flag.item()) != 0:
+            sys.exit("Error: a rank failed, %s is not written" % args.merged_fn)
+    merged = None
+    if rank == 0:
+        files = [out for _name, _start, _end, out in todo if os.path.isfile(out)]
+        if not files:
+            sys.exit("Error: no chunk wrote a VCF, %s is not written" % args.merged_fn)
+        merged = vcf_merge.merge(files, args.merged_fn, fai_fn=args.ref_fn + ".fai")
+    if ws > 1:
+        dist.barrier()
+    return merged
 
 
 _CLI = (
@@ -148,6 +185,8 @@ _CLI = (
     ("--samtools", str, "samtools", "Path to the 'samtools', default: %(default)s"),
     ("--pypy", str, "pypy", "Path to the 'pypy', default: %(default)s"),
     ("--delay", int, 10, "Wait a short while for no more than %(default)s to start the job."),
+    ("--merged_fn", str, None, "(--run) merge the chunk VCFs into this sorted file once all chunks are written: .vcf.gz "
+                               "(BGZF + .tbi) or .vcf, default: leave the chunk files alone"),
     ("--prefetch", int, 3, "(--run) chunks whose `samtools view` text is fetched ahead, default: %(default)s"),
 )
 _SWITCHES = (("--includingAllContigs", False, "Call variants on all contigs, default: chr{1..22,X,Y,M,MT} and {1..22,X,Y,MT}"),

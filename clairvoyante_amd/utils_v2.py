@@ -728,6 +728,7 @@ class BgzfWriter(object):
         self.owned = isinstance(fn, str)
         self.level, self.block, self.strategy = level, min(block or self.BLOCK, self.BLOCK), strategy
         self.parts, self.have = [], 0
+        self.member_sizes = []           # compressed bytes of every member written so far, in file order (the EOF marker is not one)
         # members are independent: a pool compresses them side by side (zlib releases the GIL) and they are written in
         # order, at most 2 x threads of them in flight.  threads=1: one member after the other on the caller's thread
         self.threads = max(1, min(16, _lib.usable_cores()) if threads is None else int(threads))
@@ -749,18 +750,22 @@ class BgzfWriter(object):
     def _put(self, data):
         """the member of `data` goes to the file behind every member put before it"""
         if self.threads == 1:
-            self.fh.write(self.member(data, self.level, self.strategy))
+            self._out(self.member(data, self.level, self.strategy))
             return
         if self.pool is None:
             from concurrent.futures import ThreadPoolExecutor
             self.pool = ThreadPoolExecutor(max_workers=self.threads)
         while len(self.inflight) >= 2 * self.threads:
-            self.fh.write(self.inflight.popleft().result())
+            self._out(self.inflight.popleft().result())
         self.inflight.append(self.pool.submit(self.member, data, self.level, self.strategy))
+
+    def _out(self, m):
+        self.fh.write(m)
+        self.member_sizes.append(len(m))
 
     def _drain(self):
         while self.inflight:
-            self.fh.write(self.inflight.popleft().result())          # (a worker's exception is raised here)
+            self._out(self.inflight.popleft().result())              # (a worker's exception is raised here)
 
     def write(self, data):
         self.parts.append(bytes(data)); self.have += len(data)

@@ -1014,6 +1014,45 @@ int64_t cv_inflate_stream(const uint8_t *src, int64_t n, int64_t *bitpos, uint8_
                           int64_t want, int32_t *final);
 uint32_t cv_crc32_ieee(uint32_t crc, const uint8_t *p, int64_t n);
 
+/* ---- chunk VCFs merged on the device (csrc/cv_vcfmerge_dev.hip, csrc/cv_vcfmerge_core.hpp) ----------------------------
+ * The last line of the whole-genome recipe (vcfcat | vcfstreamsort | bgziptabix): clairvoyante_amd/vcf_merge.py holds the
+ * definition.  text_dev[0, text_len) = the record bytes of all inputs end to end, 16-byte aligned and readable up to the
+ * next multiple of 16 behind text_len; pos / run / off / len = the n rows of cv_item_lines_dev over it (every line a ROW);
+ * run_rank_dev[nruns] = the contig rank (0 .. nrank - 1) of each run.
+ *
+ * cv_vcf_merge_dev: a line is vouched for unless it has fewer than 8 tab-separated columns, its first two columns are not
+ * "token TAB digits TAB", INFO holds an END= key (at its start or behind a ';'), REF is empty, POS < 1 or POS - 1 +
+ * len(REF) > 2^29, or its row lies outside the text / its run outside the ranks.  The records are ordered by (rank, POS,
+ * line number) -- one stable radix sort over the key bits the data needs --, and in that order:
+ *   srank_dev[i] int32, sbeg_dev[i] = POS - 1, send_dev[i] = sbeg + len(REF), ooff_dev[n + 1] = the offset of record i in
+ *   the output (an exclusive sum of the lengths; ooff[n] = the bytes in all);
+ *   out_text_dev[0, ooff[n]) the sorted text (may be NULL: no text; a range that does not fit below out_cap is not written);
+ *   chunks_dev[4][n] = rank, bin, ubeg, uend of the info[1] chunks -- the maximal runs of equal (rank, reg2bin) --
+ *   sorted by (rank, bin), in file order within a bin;
+ *   stats_dev[4][nrank] = per rank the offset of its first record, the offset behind its last, its records, its largest end;
+ *   info_dev[8] = {lines not vouched for, chunks, bytes, 0 ...}.  With info[0] != 0 nothing else is to be used: the
+ *   call is the host loop's.  At most 2^30 records and 2^20 ranks.
+ * cv_vcf_windows_dev: win_dev[win_off[r] + w] = the smallest ooff of a record of rank r that overlaps window w of 16 384
+ * bp, a window no record touches taking the next one's value (the linear index, back-filled); win_off_dev[nrank + 1] is
+ * the caller's (n_intv per rank from stats), windows outside it are not written.  Needs no workspace.
+ * The _host_form twins: the same core on the CPU over HOST pointers.  The _dev calls are asynchronous on `stream`: no
+ * allocation, no synchronisation; the workspace is 256-byte aligned.                                                     */
+int cv_vcf_merge_workspace(int64_t n, int64_t *bytes);
+int cv_vcf_merge_dev(const char *text_dev, int64_t text_len, int64_t n, const int64_t *pos_dev, const int32_t *run_dev,
+                     const int64_t *off_dev, const int64_t *len_dev, const int32_t *run_rank_dev, int64_t nruns, int32_t nrank,
+                     int32_t *srank_dev, int64_t *sbeg_dev, int64_t *send_dev, int64_t *ooff_dev, char *out_text_dev,
+                     int64_t out_cap, int64_t *chunks_dev, int64_t *stats_dev, int64_t *info_dev, void *workspace_dev,
+                     int64_t workspace_bytes, void *stream);
+int cv_vcf_merge_host_form(const char *text, int64_t text_len, int64_t n, const int64_t *pos, const int32_t *run,
+                           const int64_t *off, const int64_t *len, const int32_t *run_rank, int64_t nruns, int32_t nrank,
+                           int32_t *srank, int64_t *sbeg, int64_t *send, int64_t *ooff, char *out_text, int64_t out_cap,
+                           int64_t *chunks, int64_t *stats, int64_t *info);
+int cv_vcf_windows_dev(int64_t n, const int32_t *srank_dev, const int64_t *sbeg_dev, const int64_t *send_dev,
+                       const int64_t *ooff_dev, int32_t nrank, const int64_t *win_off_dev, int64_t *win_dev, int64_t nwin,
+                       void *stream);
+int cv_vcf_windows_host_form(int64_t n, const int32_t *srank, const int64_t *sbeg, const int64_t *send, const int64_t *ooff,
+                             int32_t nrank, const int64_t *win_off, int64_t *win, int64_t nwin);
+
 #ifdef __cplusplus
 }
 #endif
