@@ -244,8 +244,10 @@ def OutputAlnTensor(args):
         fp = TensorStdout(sys.stdout.buffer)
     # the rows are made on the device, one block and one write per 32 768 of them, or by format_rows on the host, row by
     # row (pileup.format_row_blocks: CV_ROW_FORMAT, else pileup.ROWTEXT_DEVICE_MIN_ROWS) -- the same bytes either way
-    for block in format_row_blocks(args.ctgName, res["centers"], res["ref_seq"], res["shift"], res["tensors"]):
-        fp.stdin.write(block)
+    # With the device BGZF writer (CV_BGZF_DEFLATE=device) a block the kernel printed stays in HBM and is compressed there.
+    in_hbm = bgzf is not None and bgzf.deflate == "device"
+    for block in format_row_blocks(args.ctgName, res["centers"], res["ref_seq"], res["shift"], res["tensors"], in_hbm=in_hbm):
+        bgzf.write_device(block) if hasattr(block, "is_cuda") else fp.stdin.write(block)
     if bgzf is not None:
         bgzf.close()
     elif fpo is not None:

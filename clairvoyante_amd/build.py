@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libclairvoyante_hip.so")
-SOURCES = ["cv_api.hip", "cv_kernels_ref.hip", "cv_kernels_mfma.hip", "cv_kernels_wgrad.hip", "cv_post.hip", "cv_eval.hip", "cv_train.hip", "cv_pileup.hip", "cv_textparse.hip", "cv_trainset.hip", "cv_truth_dev.hip", "cv_beditems_dev.hip", "cv_bamtrain.hip", "cv_inflate_dev.hip", "cv_gzip_dev.hip", "cv_blosc_dev.hip", "cv_blosc_pack_dev.hip", "cv_bam_dev.hip", "cv_rowtext_dev.hip", "cv_candrows_dev.hip", "cv_vcfmerge_dev.hip", "cv_vcf_dev.hip", "cv_callcols_dev.hip", "cv_hostio.cpp", "cv_bam.cpp", "cv_inflate.cpp"]
+SOURCES = ["cv_api.hip", "cv_kernels_ref.hip", "cv_kernels_mfma.hip", "cv_kernels_wgrad.hip", "cv_post.hip", "cv_eval.hip", "cv_train.hip", "cv_pileup.hip", "cv_textparse.hip", "cv_trainset.hip", "cv_truth_dev.hip", "cv_beditems_dev.hip", "cv_bamtrain.hip", "cv_inflate_dev.hip", "cv_gzip_dev.hip", "cv_blosc_dev.hip", "cv_blosc_pack_dev.hip", "cv_bam_dev.hip", "cv_rowtext_dev.hip", "cv_candrows_dev.hip", "cv_vcfmerge_dev.hip", "cv_bgzf_deflate_dev.hip", "cv_vcf_dev.hip", "cv_callcols_dev.hip", "cv_hostio.cpp", "cv_bam.cpp", "cv_inflate.cpp"]
 # -ffp-contract=off: the canonical arithmetic fuses only where fmaf()/MFMA say so
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value"]
 

@@ -425,9 +425,11 @@ def _pinned_bytes(n):
     return _pinned
 
 
-def format_rows_device(ctg, centers, ref_seq, ref_shift, tensors_dev, batch=ROWTEXT_BATCH):
+def format_rows_device(ctg, centers, ref_seq, ref_shift, tensors_dev, batch=ROWTEXT_BATCH, in_hbm=False):
     """format_rows on the device: yields, per batch of at most 32 768 rows, ONE block of bytes -- the rows format_rows
-    gives for it, each followed by "\\n".  tensors_dev [k,33,4,4] fp32 on a GPU; ref_seq bytes / str (uploaded once here)
+    gives for it, each followed by "\\n".  in_hbm: a batch the kernel printed is yielded where it lies, as a uint8
+    tensor on the GPU (for utils_v2.BgzfWriter.write_device: the text never crosses); a batch the host takes stays bytes.
+    tensors_dev [k,33,4,4] fp32 on a GPU; ref_seq bytes / str (uploaded once here)
     or a uint8 tensor already on that GPU.  A batch with a row the device does not vouch for (cv_tensor_rows_text_dev:
     status CV_ROWTEXT_HOST) is formatted whole by format_rows, so is one with a centre less than 17 bytes into the
     reference; row_format_counts() tells which side took what."""
@@ -474,6 +476,10 @@ def format_rows_device(ctg, centers, ref_seq, ref_shift, tensors_dev, batch=ROWT
                 continue
             text = torch.empty(total, dtype=torch.uint8, device=dev)
             call(ptr(text), total)
+            if in_hbm:
+                _row_counts["device"] += n
+                yield text
+                continue
             pin = _pinned_bytes(total)
             pin[:total].copy_(text, non_blocking=True)
             torch.cuda.current_stream(dev).synchronize()
@@ -481,12 +487,13 @@ def format_rows_device(ctg, centers, ref_seq, ref_shift, tensors_dev, batch=ROWT
             yield pin.numpy()[:total].tobytes()
 
 
-def format_row_blocks(ctg, centers, ref_seq, ref_shift, tensors, batch=ROWTEXT_BATCH):
+def format_row_blocks(ctg, centers, ref_seq, ref_shift, tensors, batch=ROWTEXT_BATCH, in_hbm=False):
     """the text of the rows as pieces to write one after the other, by the route CV_ROW_FORMAT / ROWTEXT_DEVICE_MIN_ROWS
     choose: one block per `batch` rows from the device, row by row from the host (joining them first costs more than the
-    writes it saves); the same bytes either way.  tensors: [k,33,4,4] fp32, a torch tensor (on a GPU for the device route)."""
+    writes it saves); the same bytes either way.  tensors: [k,33,4,4] fp32, a torch tensor (on a GPU for the device route).
+    in_hbm: format_rows_device's -- the device route's blocks as tensors on the GPU."""
     if _row_route(len(centers), bool(getattr(tensors, "is_cuda", False))) == "device":
-        for block in format_rows_device(ctg, centers, ref_seq, ref_shift, tensors, batch):
+        for block in format_rows_device(ctg, centers, ref_seq, ref_shift, tensors, batch, in_hbm):
             yield block
         return
     for s in range(0, len(centers), batch):                 # the host's loop as it always ran: a row, its newline, nothing joined

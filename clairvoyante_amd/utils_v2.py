@@ -715,18 +715,56 @@ def GetTensor(tensor_fn, num, log=True, part=None):
 
 
 # ---- BGZF: gzip as independent members of at most 64 KiB (bgzip / htslib), which the GPU inflates side by side -----------
+bgzf_deflate_member_counts = {"host": 0, "device": 0, "host_form": 0, "stored": 0, "fixed": 0, "dynamic": 0, "uploaded": 0, "downloaded": 0}
+
+
+def bgzf_deflate_counts(reset=False):
+    """members BgzfWriter wrote since the start (or the last reset) per route -- "host" (zlib), "device" (the kernels),
+    "host_form" (the core on the CPU) --, the device encoder's members per block type (stored / fixed / dynamic), and
+    the bytes its route sent up (text from host memory) and brought down (the file's)"""
+    out = dict(bgzf_deflate_member_counts)
+    if reset:
+        for k in bgzf_deflate_member_counts:
+            bgzf_deflate_member_counts[k] = 0
+    return out
+
+
+def bgzf_deflate_route(deflate=None):
+    """-> "host", "device" or "host_form" for a BgzfWriter: the argument, or CV_BGZF_DEFLATE when it is None (unset or
+    "host": zlib as ever; "device": the GPU; anything else raises).  "device" without a usable GPU is "host"."""
+    if deflate is None:
+        deflate = os.environ.get("CV_BGZF_DEFLATE") or "host"
+        if deflate not in ("host", "device"):
+            raise _lib.CvError("CV_BGZF_DEFLATE must be host or device, not %r" % deflate)
+    if deflate not in ("host", "device", "host_form"):
+        raise _lib.CvError("BgzfWriter: deflate must be None, 'host' or 'device', not %r" % (deflate,))
+    return "host" if deflate == "device" and not _gpu_present() else deflate
+
+
 class BgzfWriter(object):
     """write() / close() over a new BGZF file: every BLOCK input bytes become one gzip member -- raw DEFLATE from zlib
     between a header whose "BC" extra subfield states the member's size and the CRC-32 / ISIZE trailer --, the 28-byte
     empty member that marks the end follows the last.  Any gzip reads the file as ordinary multi-member gzip.
-    threads: members compressed at a time (None: min(16, usable cores)); the file does not depend on it."""
+    threads: members compressed at a time (None: min(16, usable cores)); the file does not depend on it.
+    deflate: who compresses the members -- "host" (zlib on the pool, the file as it always was), "device" (the kernels of
+    csrc/cv_bgzf_deflate_dev.hip: whole members are gathered up to a slab of SLAB_MEMBERS, compressed in HBM, and only the
+    file's bytes come back) or None: CV_BGZF_DEFLATE (bgzf_deflate_route).  The member cuts, hence the inflated file, the
+    ISIZEs and every uncompressed offset, are the same on both routes; the compressed bytes are not (zlib is the judge of
+    the device's members, not their model), so member_sizes differ.  level and strategy mean nothing on the device route:
+    its encoder has one setting, about zlib's level 1 in size.  write_device() appends text that already
+    lies in HBM; it and write() may be mixed.  "host_form" is the device route with the core's host form in the place of
+    the kernels (the tests' handle on the slab logic)."""
     BLOCK = 65280
+    SLAB_MEMBERS = 256
     EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
-    def __init__(self, fn, level=6, block=None, strategy=0, threads=None):
+    def __init__(self, fn, level=6, block=None, strategy=0, threads=None, deflate=None):
+        self.deflate = bgzf_deflate_route(deflate)
         self.fh = open(fn, "wb") if isinstance(fn, str) else fn
         self.owned = isinstance(fn, str)
         self.level, self.block, self.strategy = level, min(block or self.BLOCK, self.BLOCK), strategy
+        self.pieces, self.pending = collections.deque(), 0      # the device route: bytes and uint8 tensors not yet in a member
+        self.dev, self.dev_ws, self.dev_pin = None, None, None
         self.parts, self.have = [], 0
         self.member_sizes = []           # compressed bytes of every member written so far, in file order (the EOF marker is not one)
         # members are independent: a pool compresses them side by side (zlib releases the GIL) and they are written in
@@ -762,12 +800,120 @@ class BgzfWriter(object):
     def _out(self, m):
         self.fh.write(m)
         self.member_sizes.append(len(m))
+        bgzf_deflate_member_counts["host"] += 1
 
     def _drain(self):
         while self.inflight:
             self._out(self.inflight.popleft().result())              # (a worker's exception is raised here)
 
+    # ---- the device route: pieces (bytes, or uint8 tensors in HBM) queue up; whole members leave in slabs ----------------
+    def write_device(self, text):
+        """appends a 1-d uint8 tensor that lies in HBM (on the host route, or from host memory, it is write()'s)"""
+        if self.deflate != "device" or not getattr(text, "is_cuda", False):
+            return self.write(text.cpu().numpy().tobytes() if hasattr(text, "cpu") else text)
+        n = int(text.numel())
+        if n:
+            self.pieces.append(text.contiguous().reshape(-1))
+            self.pending += n
+            self._slabs(False)
+            # what waits for the next call is the writer's own: the caller may reuse its buffer
+            theirs = text.untyped_storage().data_ptr()
+            self.pieces = collections.deque(p.clone() if not isinstance(p, bytes) and p.untyped_storage().data_ptr() == theirs else p
+                                            for p in self.pieces)
+        return n
+
+    def _take(self, n):
+        """-> the next n pending bytes as pieces (the last one split where it must be)"""
+        out = []
+        while n:
+            p = self.pieces.popleft()
+            k = len(p)
+            if k > n:
+                self.pieces.appendleft(p[n:])
+                p, k = p[:n], n
+            out.append(p)
+            n -= k
+            self.pending -= k
+        return out
+
+    def _slabs(self, last):
+        slab = self.SLAB_MEMBERS * self.block
+        while self.pending >= (1 if last else slab):
+            whole = self.pending - self.pending % self.block
+            n = min(slab, whole) if whole else self.pending     # (only the last call sends a member shorter than the block)
+            data, sizes, info = (self._compress_host_form if self.deflate == "host_form" else self._compress_device)(self._take(n), n)
+            assert len(sizes) == -(-n // self.block) and int(info[0]) == len(data) == int(sizes.sum())
+            self.fh.write(data)
+            self.member_sizes.extend(int(v) for v in sizes)
+            bgzf_deflate_member_counts[self.deflate] += len(sizes)
+            for k, name in enumerate(("stored", "fixed", "dynamic")):
+                bgzf_deflate_member_counts[name] += int(info[2 + k])
+            bgzf_deflate_member_counts["downloaded"] += len(data)
+
+    def _compress_host_form(self, pieces, n):
+        text = np.frombuffer(b"".join(bytes(p) for p in pieces), dtype=np.uint8)
+        members = -(-n // self.block)
+        out = np.empty(members * (self.block + 31), dtype=np.uint8)
+        sizes, info = np.zeros(members, dtype=np.int32), np.zeros(8, dtype=np.int64)
+        V = lambda a: ctypes.c_void_p(a.ctypes.data)
+        _lib.check(_lib.load().cv_bgzf_deflate_host_form(V(text), n, self.block, V(out), len(out), V(sizes), V(info)))
+        return out[:int(info[0])].tobytes(), sizes, info
+
+    def _compress_device(self, pieces, n):
+        import torch
+        lib = _lib.load()
+        if self.dev is None:
+            on = [p.device for p in pieces if not isinstance(p, bytes)]
+            self.dev = on[0] if on else torch.device("cuda", torch.cuda.current_device())
+        dev = self.dev
+        with torch.cuda.device(dev):
+            if len(pieces) == 1 and not isinstance(pieces[0], bytes) and pieces[0].device == dev:
+                text = pieces[0]                                # (any alignment: no copy)
+            else:                                               # pieces that straddle cuts are joined here, in HBM
+                text = torch.empty(n, dtype=torch.uint8, device=dev)
+                at, k = 0, 0
+                while k < len(pieces):
+                    if isinstance(pieces[k], bytes):
+                        j = k
+                        while j < len(pieces) and isinstance(pieces[j], bytes):
+                            j += 1
+                        host = b"".join(pieces[k:j])
+                        text[at:at + len(host)].copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8), non_blocking=False)
+                        bgzf_deflate_member_counts["uploaded"] += len(host)
+                        at, k = at + len(host), j
+                    else:
+                        text[at:at + len(pieces[k])].copy_(pieces[k])
+                        at, k = at + len(pieces[k]), k + 1
+            members = -(-n // self.block)
+            need = _lib.workspace(lib.cv_bgzf_deflate_workspace, members, self.block)
+            if self.dev_ws is None or self.dev_ws.numel() < need:
+                self.dev_ws = None
+                self.dev_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            cap = members * (self.block + 31)
+            out = torch.empty(cap, dtype=torch.uint8, device=dev)
+            tail = torch.empty(8 + (members + 1) // 2, dtype=torch.int64, device=dev)      # info, then the sizes: one copy
+            sizes_dev = tail[8:].view(torch.int32)[:members]
+            _lib.check(lib.cv_bgzf_deflate_dev(_lib.ptr(text), n, self.block, _lib.ptr(out), cap, _lib.ptr(sizes_dev), _lib.ptr(tail),
+                                               _lib.ptr(self.dev_ws), need, _lib.stream_arg(dev)))
+            got = tail.cpu()
+            info, sizes = got[:8].numpy(), got[8:].view(torch.int32)[:members].numpy()
+            total = int(info[0])
+            if total > cap:
+                raise _lib.CvError("cv_bgzf_deflate_dev: %d bytes for %d members of %d" % (total, members, self.block))
+            if self.dev_pin is None or self.dev_pin.numel() < total:
+                self.dev_pin = torch.empty(max(total, 1 << 20), dtype=torch.uint8).pin_memory()
+            self.dev_pin[:total].copy_(out[:total], non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+            return self.dev_pin.numpy()[:total].tobytes(), sizes, info
+
     def write(self, data):
+        if self.deflate != "host":
+            data = bytes(data)
+            if data:
+                self.pieces.append(data)
+                self.pending += len(data)
+                self._slabs(False)
+            return len(data)
         self.parts.append(bytes(data)); self.have += len(data)
         if self.have >= self.block:
             buf = b"".join(self.parts)
@@ -788,9 +934,12 @@ class BgzfWriter(object):
                 self._put(b"".join(self.parts))
                 self.parts, self.have = [], 0
             self._drain()
+            self._slabs(True)
             self.fh.write(self.EOF)
         finally:
             fh, self.fh = self.fh, None
+            self.pieces.clear()
+            self.dev_ws = self.dev_pin = None
             if self.pool is not None:
                 for f in self.inflight:
                     f.cancel()

@@ -278,7 +278,8 @@ def write_tbi(fn, names, contigs, threads=None):
         out.append(struct.pack("<Ii4Q", PSEUDO_BIN, 2, first, last, count, 0))
         out.append(struct.pack("<i", len(ioff)))
         out.append(np.asarray(ioff, dtype="<u8").tobytes())
-    with utils_v2.BgzfWriter(fn, threads=threads) as w:    # (the index is BGZF too; its bytes do not depend on the threads)
+    # (the index is BGZF too; its bytes do not depend on the threads -- nor on CV_BGZF_DEFLATE: zlib writes it)
+    with utils_v2.BgzfWriter(fn, threads=threads, deflate="host") as w:
         w.write(b"".join(out))
 
 
@@ -295,8 +296,8 @@ def _write(out_fn, header, blocks, t, block, threads):
     w = utils_v2.BgzfWriter(out_fn, block=block, threads=threads)
     with w:
         w.write(header)
-        for b in blocks:
-            w.write(b)
+        for b in blocks:                                    # (a block that is still in HBM: the device writer's)
+            w.write_device(b) if hasattr(b, "is_cuda") else w.write(b)
     t1 = time.time()
     H = len(header)
     V = lambda u: _virtual(np.asarray(u, dtype=np.int64) + H, w.block, w.member_sizes)
@@ -527,8 +528,15 @@ def _merge_device(files, out_fn, fai_fn, block, threads, device):
             TIMES["read_s"] = TIMES.get("read_s", 0.0) + t_read - t0
             TIMES["order_index_s"] = TIMES.get("order_index_s", 0.0) + t_dev - t_read
 
-        # 6. the sorted text crosses in pinned slabs, straight into the writer
+        # 6. the sorted text crosses in pinned slabs, straight into the writer -- or, with the device writer
+        # (CV_BGZF_DEFLATE=device), stays where it is: the writer compresses it in HBM and only the file's bytes cross
+        in_hbm = not out_fn.endswith(".vcf") and utils_v2.bgzf_deflate_route() == "device"
+
         def slabs(step=1 << 24):
+            if in_hbm:
+                for lo in range(0, n_text, step):
+                    yield out_text[lo:min(lo + step, n_text)]
+                return
             pinned = torch.empty(min(step, max(n_text, 1)), dtype=torch.uint8).pin_memory()
             for lo in range(0, n_text, step):
                 k = min(step, n_text - lo)

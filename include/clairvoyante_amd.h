@@ -1053,6 +1053,27 @@ int cv_vcf_windows_dev(int64_t n, const int32_t *srank_dev, const int64_t *sbeg_
 int cv_vcf_windows_host_form(int64_t n, const int32_t *srank, const int64_t *sbeg, const int64_t *send, const int64_t *ooff,
                              int32_t nrank, const int64_t *win_off, int64_t *win, int64_t nwin);
 
+/* ---- BGZF members compressed on the device (csrc/cv_bgzf_deflate_dev.hip, csrc/cv_bgzf_deflate_core.hpp) ---------------
+ * The writer's side of utils_v2.BgzfWriter (deflate="device"): text_dev[0, len) -- any alignment -- is cut every `block`
+ * bytes (1 .. 65 280); member k holds the bytes [k * block, min(len, (k + 1) * block)) as the 18-byte BGZF header with
+ * BSIZE, ONE final DEFLATE block -- the smallest of stored, fixed and dynamic Huffman, from a position-parallel match
+ * search and a greedy parse -- and the CRC-32 / ISIZE trailer.  An empty text is one empty member.  The members lie back to
+ * back in out_dev[0, info[0]); a member that does not fit below out_cap is not written.  No member is larger than its
+ * stored form, len_k + 31 bytes, so members * (block + 31) always suffices.
+ *   sizes_dev[members] int32 = the bytes of each member, header and trailer included;
+ *   info_dev[8] = {bytes of all members, members, stored, fixed, dynamic, 0 ...}.
+ * The bytes are those of cv_bgzf_deflate_host_form, the same core on the CPU over HOST pointers, and depend on nothing but
+ * the text and the block.  They are NOT zlib's: any inflater is the judge.  Asynchronous on `stream`: no allocation, no
+ * synchronisation; the workspace is 256-byte aligned.                                                                    */
+int cv_bgzf_deflate_workspace(int64_t members, int64_t block, int64_t *bytes);
+int cv_bgzf_deflate_dev(const uint8_t *text_dev, int64_t len, int64_t block, uint8_t *out_dev, int64_t out_cap, int32_t *sizes_dev,
+                        int64_t *info_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+/* one of the three launches alone (0 compress, 1 offsets, 2 assemble), for the probe's HIP events; after one whole call */
+int cv_bgzf_deflate_phase_dev(int phase, const uint8_t *text_dev, int64_t len, int64_t block, uint8_t *out_dev, int64_t out_cap,
+                              int32_t *sizes_dev, int64_t *info_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int cv_bgzf_deflate_host_form(const uint8_t *text, int64_t len, int64_t block, uint8_t *out, int64_t out_cap, int32_t *sizes,
+                              int64_t *info);
+
 #ifdef __cplusplus
 }
 #endif
