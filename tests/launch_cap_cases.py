@@ -13,12 +13,17 @@ class:
 GRID_FOR is cv_grid_for's default geometry (csrc/cv_dev_common.hpp): 4 096 blocks of 256 threads under CV_GRID_STRIDE."""
 
 FILES = ("cv_textparse", "cv_trainset", "cv_truth_dev", "cv_beditems_dev", "cv_bamtrain", "cv_candrows_dev", "cv_callcols_dev",
-         "cv_vcf_dev", "cv_rowtext_dev", "cv_eval", "cv_inflate_dev", "cv_gzip_dev", "cv_blosc_dev", "cv_blosc_pack_dev", "cv_bam_dev")
+         "cv_vcf_dev", "cv_rowtext_dev", "cv_eval", "cv_inflate_dev", "cv_gzip_dev", "cv_blosc_dev", "cv_blosc_pack_dev", "cv_bam_dev",
+         "cv_vcfmerge_dev", "cv_bgzf_deflate_dev")
+# the compute plane: held by the oracle, parity and planted tests, whose shapes are the model's and not a launch cap's
+OUTSIDE = ("cv_api", "cv_kernels_ref", "cv_kernels_mfma", "cv_kernels_wgrad", "cv_pileup", "cv_post", "cv_train")
 
 GRID_FOR = 4096 * 256
 
 _NEW = "tests/test_gpu_launch_caps.py::"
 _BIG = "tests/test_gpu_past_4gib.py::"
+_MERGE = _NEW + "test_vcf_merge_past_the_grid_stride_line"
+_DEFLATE = "tests/test_gpu_bgzf_deflate.py::"
 
 
 def _uncapped(file, grid):
@@ -152,4 +157,24 @@ KERNELS = {
     "bam_resolve": _uncapped("cv_bam_dev", "ceil(records / 256); a ballot per wave, no loop in front of it"),
     "bam_totals": _fixed("cv_bam_dev", "one thread"),
     "bam_emit": _uncapped("cv_bam_dev", "ceil(records / 4): one wave per record"),
+    # ---- cv_vcfmerge_dev.hip -------------------------------------------------------------------------------------------------
+    "vm_fields": _grid_for("cv_vcfmerge_dev", "records", _MERGE),
+    "vm_sorted": _grid_for("cv_vcfmerge_dev", "records + 1", _MERGE),
+    "vm_gather": _capped("cv_vcfmerge_dev", "tiles of 64 output records, one one-wave block each (65 536 blocks; the block's LDS tile "
+                         "serves its second tile)", 65536 * 64, _NEW + "test_vcf_gather_past_the_tile_line"),
+    "vm_heads": _grid_for("cv_vcfmerge_dev", "records + 1", _MERGE),
+    "vm_chunks": _grid_for("cv_vcfmerge_dev", "records", _MERGE),
+    "vm_chunk_out": _grid_for("cv_vcfmerge_dev", "records", _MERGE),
+    "vw_fill": _grid_for("cv_vcfmerge_dev", "windows of 16 384 bases", _MERGE),
+    "vw_min": _grid_for("cv_vcfmerge_dev", "records", _MERGE),
+    "vw_backfill": _capped("cv_vcfmerge_dev", "contig ranks, one block each (1 024 blocks)", 1024, _MERGE),
+    # ---- cv_bgzf_deflate_dev.hip ---------------------------------------------------------------------------------------------
+    "bd_compress": _capped("cv_bgzf_deflate_dev", "members, one workgroup each (MAX_GRID = 512; the workgroup's LDS state and its "
+                           "verdicts in the workspace serve its second member)", 512,
+                           _DEFLATE + "test_multi_tile_members_past_the_workgroup_line",
+                           also=[_DEFLATE + "test_more_members_than_workgroups"]),
+    "bd_offsets": _fixed("cv_bgzf_deflate_dev", "one block of 256 threads walks the sizes in steps of its size with a carry; 20 steps in "
+                         + _DEFLATE + "test_more_members_than_workgroups"),
+    "bd_assemble": _capped("cv_bgzf_deflate_dev", "members, one block each (4 096 blocks)", 4096,
+                           _DEFLATE + "test_more_members_than_workgroups"),
 }

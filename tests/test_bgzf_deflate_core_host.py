@@ -104,6 +104,44 @@ def test_small_members_and_the_empty_text():
         bc.judge(data, sizes, text, 65280)
 
 
+@pytest.mark.parametrize("members,block", bc.TWO_TRIPS)
+def test_the_two_trip_text_alternates_its_block_types(members, block):
+    """what test_gpu_bgzf_deflate.py's multi-tile case claims: more members than workgroups, every member a whole block of
+    16 or 255 tiles, members m and m + 512 of different block types, and in a text member matches that reach further back
+    than one tile of 256 positions, by the hundred (the member's own distances, read from its DEFLATE block)"""
+    text = bc.two_trip_text(members, block)
+    assert members > bc.WORKGROUPS == 512 and len(text) == members * block and block // 256 in (16, 255)
+    data, sizes, info = bc.host_form(text, block)
+    kinds = bc.member_kinds(data, sizes)
+    assert [kinds.count(k) for k in (0, 1, 2)] == info[2:5].tolist() and info[2] > 0 and info[4] > 0
+    assert all(kinds[m] != kinds[m + bc.WORKGROUPS] for m in range(members - bc.WORKGROUPS)) and members - bc.WORKGROUPS in (77, 3)
+    assert all((kinds[m] == 2) == bc.two_trip_kind(m) and kinds[m] in (0, 2) for m in range(members))
+    half = block // 2
+    for m in (0, 2, bc.WORKGROUPS + 1):                         # (a first trip's, and a second trip's)
+        assert bc.two_trip_kind(m) and text[m * block:m * block + half] == text[m * block + half:(m + 1) * block] and half > 256
+        at = int(np.sum(sizes[:m]))
+        far = [d for d in bc.match_distances(data[at:at + int(sizes[m])]) if d > 256]
+        assert len(far) > block // 40 and max(far) > block // 4, (m, len(far))
+    if block == 4096:
+        assert bc.judge(data, sizes, text, block) == kinds
+
+
+def test_an_output_too_small_for_its_members():
+    """nothing of a member that does not fit is written, the rest keeps what it held, info[0] names the full need; zlib
+    judges the members a cap of whole members holds"""
+    text = bc.fixture("vcf_records")[:9 * 1000 + 123]
+    full, sizes, info = bc.host_form(text, 1000)
+    off = np.concatenate(([0], np.cumsum(sizes)))
+    assert len(sizes) == 10 and info[0] == len(full)
+    for cap, fit in bc.small_output_caps(sizes):
+        out, s, i = bc.host_form(text, 1000, out_cap=cap, fill=0x5A)
+        edge = int(off[fit])
+        assert s.tolist() == sizes.tolist() and i.tolist() == info.tolist() and edge <= cap
+        assert out[:edge] == full[:edge] and out[edge:] == b"\x5a" * (len(out) - edge), cap
+        if edge == cap and fit:
+            bc.judge(out[:edge], sizes[:fit], text[:fit * 1000], 1000)
+
+
 def test_arguments_are_checked():
     import ctypes
     from clairvoyante_amd import _lib

@@ -2,7 +2,14 @@
 bytes, sizes and counts equal cv_bgzf_deflate_host_form's (held to zlib's judgement and run under the sanitizers by
 test_bgzf_deflate_core_host.py), with canaries behind every output and the workspace; then the writer and its two drivers:
 MergeVcf and CreateTensor --bgzf write files whose inflated bytes, ISIZEs and index answers are the host route's, and the
-device's own inflater reads what the device's compressor wrote."""
+device's own inflater reads what the device's compressor wrote.
+
+bd_compress has 512 workgroups and loops over the members: test_multi_tile_members_past_the_workgroup_line gives it 589
+members of 16 tiles and 515 of 255 tiles, text and random bytes in turn so that a workgroup's second member has the other
+block type than its first (bgzf_deflate_cases.two_trip_text; test_bgzf_deflate_core_host.py holds the text to that).  With
+the member loop cut to one trip, in a library built from a scratch copy, it fails: sizes[512] keeps its canary.
+Seconds on one MI355X (pytest --durations): 0.27 at block 4 096, 0.71 at block 65 280 (33.6 MB, the host form's time);
+the output too small for its members 0.01."""
 import ctypes
 import gzip
 import io
@@ -40,9 +47,10 @@ class _Guarded(object):
         return b[self.at:self.at + self.size]
 
 
-def dev_call(text, block, offset=0, ws_shift=0, ws_short=0):
+def dev_call(text, block, offset=0, ws_shift=0, ws_short=0, out_cap=None):
     """cv_bgzf_deflate_dev over `text` lying `offset` bytes behind a 256-byte boundary, everything guarded
-    -> (file bytes without the EOF marker, sizes, info) like bc.host_form"""
+    -> (file bytes without the EOF marker, sizes, info) like bc.host_form; with out_cap, the room the call is told the
+    output has: the WHOLE output comes back, the canary where nothing was written"""
     import torch
     from clairvoyante_amd import _lib
     lib = _lib.load()
@@ -53,13 +61,13 @@ def dev_call(text, block, offset=0, ws_shift=0, ws_short=0):
     out, sizes, info = _Guarded(torch, dev, cap), _Guarded(torch, dev, 4 * members), _Guarded(torch, dev, 64)
     need = _lib.workspace(lib.cv_bgzf_deflate_workspace, members, block)
     ws = _Guarded(torch, dev, need - ws_short, ws_shift)
-    _lib.check(lib.cv_bgzf_deflate_dev(src.ptr if len(text) else None, len(text), block, out.ptr, cap, sizes.ptr, info.ptr, ws.ptr,
-                                       need - ws_short, _lib.stream_arg(dev)))
+    _lib.check(lib.cv_bgzf_deflate_dev(src.ptr if len(text) else None, len(text), block, out.ptr, cap if out_cap is None else out_cap,
+                                       sizes.ptr, info.ptr, ws.ptr, need - ws_short, _lib.stream_arg(dev)))
     torch.cuda.synchronize()
     ws.read()
     assert src.read().tobytes() == text
     i, s = info.read().view(np.int64).copy(), sizes.read().view(np.int32).copy()
-    return out.read()[:int(i[0])].tobytes(), s, i
+    return (out.read()[:int(i[0])] if out_cap is None else out.read()).tobytes(), s, i
 
 
 def same(text, block, offset=0):
@@ -98,6 +106,35 @@ def test_more_members_than_workgroups():
     text = (bc.fixture("vcf_records") * 3)[:5000 * 64 - 17]
     data, sizes, info = same(text, 64)
     assert len(sizes) == 5000 == info[1] and info[2:5].sum() == 5000
+
+
+@pytest.mark.parametrize("members,block", bc.TWO_TRIPS)
+def test_multi_tile_members_past_the_workgroup_line(members, block):
+    """more members than bd_compress has workgroups, of 16 and of 255 tiles: a workgroup's second member reads a hash
+    table, verdicts and an LDS state its first one filled tile after tile, and follows a stored member with a dynamic one
+    or the other way round (tests/test_bgzf_deflate_core_host.py holds the text to that)"""
+    text = bc.two_trip_text(members, block)
+    data, sizes, info = same(text, block)
+    assert len(sizes) == members == info[1] > bc.WORKGROUPS and info[2] > 0 and info[4] > 0 and info[2:5].sum() == members
+    kinds = bc.member_kinds(data, sizes)
+    assert all(kinds[m] != kinds[m + bc.WORKGROUPS] for m in range(members - bc.WORKGROUPS))
+    if block == 4096:
+        assert bc.judge(data, sizes, text, block) == kinds
+
+
+def test_an_output_too_small_for_its_members():
+    """bd_assemble skips a member that does not fit below out_cap; info[0] still names what all of them need"""
+    text = bc.fixture("vcf_records")[:9 * 1000 + 123]
+    full, sizes, info = dev_call(text, 1000)
+    off = np.concatenate(([0], np.cumsum(sizes)))
+    assert len(sizes) == 10 and info[0] == len(full) == off[-1]
+    for cap, fit in bc.small_output_caps(sizes):
+        got, want = dev_call(text, 1000, out_cap=cap), bc.host_form(text, 1000, out_cap=cap, fill=CANARY)
+        assert got[1].tolist() == want[1].tolist() == sizes.tolist() and got[2].tolist() == want[2].tolist() == info.tolist(), cap
+        assert got[0] == want[0], cap
+        edge = int(off[fit])
+        assert edge <= cap and (fit == len(sizes) or off[fit + 1] > cap)
+        assert got[0][:edge] == full[:edge] and got[0][edge:] == bytes([CANARY]) * (len(got[0]) - edge), cap
 
 
 @pytest.mark.parametrize("offset", (1, 7, 15))

@@ -14,6 +14,18 @@ That the tests bite: with CV_GRID_STRIDE cut to one trip, every test here whose 
 others hold kernels with loops of their own (ik_copy, tp_parse_rows and the index kernels, the decoders, the packer,
 bam_gather) or, test_three_rows_over_65535_contigs, a loop that never strides.
 
+The VCF merge (section 10; inputs from tests/vcf_merge_big_cases.py, held to their claims on the CPU by
+test_vcf_merge_big_cases_host.py): vm_fields, vm_sorted, vm_heads, vm_chunks, vm_chunk_out and vw_min cross GRID_FOR at
+1 048 653 records, vw_fill at 1 162 900 windows, vw_backfill its 1 024 blocks at 1 100 contig ranks, vm_gather its
+65 536 blocks x 64 records at 4 194 381 records (its workspace is 340 281 088 bytes by the query: under the 512 MB a
+buffer of a test here may take, which _merge_call asserts).
+That they bite, each with a library built from a scratch copy for one run: with vm_gather's tile loop cut to one trip
+test_vcf_gather_past_the_tile_line fails (the text of tiles 65 536 and 65 537 keeps its sentinel); with CV_GRID_STRIDE
+cut to one trip test_vcf_merge_past_the_grid_stride_line fails at info (83 407 chunks for 83 430).  That second run had
+the workspace filled with zeros: vm_fields' unwritten line numbers are indices, and 0xAB bytes would have been wild ones.
+Seconds on one MI355X (pytest --durations): the merge past the grid-stride line 2.8 (two builds, two host forms, two
+device calls), the gather past the tile line 1.5, the rank widths 0.05.
+
 The lines, as arithmetic on the sources' own constants:"""
 import ctypes
 
@@ -35,6 +47,9 @@ GZIP_REST_LINE = 4096 * 256 * 8    # csrc/cv_gzip_dev.hip, gzip_rest: GRID block
 BLOSC_LINE = 8192 * 4              # csrc/cv_blosc_dev.hip, blosc_decode: DECODE_GRID x DECODE_WAVES, one wave per stream
 PACK_LINE = 1 << 20                # csrc/cv_blosc_pack_dev.hip, pack_encode / pack_assemble: MAX_GRID blocks, one per stream
 WALK_LINE = 4096                   # csrc/cv_bam_dev.hip, bam_gather: 4 096 blocks, one per walker
+MERGE_TILE_LINE = 65536 * 64       # csrc/cv_vcfmerge_dev.hip, vm_gather: 65 536 one-wave blocks, a tile of 64 output records each
+BACKFILL_LINE = 1024               # csrc/cv_vcfmerge_dev.hip, vw_backfill: 1 024 blocks, one contig rank each
+TEST_BYTES = 512 << 20             # the largest single buffer a test here allocates
 WSIZE, MARK = 32768, 0x8000        # csrc/cv_gzip_core.hpp: the window, the marker bit of a symbol
 R = 77                             # ragged: no multiple of 16, 64 or 256
 CANARY = 96                        # elements of sentinel behind every output
@@ -1029,3 +1044,96 @@ def test_one_bam_slab_past_the_walker_line(tmp_path):
     TB.clean(cnt)
     assert cnt["walkers"] > WALK_LINE + R - 2 and cnt["device_slabs"] == 1
     assert h[4] == nreads and h[3].all() and h[1].any()
+
+
+# ---- 10. the VCF merge (vm_fields, vm_sorted, vm_gather, vm_heads, vm_chunks, vm_chunk_out, vw_fill, vw_min, vw_backfill) --------
+def _merge_call(a, phase=0):
+    """cv_vcf_merge_dev + cv_vcf_windows_dev over the arrays of vcf_merge_big_cases, the output text at `phase` mod 16
+    -> dict like vcf_merge_cases.host_form's; what lies behind the used part of an output still holds its sentinel"""
+    A, lib = _abi()
+    n, nrank, n_text = a["n"], a["nrank"], a["n_text"]
+    text, pos, run, off, ln, rr = (_up(a[k]) for k in ("text", "pos", "run", "off", "len", "run_rank"))
+    assert text.data_ptr() % 16 == 0 and len(a["text"]) == n_text + 16
+    o = {"srank": Out(n, "int32"), "sbeg": Out(n, "int64"), "send": Out(n, "int64"), "ooff": Out(n + 1, "int64"),
+         "text": Out(n_text + 16, "uint8"), "chunks": Out(4 * n, "int64"), "stats": Out(4 * nrank, "int64"), "info": Out(8, "int64")}
+    shift = (phase - o["text"].t.data_ptr()) % 16
+    ws, need = _workspace(lib.cv_vcf_merge_workspace, n)
+    assert max(need, 32 * n, n_text) <= TEST_BYTES
+    A.check(lib.cv_vcf_merge_dev(_p(text), n_text, n, _p(pos), _p(run), _p(off), _p(ln), _p(rr), a["nruns"], nrank, o["srank"].p, o["sbeg"].p,
+                                 o["send"].p, o["ooff"].p, ctypes.c_void_p(o["text"].t.data_ptr() + shift), n_text, o["chunks"].p,
+                                 o["stats"].p, o["info"].p, _p(ws), need, _stream()))
+    g = {k: v.get() for k, v in o.items() if k != "text"}
+    nbytes, nc = int(g["info"][2]), int(g["info"][1])
+    full = o["text"].get(shift + nbytes)                            # (asserts the sentinel behind the text's last byte)
+    assert (full[:shift] == SENTINEL["uint8"]).all()
+    g["text"] = full[shift:]
+    g["chunks"], g["stats"] = g["chunks"].reshape(4, n), g["stats"].reshape(4, nrank)
+    assert (g["chunks"][:, nc:] == SENTINEL["int64"]).all()
+    count, maxend = g["stats"][2], g["stats"][3]
+    g["win_off"] = np.concatenate(([0], np.cumsum(np.where(count > 0, ((maxend - 1) >> 14) + 1, 0)))).astype(np.int64)
+    nwin = int(g["win_off"][-1])
+    win, d_off = Out(nwin, "int64"), _up(g["win_off"])
+    A.check(lib.cv_vcf_windows_dev(n, o["srank"].p, o["sbeg"].p, o["send"].p, o["ooff"].p, nrank, _p(d_off), win.p, nwin, _stream()))
+    g["win"] = win.get()
+    return g
+
+
+def _merge_same(g, w, a):
+    """every output of the two entry points against the host forms': what _same of test_gpu_vcf_merge.py compares"""
+    n, nc, nwin, nbytes = a["n"], int(w["info"][1]), int(w["win_off"][-1]), int(w["info"][2])
+    assert g["info"].tolist() == w["info"].tolist()
+    for k in ("srank", "sbeg", "send"):
+        assert np.array_equal(g[k], w[k][:n]), k
+    assert np.array_equal(g["ooff"], w["ooff"]) and np.array_equal(g["stats"], w["stats"]) and np.array_equal(g["win_off"], w["win_off"])
+    assert np.array_equal(g["chunks"][:, :nc], w["chunks"][:, :nc])
+    assert len(g["win"]) == nwin and np.array_equal(g["win"], w["win"][:nwin])
+    assert len(g["text"]) == nbytes <= a["n_text"] and np.array_equal(g["text"], w["text"][:nbytes])
+
+
+def test_vcf_merge_past_the_grid_stride_line():
+    """GRID_FOR + R unique lines of eight sorted files laid end to end, over 1 100 contig ranks (vw_backfill's blocks take a
+    second contig), 33 of which reach 2^29 (1 162 900 windows: vw_fill strides), 83 430 chunks, four in ten of the records
+    tied with a record of another run, one key 5 002 times: only a stable sort gives the host form's order.
+    Then the same with one line among the last R that the device does not vouch for"""
+    import vcf_merge_big_cases as B
+    import vcf_merge_cases as vc
+    a, _facts = B.merge_case()
+    assert a["n"] == GRID_FOR + R and a["nrank"] > BACKFILL_LINE
+    w = vc.host_form(a)
+    assert int(w["win_off"][-1]) > GRID_FOR and w["info"][0] == 0
+    _merge_same(_merge_call(a), w, a)
+    b, facts = B.merge_case(with_end=True)
+    assert facts["end_at"] >= GRID_FOR
+    wb = vc.host_form(b)
+    assert wb["info"][0] == 1
+    _merge_same(_merge_call(b, phase=9), wb, b)
+
+
+def test_vcf_gather_past_the_tile_line():
+    """MERGE_TILE_LINE + R records of 20 to 30 bytes: 65 538 tiles, so blocks 0 and 1 of vm_gather write their LDS tile a
+    second time, the last tile holds 13 records, and the output stands at phase 5 (granule stores and end bytes).  The
+    CV_GRID_STRIDE kernels make four trips and a ragged fifth"""
+    import vcf_merge_big_cases as B
+    import vcf_merge_cases as vc
+    a = B.gather_case()
+    assert a["n"] == MERGE_TILE_LINE + R and -(-a["n"] // 64) == 65536 + 2 and a["n"] % 64 == 13
+    _merge_same(_merge_call(a, phase=5), vc.host_form(a), a)
+
+
+def test_vcf_merge_rank_widths():
+    """the sort keys are POS_BITS + bits_for(nrank) and 16 + bits_for(nrank + 1) bits wide: records in the lowest and the
+    highest rank, either side of every power of two the widths turn at, up to MAX_RANKS; one more is refused"""
+    import vcf_merge_big_cases as B
+    import vcf_merge_cases as vc
+    A, _lib = _abi()
+    for nrank in B.RANK_COUNTS:
+        a = B.rank_case(nrank)
+        w = vc.host_form(a)
+        assert w["srank"][a["n"] - 1] == nrank - 1 and w["sbeg"][a["n"] - 1] == (1 << 29) - 1
+        _merge_same(_merge_call(a, phase=nrank % 16), w, a)
+    a = dict(B.rank_case(B.MAX_RANKS), nrank=B.MAX_RANKS + 1)
+    with pytest.raises(A.CvError, match="contig ranks"):
+        vc.host_form(a)
+    with pytest.raises(A.CvError, match="contig ranks"):
+        _merge_call(a)
+

@@ -32,6 +32,11 @@ and its wrapped addresses 2.31 (the fill of 17.18 GB and ~1 100 row-sized copies
 0.55 (the pass itself 0.029) / slim 0.09 (0.014), cv_forward over 4 067 220 rows 0.48, cv_tensor_rows_text_dev 0.20,
 cv_text_gather_rows into the large output 0.13, cv_trainset_gather into the large output 0.09, cv_call_postproc 0.07,
 cv_trainset_gather from the large source 0.05, cv_vcf_records_dev 0.04, the other six 0.01 or less.
+
+cv_vcf_merge_dev (test_vcf_merge_gathers_from_and_into_text_past_2_32_bytes, 0.31 s): a source text of 2^32 + 2^20 bytes
+whose records all lie in its last MiB (every off past 2^32), 524 352 records of 8 192 bytes -- 4 295 491 584 bytes, so
+ooff passes 2^32 at record 524 288, inside vm_gather's wave-per-record path -- and 200 records of 40 to 90 bytes behind
+them, whose tiles take the LDS path wholly past the line; source and output 4.30 GB each.
 """
 import ctypes
 import time
@@ -374,6 +379,53 @@ def test_gather_tokens_planted_past_2_32_bytes(text):
     got = out.cpu().numpy().tobytes()
     assert got[:len(want_bytes)] == want_bytes and got[len(want_bytes):] == b"\xa5" * 64
     assert meta_out.cpu().numpy().tolist() == want_meta + [[-7] * 6]
+
+
+def test_vcf_merge_gathers_from_and_into_text_past_2_32_bytes():
+    """cv_vcf_merge_dev: every record lies in the last MiB of a source text of 2^32 + 2^20 bytes, and 524 352 records of
+    8 192 bytes (64 lines, 8 193 copies each, a tie run per line) make an output whose offsets pass 2^32 inside vm_gather's
+    wave-per-record path; 200 short records follow in a higher rank, their tiles on the LDS path wholly behind the line.
+    The order is numpy's lexsort by (rank, POS, input index)"""
+    import torch
+    import vcf_merge_big_cases as B
+    A, lib = _abi()
+    mib, a, line = B.big_case()
+    n, n_long = a["n"], B.BIG_LINES * B.BIG_COPIES
+    order = B.expected_order(a)
+    ooff = np.concatenate(([0], np.cumsum(a["len"][order])))
+    total = int(ooff[-1])
+    assert a["n_text"] == TEXT_LEN and a["off"].min() >= 1 << 32 and ooff[n_long] == (1 << 32) + 524288 and ooff[524288] == 1 << 32
+    need = ctypes.c_int64(-1)
+    A.check(lib.cv_vcf_merge_workspace(n, ctypes.byref(need)))
+    _room(TEXT_LEN + total + need.value + (2 << 30), "cv_vcf_merge_dev over a source and an output text of 4.3 GB each")
+    src = torch.zeros(TEXT_LEN + 64, dtype=torch.uint8, device="cuda")
+    src[B.BIG_BASE:TEXT_LEN] = torch.from_numpy(mib).cuda()
+    assert src.data_ptr() % 16 == 0
+    out = torch.full((total + 256,), 0xA5, dtype=torch.uint8, device="cuda")
+    d = [torch.from_numpy(a[k]).cuda() for k in ("pos", "run", "off", "len", "run_rank")]
+    srank, sbeg, send, d_ooff = (torch.full((n + 2,), -7, dtype=dt, device="cuda") for dt in (torch.int32, torch.int64, torch.int64, torch.int64))
+    chunks, stats, info = (torch.full((k,), -7, dtype=torch.int64, device="cuda") for k in (4 * n, 4 * 2, 8))
+    ws = torch.full((need.value,), 0xAB, dtype=torch.uint8, device="cuda")
+    A.check(lib.cv_vcf_merge_dev(_p(src), TEXT_LEN, n, _p(d[0]), _p(d[1]), _p(d[2]), _p(d[3]), _p(d[4]), a["nruns"], 2, _p(srank), _p(sbeg),
+                                 _p(send), _p(d_ooff), _p(out), total, _p(chunks), _p(stats), _p(info), _p(ws), need.value, _stream()))
+    assert info.cpu().numpy().tolist()[:3:2] == [0, total]
+    got_off = d_ooff.cpu().numpy()
+    assert np.array_equal(got_off[:n + 1], ooff) and got_off[n + 1] == -7
+    assert np.array_equal(srank.cpu().numpy()[:n], a["rank"][order]) and np.array_equal(sbeg.cpu().numpy()[:n], a["pos"][order] - 1)
+    st = stats.cpu().numpy().reshape(4, 2)
+    assert st[0].tolist() == [0, ooff[n_long]] and st[1].tolist() == [ooff[n_long], total] and st[2].tolist() == [n_long, 200]
+    # the text, on the device: the long records slice by slice from the 64 lines, then the short ones
+    lines = src[B.BIG_BASE:B.BIG_BASE + B.BIG_LINES * B.LINE_CAP].view(B.BIG_LINES, B.LINE_CAP)
+    which = torch.from_numpy(line[order[:n_long] - B.BIG_SHORT]).cuda()
+    per = (256 << 20) // B.LINE_CAP
+    for r0 in range(0, n_long, per):
+        r1 = min(r0 + per, n_long)
+        assert torch.equal(out[r0 * B.LINE_CAP:r1 * B.LINE_CAP], lines[which[r0:r1]].view(-1)), r0
+    short = b"".join(mib[int(a["off"][j]) - B.BIG_BASE:int(a["off"][j]) - B.BIG_BASE + int(a["len"][j])].tobytes() for j in order[n_long:])
+    tail = out[n_long * B.LINE_CAP:].cpu().numpy().tobytes()
+    assert tail == short + b"\xa5" * 256 and len(short) == total - n_long * B.LINE_CAP
+    del src, out, lines, which
+    torch.cuda.empty_cache()
 
 
 def _planted_rows():

@@ -2,7 +2,14 @@
 the definition: the .vcf.gz and the .tbi of the device route equal its files byte for byte, with vcf_merge.counts() showing
 where the work ran, so that neither a silent hand-over nor a dropped record can pass.  The arrays of the two entry points
 are compared with cv_vcf_merge_host_form / cv_vcf_windows_host_form (held to the definition and run under the sanitizers
-by test_vcf_merge_core_host.py), with canaries behind every output array."""
+by test_vcf_merge_core_host.py), with canaries behind every output array.
+
+vm_gather assembles the text of 64 output records in an LDS tile when it is at most TILE_TEXT = 16 384 bytes, and writes
+record by record otherwise: tiles of exactly 16 384 and of 16 385 bytes, at output phases 0 and 15, a call whose three
+tiles take the two paths in turn, and an out_cap too small for the text (a range that does not fit is not written, every
+other output is unchanged) -- inputs from tests/vcf_merge_big_cases.py.  The sizes the kernels were written for, past
+their launch caps, are in test_gpu_launch_caps.py, the gather past 2^32 bytes in test_gpu_past_4gib.py.
+Seconds on one MI355X (pytest --durations): each of these eleven cases under 0.005."""
 import ctypes
 import os
 
@@ -112,8 +119,9 @@ class _Guarded(object):
         return b[self.at:self.at + self.size].view(self.dtype)
 
 
-def _dev_call(a, phase=0, ws_shift=0, ws_short=0):
-    """cv_vcf_merge_dev + cv_vcf_windows_dev over line_arrays' dict, every output guarded -> dict like vc.host_form's"""
+def _dev_call(a, phase=0, ws_shift=0, ws_short=0, out_cap=None):
+    """cv_vcf_merge_dev + cv_vcf_windows_dev over line_arrays' dict, every output guarded -> dict like vc.host_form's;
+    out_cap: the room the call is told the output text has (default: all of it; what is not written holds CANARY)"""
     import torch
     from clairvoyante_amd import _lib
     lib = _lib.load()
@@ -132,7 +140,7 @@ def _dev_call(a, phase=0, ws_shift=0, ws_short=0):
     base = ws.data_ptr() + (-ws.data_ptr()) % 256 + ws_shift
     st = _lib.stream_arg(dev)
     _lib.check(lib.cv_vcf_merge_dev(P(text), n_text, n, P(pos), P(run), P(off), P(ln), P(rr), a["nruns"], nrank, g["srank"].ptr, g["sbeg"].ptr,
-                                    g["send"].ptr, g["ooff"].ptr, g["text"].ptr, n_text, g["chunks"].ptr, g["stats"].ptr, g["info"].ptr,
+                                    g["send"].ptr, g["ooff"].ptr, g["text"].ptr, n_text if out_cap is None else out_cap, g["chunks"].ptr, g["stats"].ptr, g["info"].ptr,
                                     ctypes.c_void_p(base), need - ws_short, st))
     torch.cuda.synchronize()
     o = {k: v.read().copy() for k, v in g.items()}
@@ -179,6 +187,46 @@ def test_long_records_take_the_wave_per_record_path():
     o, w = _dev_call(a), vc.host_form(a)
     assert o["info"][0] == 1 == w["info"][0]
     _same(o, w, a["n"], a["n_text"])
+
+
+# ---- the gather's tile line (TILE_TEXT = 16 384 bytes of 64 records), and an output that is too small ---------------------------
+@pytest.mark.parametrize("total,phase", [(16384, 0), (16384, 15), (16385, 0), (16385, 15)])
+def test_a_tile_of_exactly_16384_bytes_and_of_one_more(total, phase):
+    """16 384 bytes fill the LDS tile (at phase 15 it ends at byte 16 399 of its 16 416); 16 385 take the wave-per-record path"""
+    import vcf_merge_big_cases as B
+    a = B.tile_case(total)
+    assert a["n"] == 64 and a["n_text"] == total and B.TILE_TEXT == 16384
+    _same(_dev_call(a, phase), vc.host_form(a), a["n"], a["n_text"])
+
+
+@pytest.mark.parametrize("phase", [0, 3, 15])
+def test_both_paths_write_neighbouring_ranges_of_one_output(phase):
+    import vcf_merge_big_cases as B
+    a = B.three_tile_case()
+    o, w = _dev_call(a, phase), vc.host_form(a)
+    tiles = np.diff(w["ooff"][[0, 64, 128, 192]])
+    assert tiles[0] < B.TILE_TEXT < tiles[1] and tiles[2] < B.TILE_TEXT
+    _same(o, w, a["n"], a["n_text"])
+
+
+@pytest.mark.parametrize("which", ["the first tile's end", "one byte less", "the whole text minus 1", "nothing"])
+def test_an_output_too_small_for_the_text(which):
+    """nothing of a tile's range that does not fit below out_cap is written: the text is the host form's over a buffer of
+    the same sentinel, every other output is what it is with room for all"""
+    import vcf_merge_big_cases as B
+    a = B.three_tile_case()
+    full = vc.host_form(a)
+    first = int(full["ooff"][64])
+    cap, kept = {"the first tile's end": (first, 1), "one byte less": (first - 1, 0), "the whole text minus 1": (a["n_text"] - 1, 2),
+                 "nothing": (0, 0)}[which]
+    o, w = _dev_call(a, 5, out_cap=cap), vc.host_form(a, out_cap=cap, fill=CANARY)
+    edge = int(full["ooff"][64 * kept])
+    assert np.array_equal(o["text"], w["text"][:a["n_text"]])
+    assert np.array_equal(o["text"][:edge], full["text"][:edge]) and (o["text"][edge:] == CANARY).all() and edge <= cap
+    for k in ("info", "ooff", "srank", "sbeg", "send", "stats", "win_off", "win"):
+        assert np.array_equal(o[k][:len(full[k])], full[k][:len(o[k])]) and np.array_equal(w[k], full[k]), k
+    nc = int(full["info"][1])
+    assert np.array_equal(o["chunks"][:, :nc], full["chunks"][:, :nc]) and np.array_equal(w["chunks"], full["chunks"])
 
 
 def test_workspaces_and_arguments_are_refused_with_a_message():

@@ -23,6 +23,18 @@ def test_the_expression_reads_every_spelling():
     assert KERNEL.findall(text) == ["a", "b", "c", "d", "e"]
 
 
+def test_every_device_file_is_listed_once():
+    """a .hip file is the inventory's (FILES) or the compute plane's (OUTSIDE): a new one cannot go by unlisted"""
+    stems = sorted(f[:-4] for f in os.listdir(CSRC) if f.endswith(".hip"))
+    assert len(set(L.FILES)) == len(L.FILES) and len(set(L.OUTSIDE)) == len(L.OUTSIDE)
+    both = sorted(set(L.FILES) & set(L.OUTSIDE))
+    unlisted = sorted(set(stems) - set(L.FILES) - set(L.OUTSIDE))
+    gone = sorted((set(L.FILES) | set(L.OUTSIDE)) - set(stems))
+    assert not both, "in FILES and in OUTSIDE of tests/launch_cap_cases.py: %s" % ", ".join(both)
+    assert not unlisted, "device files neither in FILES nor in OUTSIDE of tests/launch_cap_cases.py: %s" % ", ".join(s + ".hip" for s in unlisted)
+    assert not gone, "listed in tests/launch_cap_cases.py, missing in csrc: %s" % ", ".join(gone)
+
+
 def test_every_kernel_has_an_entry_and_every_entry_a_kernel():
     found = {}
     for stem in L.FILES:
@@ -78,7 +90,13 @@ def test_the_lines_are_the_sources_constants():
                           ("cv_blosc_pack_dev.hip", ("MAX_GRID = 1 << 20",)),
                           ("cv_beditems_dev.hip", ("blocks < 65536 ? blocks : 65536",)),
                           ("cv_bam_dev.hip", ("nwalk < 4096 ? nwalk : 4096",)),
-                          ("cv_inflate_core.hpp", ("CRC_CHUNK = 1024",))):
+                          ("cv_inflate_core.hpp", ("CRC_CHUNK = 1024",)),
+                          ("cv_bgzf_deflate_dev.hip", ("MAX_GRID = 512", "cv_grid_for(members, 1, MAX_GRID)", "cv_grid_for(members, 1, 4096)")),
+                          ("cv_vcfmerge_dev.hip", ("cv_grid_for((n + LANES - 1) / LANES, 1, 1 << 16)", "cv_grid_for(nrank, 1, 1024)")),
+                          ("cv_vcfmerge_core.hpp", ("TILE_TEXT = 16 * 1024", "LANES = 64", "MAX_RANKS = 1 << 20", "POS_BITS = 40"))):
         text = src(stem)
         for needle in needles:
             assert needle in text, (stem, needle)
+    K = L.KERNELS
+    assert K["bd_compress"]["line"] == 512 and K["bd_assemble"]["line"] == 4096 and K["vw_backfill"]["line"] == 1024
+    assert K["vm_gather"]["line"] == (1 << 16) * 64 == 4194304

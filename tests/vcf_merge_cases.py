@@ -168,19 +168,20 @@ def line_arrays(per, names=FAI_NAMES):
             "run_rank": run_rank, "nruns": runs, "names": names, "nrank": max(len(names), 1), "_raw": raw}
 
 
-def host_form(a):
-    """cv_vcf_merge_host_form + cv_vcf_windows_host_form over line_arrays' dict -> dict of every output"""
+def host_form(a, out_cap=None, fill=0):
+    """cv_vcf_merge_host_form + cv_vcf_windows_host_form over line_arrays' dict -> dict of every output; out_cap: the room
+    the call is told the output text has (default: all of it), fill: what the output text holds before the call"""
     import ctypes
     from clairvoyante_amd import _lib
     lib = _lib.load()
     n, nrank = a["n"], a["nrank"]
     V = lambda x: ctypes.c_void_p(x.ctypes.data)
     o = {"srank": np.zeros(max(n, 1), dtype=np.int32), "sbeg": np.zeros(max(n, 1), dtype=np.int64), "send": np.zeros(max(n, 1), dtype=np.int64),
-         "ooff": np.zeros(n + 1, dtype=np.int64), "text": np.zeros(a["n_text"] + 1, dtype=np.uint8),
+         "ooff": np.zeros(n + 1, dtype=np.int64), "text": np.full(a["n_text"] + 1, fill, dtype=np.uint8),
          "chunks": np.zeros((4, max(n, 1)), dtype=np.int64), "stats": np.zeros((4, nrank), dtype=np.int64), "info": np.zeros(8, dtype=np.int64)}
     _lib.check(lib.cv_vcf_merge_host_form(V(a["text"]), a["n_text"], n, V(a["pos"]), V(a["run"]), V(a["off"]), V(a["len"]), V(a["run_rank"]),
                                           a["nruns"], nrank, V(o["srank"]), V(o["sbeg"]), V(o["send"]), V(o["ooff"]), V(o["text"]),
-                                          a["n_text"], V(o["chunks"]), V(o["stats"]), V(o["info"])))
+                                          a["n_text"] if out_cap is None else out_cap, V(o["chunks"]), V(o["stats"]), V(o["info"])))
     count, maxend = o["stats"][2], o["stats"][3]
     o["win_off"] = np.concatenate(([0], np.cumsum(np.where(count > 0, ((maxend - 1) >> 14) + 1, 0)))).astype(np.int64)
     o["win"] = np.zeros(max(int(o["win_off"][-1]), 1), dtype=np.int64)
