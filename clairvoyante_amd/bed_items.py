@@ -14,7 +14,11 @@ slab by slab (plain text memory-mapped, BGZF inflated on the device, an ordinary
 gives every line a verdict (cv_item_lines_dev), keeps the rows the BED covers and gathers their bytes
 (cv_items_keep_dev).  A line only the definition answers (HOST) hands the REST of the file to the host's per-line function
 from that slab's first unconsumed line on: what has been written, the counts and the exception raised are the host loop's.
-Sampling walks [start, end) in tiles of SAMPLE_TILE positions (cv_sample_positions_dev)."""
+Sampling walks [start, end) in tiles of SAMPLE_TILE positions (cv_sample_positions_dev).
+
+_PairWalk is the device side of PairWithNonVariants (CV_PAIR=device): the same line pass over both tensor files, the
+kernels of the training-set builders for the BED test, the truth look-up and the pairing, and cv_items_copy_dev, the gather
+above fed with lengths the caller chose.  There a HOST line hands the WHOLE call to the loop, before anything is written."""
 import ctypes
 import itertools
 import os
@@ -284,6 +288,217 @@ class _ItemWalk(object):
             rest, chunks = walk.rest(e.at)
             e.blocks = itertools.chain([rest], _host_blocks(chunks))
             raise
+
+
+# ---- PairWithNonVariants on the device: existing kernels composed (PairWithNonVariants.Pair chooses the route) -------------
+PAIR_RESIDENT_BYTES = None          # tests: text of one file that may stay in HBM between the two passes (None: half of what is free)
+_KEY_BITS = 40                      # a position of at most 12 digits is below 2^40: (contig id << 40 | position) is one int64
+
+
+class _PairFile(object):
+    """what the counting pass keeps of one tensor file: per row the contig id and the position (and, for candidates, the
+    usable flag); per line pass a unit (rows, bytes, buffer, offsets, lengths) -- buffer, offsets and lengths only while
+    the file's text stays resident"""
+
+    def __init__(self, fn, room):
+        self.fn, self.room = fn, room
+        self.ctg, self.pos, self.usable, self.units = [], [], [], []
+        self.rows = self.held = 0
+        self.resident, self.cur = True, None
+
+    def saw(self, buf):
+        """a new buffer of the walk: does the file's text still fit?"""
+        if buf is not self.cur:
+            self.cur = buf
+            self.held += int(buf.numel())
+            if self.resident and self.held > self.room:
+                self.resident = False
+                self.units = [(rows, used, None, None, None) for rows, used, _b, _o, _l in self.units]
+
+    def column(self, torch, parts, dtype, device):
+        return torch.cat(parts) if parts else torch.empty(0, dtype=dtype, device=device)
+
+
+class _PairWalk(object):
+    """The device side of PairWithNonVariants.Pair.  Nothing here is a kernel of its own: the BED through
+    _TruthReader.bed_table, both tensor files slab by slab through cv_item_lines_dev, the BED test and the truth look-up
+    of the candidates through cv_trainset_join, ONE cv_bamtrain_pair over the rows of both files, the written lines
+    through cv_items_copy_dev; torch for the glue (the truth keys sorted and made unique, the edge bytes of every line).
+    _TruthHandOver wherever only the loop answers: every verdict is known before the first byte is written, so the WHOLE
+    call is Pair_host's then."""
+
+    def __init__(self, device, bed_fn):
+        import torch
+        self.torch, self.device = torch, device
+        self.rd = _TruthReader(device)
+        self.lib, self.st = self.rd.lib, _lib.stream_arg(device)
+        self.E = lambda n, dt=torch.int64: torch.empty(n, dtype=dt, device=device)
+        self.has_bed = bed_fn is not None
+        self.bed_lines = 0
+        if self.has_bed:
+            self.bed_off, self.bed_begin, self.bed_emax, self.bed_lines, _nctg = self.rd.bed_table(bed_fn)     # (its intervals)
+            torch.cuda.current_stream(device).synchronize()   # (the workspace and the rows may go)
+        self.var = self.can = None
+
+    # -- one line pass, for both passes over a file
+    def _lines(self, buf, at, n, max_lines):
+        """cv_item_lines_dev over buf[at:at + n] -> (used, lines, rows, runs, pos, run, offsets into buf, lengths, tok)"""
+        torch, lib, P, E = self.torch, self.lib, _lib.ptr, self.E
+        need = _lib.workspace(lib.cv_item_lines_workspace, n, max_lines)
+        ws = E(need, torch.uint8)
+        pos, run, off, ln = E(max_lines), E(max_lines, torch.int32), E(max_lines), E(max_lines)
+        tok, info_dev = E((max_lines, 2)), E(8)
+        with _Timer(torch, "pair_lines") as tm:
+            _lib.check(lib.cv_item_lines_dev(ctypes.c_void_p(buf.data_ptr() + at), n, max_lines, P(pos), P(run), P(off), P(ln), P(tok),
+                                             P(info_dev), P(ws), need, self.st))
+        used, lines, rows, _skipped, host, runs = info_dev.cpu().tolist()[:6]
+        tm.read()
+        if host:
+            raise _TruthHandOver("%d line(s) only the host loop defines the result for (a blank line, fewer than two tokens, a "
+                                 "position that is not canonical decimal, '\\r', bytes outside printable ASCII, ...)" % host)
+        return used, lines, rows, runs, pos[:rows], run[:rows], off[:rows] + at, ln[:rows].clone(), tok
+
+    def _walk(self, f, line_pass):
+        slab_bytes = max(int(utils_v2.TRUTH_SLAB_BYTES), 1)
+        state = {"bytes_per_line": 16.0}                     # (both passes over a file start alike: they cut the same units)
+
+        def slab(buf, lo, hi, _padded_end):                  # (the newline the walk gives the last line is written, as strip() + "\n" is)
+            def one(at, n, max_lines):
+                used, lines = line_pass(buf, at, n, max_lines)
+                if lines:
+                    state["bytes_per_line"] = max(used / float(lines), 2.0)
+                return used, lines
+            return _while_table_full(lo, hi, lambda n: min(int(n / state["bytes_per_line"] * 1.25) + 1024, n), one)
+
+        _SlabWalk(self.torch, self.device, _truth_chunks(f.fn, slab_bytes), slab_bytes, self.rd._inflate, pad_always=False,
+                  join_unbroken=True, whole_lines=True).run(slab)
+
+    def _count(self, fn, on_rows):
+        """the counting pass over one file: on_rows(f, rows, pos, run, run_ctg, runs) per line pass with rows"""
+        torch = self.torch
+        room = PAIR_RESIDENT_BYTES
+        if room is None:
+            room = torch.cuda.mem_get_info(self.device)[0] // 2
+        f = _PairFile(fn, room)
+
+        def line_pass(buf, at, n, max_lines):
+            used, lines, rows, runs, pos, run, off, ln, tok = self._lines(buf, at, n, max_lines)
+            f.saw(buf)
+            if rows:
+                # the device writes a line's raw bytes: they are strip() + "\n" only without a blank at either edge
+                edge = buf[torch.cat((off, off + ln - 2))]
+                if bool(((edge == 32) | (edge == 9)).any()):
+                    raise _TruthHandOver("a line with white space at either edge: the host loop strips it")
+                ids = [self.rd.contigs.id_of(name) for name in self.rd.run_names(buf, at, n, tok, runs)]
+                run_ctg = torch.from_numpy(np.array(ids, dtype=np.int32)).to(self.device)
+                on_rows(f, rows, pos, run, run_ctg, runs)
+                f.pos.append(pos.clone())
+                f.units.append((rows, used, buf, off, ln) if f.resident else (rows, used, None, None, None))
+                f.rows += rows
+            return used, lines
+
+        self._walk(f, line_pass)
+        torch.cuda.current_stream(self.device).synchronize()
+        f.ctg = f.column(torch, f.ctg, torch.int32, self.device)
+        f.pos = f.column(torch, f.pos, torch.int64, self.device)
+        return f
+
+    def count_variants(self, fn):
+        """v, and the truth keys of all contigs as the tables cv_trainset_join reads (a duplicate row counts in v, once here)"""
+        torch = self.torch
+        self.var = f = self._count(fn, lambda f, rows, pos, run, run_ctg, runs: f.ctg.append(run_ctg[run.long()]))
+        self.ntab = ntab = len(self.rd.names)
+        keys = torch.unique((f.ctg.to(torch.int64) << _KEY_BITS) | f.pos)
+        self.truth_pos = keys & ((1 << _KEY_BITS) - 1)
+        self.truth_off = torch.searchsorted(keys, torch.arange(ntab + 1, dtype=torch.int64, device=self.device) << _KEY_BITS)
+        # a contig the truth file brought has no BED interval: an empty table, so the BED test drops it as the loop does
+        off = self.bed_off if self.has_bed else torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.tab_off = torch.cat((off, off[-1:].expand(ntab + 1 - int(off.numel())))) if off.numel() < ntab + 1 else off
+        one = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.tab_begin = self.bed_begin if self.has_bed and self.bed_begin.numel() else one
+        self.tab_emax = self.bed_emax if self.has_bed and self.bed_emax.numel() else one
+        return f.rows
+
+    def count_candidates(self, fn):
+        """per candidate row the contig id and usable = the BED keeps it (when there is one) and no truth row has its key"""
+        torch, lib, P, E = self.torch, self.lib, _lib.ptr, self.E
+
+        def on_rows(f, rows, pos, run, run_ctg, runs):
+            ctg, keep, truth = E(rows, torch.int32), E(rows, torch.uint8), E(rows, torch.int32)
+            with _Timer(torch, "pair_join") as tm:
+                _lib.check(lib.cv_trainset_join(rows, P(run), P(run_ctg), runs, P(pos), self.ntab, 1 if self.has_bed else 0,
+                                                P(self.tab_off), P(self.tab_begin), P(self.tab_emax),
+                                                P(self.truth_off) if self.truth_pos.numel() else None, P(self.truth_pos),
+                                                P(ctg), P(keep), P(truth), self.st))
+            f.ctg.append(ctg)
+            f.usable.append(keep & (truth < 0).to(torch.uint8))
+            tm.read()
+
+        self.can = f = self._count(fn, on_rows)
+        f.usable = f.column(torch, f.usable, torch.uint8, self.device)
+        return f.rows
+
+    def pair(self, seed, amp):
+        """one cv_bamtrain_pair over the variant rows (truth centres, kept) and the candidate rows (keep = usable)
+        -> (v, c, r, picked); the candidates' verdicts stay in self.keep"""
+        torch, P = self.torch, _lib.ptr
+        v, n = self.var.rows, self.var.rows + self.can.rows
+        self.keep = torch.cat((torch.ones(v, dtype=torch.uint8, device=self.device), self.can.usable))
+        if n == 0:
+            return 0, 0, 1.0, 0
+        flags = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        flags[:v] = 1                                        # CV_CENTRE_TRUTH
+        acgt = torch.ones(n, dtype=torch.uint8, device=self.device)
+        ctg, pos = torch.cat((self.var.ctg, self.can.ctg)), torch.cat((self.var.pos, self.can.pos))
+        h = np.array([draws.fnv1a32(nm) for nm in self.rd.names], dtype=np.uint32).view(np.int32)
+        h_dev = torch.from_numpy(h).to(self.device)
+        counts, r = torch.zeros(4, dtype=torch.int64, device=self.device), torch.zeros(1, dtype=torch.float64, device=self.device)
+        with _Timer(torch, "pair_draw") as tm:
+            _lib.check(self.lib.cv_bamtrain_pair(n, P(ctg), P(pos), P(flags), P(acgt), P(h_dev), len(self.rd.names), int(seed), float(amp),
+                                                 P(self.keep), P(counts), P(r), self.st))
+        got_v, c, picked, kept = counts.cpu().tolist()
+        tm.read()
+        if got_v != v or kept != v + picked:
+            raise _lib.CvError("cv_bamtrain_pair: %d truth rows and %d kept rows where %d and %d were expected" % (got_v, kept, v, v + picked))
+        return v, c, float(r.item()), picked
+
+    def gather(self, f, keep, write):
+        """the kept lines of one file in file order through cv_items_copy_dev, unit by unit -> lines written.  keep: the
+        file's rows' verdicts (uint8); write(tensor of bytes in HBM).  A file whose text did not stay resident is walked again."""
+        torch, lib, P, E = self.torch, self.lib, _lib.ptr, self.E
+        done = {"unit": 0, "row": 0, "lines": 0}
+
+        def unit(buf, off, ln, rows, used):
+            k = keep[done["row"]:done["row"] + rows]
+            kept_len = ln * k
+            need = _lib.workspace(lib.cv_items_copy_workspace, rows)
+            ws, out, cnt = E(need, torch.uint8), E(used, torch.uint8), E(4)
+            with _Timer(torch, "pair_copy") as tm:
+                _lib.check(lib.cv_items_copy_dev(P(buf), int(buf.numel()), rows, P(off), P(kept_len), P(out), used, P(cnt), P(ws), need,
+                                                 self.st))
+            nbytes, lines = cnt.cpu().tolist()[2], int(k.sum())
+            tm.read()
+            if nbytes > used:
+                raise _lib.CvError("cv_items_copy_dev: %d bytes kept of a unit of %d" % (nbytes, used))
+            if nbytes:
+                write(out[:nbytes])
+            done["unit"] += 1; done["row"] += rows; done["lines"] += lines
+
+        if f.resident:
+            for rows, used, buf, off, ln in f.units:
+                unit(buf, off, ln, rows, used)
+        else:
+            def line_pass(buf, at, n, max_lines):
+                used, lines, rows, _runs, _pos, _run, off, ln, _tok = self._lines(buf, at, n, max_lines)
+                if rows:
+                    if done["unit"] >= len(f.units) or f.units[done["unit"]][:2] != (rows, used):
+                        raise _lib.CvError("%s changed between the two passes of PairWithNonVariants" % f.fn)
+                    unit(buf, off, ln, rows, used)
+                return used, lines
+            self._walk(f, line_pass)
+        if done["row"] != f.rows:
+            raise _lib.CvError("%s changed between the two passes of PairWithNonVariants" % f.fn)
+        return done["lines"]
 
 
 def _host_blocks(chunks):

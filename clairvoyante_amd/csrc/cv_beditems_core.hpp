@@ -8,6 +8,7 @@
 //   copy_lane     one lane's share of a line copied by a wave of 64 lanes (see cv_beditems_dev.hip for the form)
 //   sample_keep   "in an interval, when there are intervals, and u(pos) <= prob"
 //   lines_host_form / keep_host_form   the two slab passes on the CPU, in the layout of the *_dev calls
+//   copy_fits / copy_host_form         the bounds test of one copied line; the gather by given lengths on the CPU
 #pragma once
 #include <stdint.h>
 #include "cv_draw_core.hpp"
@@ -148,6 +149,29 @@ inline void keep_host_form(const uint8_t *text, int64_t len, int64_t n, const in
         bytes += llen[i];
     }
     counts[0] = n; counts[1] = kept; counts[2] = bytes; counts[3] = 0;
+}
+
+// "m bytes at src offset s of a text of len bytes and at dst offset d of a room of cap bytes lie inside both", without a sum
+// that could overflow on a caller's wrong length
+CVT_FN bool copy_fits(int64_t s, int64_t m, int64_t len, int64_t d, int64_t cap)
+{
+    return m > 0 && m <= len && s >= 0 && s <= len - m && m <= cap && d >= 0 && d <= cap - m;
+}
+
+// Host form of cv_items_copy_dev: the running sum of the given lengths places the lines (0: the line is not kept; a negative
+// length is the caller's error, never copied, and the sum takes it as the device's scan does), the copy lane by lane where
+// the line lies inside the text and fits the room
+inline void copy_host_form(const uint8_t *text, int64_t len, int64_t n, const int64_t *off, const int64_t *kept_len, uint8_t *out_text,
+                           int64_t out_cap, int64_t *counts)
+{
+    uint64_t bytes = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t m = kept_len[i];
+        if (copy_fits(off[i], m, len, (int64_t)bytes, out_cap))
+            for (int lane = 0; lane < WAVE; ++lane) copy_lane(out_text + bytes, text + off[i], m, lane);
+        bytes += (uint64_t)m;
+    }
+    counts[0] = 0; counts[1] = 0; counts[2] = (int64_t)bytes; counts[3] = 0;
 }
 
 }  // namespace cvb

@@ -21,6 +21,9 @@
 //                       source and destination agree modulo 16 behind a byte head, consecutive aligned 4-byte stores fed by
 //                       byte loads where they do not, and single bytes for lines under 64 bytes.
 //
+//   per slab, for a caller that has the verdicts already (cv_items_copy_dev; PairWithNonVariants' device route):
+//   the caller's kept lengths (0: not kept) copied in front of a zero, hipcub ExclusiveSum, ik_copy -- no kernel of its own
+//
 //   per tile of positions (cv_sample_positions_dev):
 //   sp_flags            stabbing test and keyed draw per position; hipcub ExclusiveSum; sp_emit writes the kept positions
 //                       ascending, as far as `cap` reaches, and both counts
@@ -153,7 +156,7 @@ __global__ __launch_bounds__(THREADS) void ik_copy(const uint8_t *text, int64_t 
         const int64_t m = kept_len[i];
         if (m <= 0) continue;
         const int64_t s = off[i], d = dst_at[i];
-        if (s < 0 || s + m > len || d + m > out_cap) continue;        // (the caller's error: nothing outside either buffer is touched)
+        if (!cvb::copy_fits(s, m, len, d, out_cap)) continue;         // (the caller's error: nothing outside either buffer is touched)
         cvb::copy_lane(out_text + d, text + s, m, lane);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) counts[2] = dst_at[n];
@@ -374,6 +377,67 @@ extern "C" int cv_items_keep_host_form(const char *text, int64_t len, int64_t n,
         return 1;
     cvb::keep_host_form((const uint8_t *)text, len, n, pos, run, off, llen, run_ctg, nruns, nctg, bed_off, bed_begin, bed_emax, want_text,
                         (uint8_t *)out_text, out_cap, counts);
+    return 0;
+}
+
+// ---- the gather by given lengths: cv_items_keep_dev without ik_flags --------------------------------------------------------
+static bool copy_pointers_ok(const char *who, const char *text, int64_t len, int64_t n, const int64_t *off, const int64_t *kept_len,
+                             const char *out_text, int64_t out_cap, const int64_t *counts)
+{
+    if (!counts || (len > 0 && !text) || (n > 0 && (!off || !kept_len)) || (out_cap > 0 && !out_text)) {
+        cv_set_error("%s: null argument", who);
+        return false;
+    }
+    if (((uintptr_t)off & 7) || ((uintptr_t)kept_len & 7) || ((uintptr_t)counts & 7)) {
+        cv_set_error("%s: the int64 arrays must be 8-byte aligned", who);
+        return false;
+    }
+    return true;
+}
+
+extern "C" int cv_items_copy_workspace(int64_t n, int64_t *bytes)
+{
+    if (!bytes) { cv_set_error("cv_items_copy_workspace: null argument"); return 1; }
+    if (!keep_args_ok("cv_items_copy_workspace", 0, n, 0, 0, 0)) return 1;
+    cv_carver c;
+    keep_ws W;
+    if (keep_plan(c, n, &W)) return 1;
+    *bytes = (int64_t)c.total();
+    return 0;
+}
+
+extern "C" int cv_items_copy_dev(const char *text_dev, int64_t len, int64_t n, const int64_t *off_dev, const int64_t *kept_len_dev,
+                                 char *out_text_dev, int64_t out_cap, int64_t *counts_dev, void *workspace_dev, int64_t workspace_bytes,
+                                 void *stream)
+{
+    if (!keep_args_ok("cv_items_copy_dev", len, n, 0, 0, out_cap)) return 1;
+    if (!copy_pointers_ok("cv_items_copy_dev", text_dev, len, n, off_dev, kept_len_dev, out_text_dev, out_cap, counts_dev)) return 1;
+    cv_carver c(workspace_dev);
+    keep_ws W;
+    if (keep_plan(c, n, &W)) return 1;
+    if (!cv_workspace_ok("cv_items_copy_dev", workspace_dev, workspace_bytes, c.total())) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    int64_t *kept_len = W.kept_len, *dst_at = W.dst_at;
+    CV_HIP(hipMemsetAsync(counts_dev, 0, 4 * sizeof(int64_t), st));
+    // the scan reads n + 1 values (its last output is the sum): the caller's n lengths and a zero behind them
+    if (n > 0) { CV_HIP(hipMemcpyAsync(kept_len, kept_len_dev, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, st)); }
+    CV_HIP(hipMemsetAsync(kept_len + n, 0, sizeof(int64_t), st));
+    size_t tb = W.tmp_bytes;
+    CV_HIP(hipcub::DeviceScan::ExclusiveSum(W.tmp, tb, (const int64_t *)kept_len, dst_at, (int)(n + 1), st));
+    const int64_t blocks = (n + THREADS / cvb::WAVE - 1) / (THREADS / cvb::WAVE);
+    hipLaunchKernelGGL(ik_copy, dim3((unsigned)(blocks < 1 ? 1 : blocks < 65536 ? blocks : 65536)), dim3(THREADS), 0, st,
+                       (const uint8_t *)text_dev, len, n, off_dev, (const int64_t *)kept_len, (const int64_t *)dst_at,
+                       (uint8_t *)out_text_dev, out_cap, counts_dev);
+    CV_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int cv_items_copy_host_form(const char *text, int64_t len, int64_t n, const int64_t *off, const int64_t *kept_len,
+                                       char *out_text, int64_t out_cap, int64_t *counts)
+{
+    if (!keep_args_ok("cv_items_copy_host_form", len, n, 0, 0, out_cap)) return 1;
+    if (!copy_pointers_ok("cv_items_copy_host_form", text, len, n, off, kept_len, out_text, out_cap, counts)) return 1;
+    cvb::copy_host_form((const uint8_t *)text, len, n, off, kept_len, (uint8_t *)out_text, out_cap, counts);
     return 0;
 }
 

@@ -560,6 +560,17 @@ int cv_truth_tables_dev(int64_t n, const int64_t *pos_dev, const float *label_de
  * bytes, 0}; without want_text neither the sum nor the copy runs and kept bytes is 0.
  * cv_items_keep_host_form: the same on the CPU, the copy lane by lane.
  *
+ * cv_items_copy_dev, over n lines of one slab whose verdicts the caller has already (PairWithNonVariants' device route:
+ * the pairing decides over the rows of whole files, the gather runs per slab): cv_items_keep_dev's gather without its
+ * BED test.  off_dev[n] = offset of each line's first byte in text_dev[0, len), kept_len_dev[n] = its length when it is
+ * kept, 0 when it is not.  The kept lines' bytes go to out_text_dev[0, out_cap) in order, one behind the other: the
+ * lengths are copied into the workspace, an exclusive sum places them, and the SAME copy kernel moves them (one wave per
+ * line).  A line that does not lie inside the text, or would not fit the room, is not copied, and a negative length is
+ * the caller's error and never copied: nothing outside either buffer is touched.  counts_dev[4] = {0, 0, sum of the
+ * lengths, 0} (the layout of cv_items_keep_dev's counters; the caller knows its rows).  Asynchronous on `stream`, the
+ * workspace (cv_items_copy_workspace(n)) is the caller's and belongs to the call until its launches have run.
+ * cv_items_copy_host_form: the same bytes and counters from the same core on the CPU.
+ *
  * cv_sample_positions_dev, one tile of positions first .. first + count - 1 of the contig whose name hashes to h
  * (FNV-1a-32): a position is kept when the contig's sorted table bed_begin_dev / bed_emax_dev[nbed] covers it (nbed = 0:
  * no BED, every position passes) and cv_draw(seed, 2, h, pos, 0) <= prob in double.  The kept positions go to
@@ -583,6 +594,12 @@ int cv_items_keep_host_form(const char *text, int64_t len, int64_t n, const int6
                             const int64_t *llen, const int32_t *run_ctg, int64_t nruns, int32_t nctg, const int64_t *bed_off,
                             const int64_t *bed_begin, const int64_t *bed_emax, int want_text, char *out_text, int64_t out_cap,
                             int64_t *counts);
+int cv_items_copy_workspace(int64_t n, int64_t *bytes);
+int cv_items_copy_dev(const char *text_dev, int64_t len, int64_t n, const int64_t *off_dev, const int64_t *kept_len_dev,
+                      char *out_text_dev, int64_t out_cap, int64_t *counts_dev, void *workspace_dev, int64_t workspace_bytes,
+                      void *stream);
+int cv_items_copy_host_form(const char *text, int64_t len, int64_t n, const int64_t *off, const int64_t *kept_len,
+                            char *out_text, int64_t out_cap, int64_t *counts);
 int cv_sample_positions_workspace(int64_t count, int64_t *bytes);
 int cv_sample_positions_dev(uint64_t seed, uint32_t h, int64_t first, int64_t count, double prob, int64_t nbed,
                             const int64_t *bed_begin_dev, const int64_t *bed_emax_dev, int64_t *out_pos_dev, int64_t cap,
