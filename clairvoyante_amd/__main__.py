@@ -8,8 +8,8 @@ import sys
 SUBMODULES = ("callVarBamParallel", "callVarBam", "callVar", "calTrainDevDiff", "evaluateListOfModels", "evaluate",
               "tensor2Bin", "trainNonstop", "train", "trainWithoutValidationNonstop", "CreateTensor",
               "ExtractVariantCandidates", "GetTruth", "PairWithNonVariants", "ChooseItemInBed", "CountNumInBed",
-              "RandomSampling", "CombineMultipleDatasetsForTraining", "MergeVcf")
-NOT_BUILT = ("demoRun", "getEmbedding", "getTensorAndLayerPNG")
+              "RandomSampling", "CombineMultipleDatasetsForTraining", "MergeVcf", "getEmbedding", "getTensorAndLayerPNG")
+NOT_BUILT = ("demoRun",)
 
 
 def main():

@@ -314,12 +314,13 @@ extern "C" int cv_get_option(const cv_model *m, const char *key, int64_t *value)
     return 1;
 }
 
-extern "C" int cv_forward(cv_model *m, const float *x_dev, int64_t n, float *out16_dev, void *stream)
+// cv_forward / cv_forward_logits: the batch in chunks of the pass workspace, each through the kernels of option impl
+static int forward_chunks(cv_model *m, const float *x_dev, int64_t n, float *out16_dev, void *stream, bool logits, const char *who)
 {
-    if (!m) { cv_set_error("cv_forward: null model"); return 1; }
-    if (n < 0) { cv_set_error("cv_forward: negative batch"); return 1; }
+    if (!m) { cv_set_error("%s: null model", who); return 1; }
+    if (n < 0) { cv_set_error("%s: negative batch", who); return 1; }
     if (n == 0) return 0;    // the reference runs predict on an empty final batch (utils_v2.py:56-59)
-    if (!x_dev || !out16_dev) { cv_set_error("cv_forward: null buffer"); return 1; }
+    if (!x_dev || !out16_dev) { cv_set_error("%s: null buffer", who); return 1; }
     CV_HIP(hipSetDevice(m->device));
     hipStream_t st = (hipStream_t)stream;
     const int64_t chunk = m->impl ? m->chunk : (m->chunk < 4096 ? m->chunk : 4096);
@@ -327,8 +328,48 @@ extern "C" int cv_forward(cv_model *m, const float *x_dev, int64_t n, float *out
         int64_t cn = n - off < chunk ? n - off : chunk;
         const float *xc = x_dev + (size_t)off * (CV_INPUT_H * CV_INPUT_W * CV_INPUT_C);
         float *oc = out16_dev + (size_t)off * CV_NUM_OUT;
-        int rc = m->impl ? cv_mfma_forward(m, xc, cn, oc, st) : cv_ref_forward(m, xc, cn, oc, st);
+        int rc = m->impl ? cv_mfma_forward(m, xc, cn, oc, st, logits) : cv_ref_forward(m, xc, cn, oc, st, logits);
         if (rc) return rc;
+    }
+    return 0;
+}
+
+extern "C" int cv_forward(cv_model *m, const float *x_dev, int64_t n, float *out16_dev, void *stream)
+{
+    return forward_chunks(m, x_dev, n, out16_dev, stream, false, "cv_forward");
+}
+
+extern "C" int cv_forward_logits(cv_model *m, const float *x_dev, int64_t n, float *out16_dev, void *stream)
+{
+    return forward_chunks(m, x_dev, n, out16_dev, stream, true, "cv_forward_logits");
+}
+
+// Per chunk: the forward pass itself (so that the pass workspace, cv_kernel_name and cv_get_activation are left exactly
+// as by cv_forward), then ONE plain launch that convolves the pooled map below -- or x -- straight into the caller's
+// buffer.  The pass needs somewhere to put its 16 outputs per candidate: the head of the chunk's own region of dst_dev
+// (at least 33 * 4 * 8 floats per candidate), which the launch behind it on the stream overwrites.
+extern "C" int cv_forward_conv_map(cv_model *m, const float *x_dev, int64_t n, int layer, float *dst_dev, void *stream)
+{
+    if (!m) { cv_set_error("cv_forward_conv_map: null model"); return 1; }
+    if (layer < 1 || layer > 3) { cv_set_error("cv_forward_conv_map: layer %d not in 1..3", layer); return 1; }
+    if (n < 0) { cv_set_error("cv_forward_conv_map: negative batch"); return 1; }
+    if (n == 0) return 0;
+    if (!x_dev || !dst_dev) { cv_set_error("cv_forward_conv_map: null buffer"); return 1; }
+    CV_HIP(hipSetDevice(m->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int l = layer - 1;
+    const size_t per = (size_t)m->sh.hc[l] * 4 * m->arch.cout[l];      // floats of the map per candidate (>= CV_NUM_OUT)
+    const int64_t chunk = m->impl ? m->chunk : (m->chunk < 4096 ? m->chunk : 4096);
+    for (int64_t off = 0; off < n; off += chunk) {
+        int64_t cn = n - off < chunk ? n - off : chunk;
+        const float *xc = x_dev + (size_t)off * (CV_INPUT_H * CV_INPUT_W * CV_INPUT_C);
+        float *dc = dst_dev + (size_t)off * per;
+        if (m->impl) {
+            if (cv_mfma_forward(m, xc, cn, dc, st) || cv_mfma_conv_map(m, xc, cn, layer, dc, st)) return 1;
+        } else {
+            if (cv_ref_forward(m, xc, cn, dc, st)) return 1;
+            if (cv_conv_map_plain(m, layer, l == 0 ? xc : m->r_p[l - 1], nullptr, cn, dc, st)) return 1;
+        }
     }
     return 0;
 }

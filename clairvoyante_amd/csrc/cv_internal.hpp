@@ -202,11 +202,16 @@ int cv_layout_current(const cv_model *m, unsigned layout, const char *who);    /
 #define CV_GRAD_HEADER 16     // floats in front of the flat gradient: the loss header (cv_train.hip)
 
 // kernel launchers (defined in the .hip files)
-int cv_ref_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStream_t st);
-int cv_mfma_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStream_t st);
+// logits (cv_forward_logits): the same kernel forms with the logits epilogue on the one that computes the heads
+int cv_ref_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStream_t st, bool logits = false);
+int cv_mfma_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStream_t st, bool logits = false);
+// cv_forward_conv_map behind a pass over the same chunk: the plain convolution over the pooled map below (in natural
+// or in_tm tile-major), and the tile path's side of it (cv_kernels_mfma.hip: makes pool1 where the pass fused it away)
+int cv_conv_map_plain(cv_model *m, int layer, const float *in, const float *in_tm, int64_t n, float *dst, hipStream_t st);
+int cv_mfma_conv_map(cv_model *m, const float *x, int64_t n, int layer, float *dst, hipStream_t st);
 int cv_pack_weights(cv_model *m, hipStream_t st);
 int cv_launch_heads(cv_model *m, const float *h4, const float *h5, int tm, int64_t n, float *out16,
-                    hipStream_t st);
+                    hipStream_t st, bool logits = false);
 bool cv_tile_supported(const cv_model *m);
 int cv_pack_train_weights(cv_model *m, hipStream_t st);
 // what a training pass over G groups will read and is stale; sw (== st: all of it on st) already runs behind st

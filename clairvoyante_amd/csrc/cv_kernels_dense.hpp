@@ -47,6 +47,9 @@ __device__ __forceinline__ void pack_heads(int64_t t, const float *__restrict__ 
 
 // Epilogue of the heads: a0 = base-head tile (rows 0..3 on q = 0), a1 = zygosity / type / length tile; sigmoid,
 // softmax(selu(.) + 1e-10) per head in registers (the 6-way softmax spans lanes c+32 / c+48), 16 outputs per candidate.
+// LOGITS (cv_forward_logits): the three softmax heads leave selu(.) + 1e-10 itself -- the same values up to there, then
+// no max, exp, sum or divide and nothing crosses lanes; the base head's sigmoid is unchanged.
+template <bool LOGITS = false>
 __device__ __forceinline__ void heads_finish(f4 a0, f4 a1, const float *__restrict__ bb, const float *__restrict__ bz,
                                              const float *__restrict__ bt, const float *__restrict__ bl, int64_t n,
                                              float *__restrict__ out16, int g, int lane)
@@ -64,6 +67,23 @@ __device__ __forceinline__ void heads_finish(f4 a0, f4 a1, const float *__restri
     for (int r = 0; r < 4; r++) lg[r] = cvm::selu(a1[r] + bias1[r]) + 1e-10f;
     const int64_t cand = (int64_t)g * 16 + c;
     float *o = out16 + (size_t)cand * 16;
+    if constexpr (LOGITS) {
+        if (cand >= n) return;
+        if (q == 0) {
+            float4 b;
+            b.x = cvm::sigmoid(a0[0] + bb[0]); b.y = cvm::sigmoid(a0[1] + bb[1]);
+            b.z = cvm::sigmoid(a0[2] + bb[2]); b.w = cvm::sigmoid(a0[3] + bb[3]);
+            *reinterpret_cast<float4 *>(o) = b;
+            o[4] = lg[0]; o[5] = lg[1];
+        } else if (q == 1) {
+            o[6] = lg[0]; o[7] = lg[1]; o[8] = lg[2]; o[9] = lg[3];
+        } else if (q == 2) {
+            o[10] = lg[0]; o[11] = lg[1]; o[12] = lg[2]; o[13] = lg[3];
+        } else {
+            o[14] = lg[0]; o[15] = lg[1];
+        }
+        return;
+    }
     // 6-way softmax across lanes q=2 (len0..3) and q=3 (len4..5)
     float m_loc = q == 3 ? fmaxf(lg[0], lg[1]) : fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
     float m_oth = __shfl_xor(m_loc, 16);
@@ -101,6 +121,7 @@ __device__ __forceinline__ void heads_finish(f4 a0, f4 a1, const float *__restri
         }
     }}
 
+template <bool LG = false>        // LG: the logits epilogue (heads_finish<true>)
 __global__ __launch_bounds__(256) void heads_tm(const f4 *__restrict__ h4, const f4 *__restrict__ h5, int NB4,
                                                  int NB5, const f4 *__restrict__ wp0, const f4 *__restrict__ wp1,
                                                  const float *__restrict__ bb, const float *__restrict__ bz,
@@ -128,7 +149,7 @@ __global__ __launch_bounds__(256) void heads_tm(const f4 *__restrict__ h4, const
 #pragma unroll
         for (int s = 0; s < 4; s++) a1 = mfma4(A[s], B[s], a1);
     }
-    heads_finish(a0, a1, bb, bz, bt, bl, n, out16, g, lane);
+    heads_finish<LG>(a0, a1, bb, bz, bt, bl, n, out16, g, lane);
 }
 
 // operands of the heads when they ride on the fc5 kernel (dense_tm EPI 2)
@@ -172,7 +193,7 @@ struct heads_args {
 // WAVES (round 6) = groups per workgroup, 8 or 4: the 112 KB of LDS allow one workgroup per CU whatever its size, so a pass
 // of up to 2 048 groups took the time of 2 048 (8 groups on each of G / 8 CUs, the other CUs idle); with fewer waves per
 // workgroup the same groups spread over more CUs (each wave then stages 8 / WAVES of a position's k fragments).
-template <int WAVES>
+template <int WAVES, bool LG = false>
 __global__ __launch_bounds__(WAVES * 64, 2) void conv3fc4_slim(const f4 *__restrict__ in_tm, const f4 *__restrict__ wp3,
                                                         const float *__restrict__ bias3, int cout3,
                                                         const f4 *__restrict__ wp4, const float *__restrict__ bias4,
@@ -348,7 +369,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv3fc4_slim(const f4 *__restr
 #pragma unroll
         for (int s4 = 0; s4 < 4; s4++) a1 = mfma4(A[s4], h5[ob][s4], a1);
     }
-    heads_finish(a0, a1, hd.bb, hd.bz, hd.bt, hd.bl, n_cand, out16, g, lane);
+    heads_finish<LG>(a0, a1, hd.bb, hd.bz, hd.bt, hd.bl, n_cand, out16, g, lane);
 }
 
 
@@ -372,7 +393,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv3fc4_slim(const f4 *__restr
 // DMA pieces behind its first MFMA block -- no LDS round trip between a barrier and the first MFMA.  Bit-identical; the
 // training step did not move: 2.1163 against 2.1167 ms at 10 000, three alternating runs each on one box,
 // profiles/r04/train_ab_fc4_forward_ring.txt.  The step behind a barrier is not what the kernel waits for; removed.)
-template <int NB, int WAVES, int EPI = 0, int GR = 1>
+// LG (EPI 2 / 3 only): the heads leave their logits (heads_finish<true>, cv_forward_logits).
+template <int NB, int WAVES, int EPI = 0, int GR = 1, bool LG = false>
 __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_tm(const f4 *__restrict__ in_tm, int KB,
                                                         const f4 *__restrict__ wp_all,
                                                         const float *__restrict__ bias, int nout,
@@ -380,6 +402,7 @@ __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_t
                                                         heads_args hd = heads_args())
 {
     static_assert(EPI != 2 || GR == 1, "the fused heads keep one group per wave");
+    static_assert(!LG || EPI == 2 || EPI == 3, "the logits epilogue belongs to the forms that compute the heads");
     static_assert(EPI != 3 || (GR == 2 && NB == 21 && WAVES == 8), "the fc5 + heads tail is written for the full topology's fc4");
     // The packed weight matrix holds NBP = roundup(NB, WAVES) fragments per k step (the pad
     // fragments are zero and never multiplied), so every thread stages exactly PER 16-byte
@@ -633,7 +656,7 @@ __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_t
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // surplus DMA pieces of the last stages
 #pragma unroll
         for (int r = 0; r < GR; r++)
-            if (g + r < G) heads_finish(hacc0[r], hacc1[r], hd.bb, hd.bz, hd.bt, hd.bl, n_cand, out16, g + r, lane_t);
+            if (g + r < G) heads_finish<LG>(hacc0[r], hacc1[r], hd.bb, hd.bz, hd.bt, hd.bl, n_cand, out16, g + r, lane_t);
         return;
     }
 #pragma unroll
@@ -661,7 +684,7 @@ __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_t
 #pragma unroll
                 for (int s = 0; s < 4; s++) hacc1 = mfma4(hW[ob][s], h[s], hacc1);
             }
-            heads_finish(hacc0, hacc1, hd.bb, hd.bz, hd.bt, hd.bl, hd.n, hd.out16, g + r, lane);
+            heads_finish<LG>(hacc0, hacc1, hd.bb, hd.bz, hd.bt, hd.bl, hd.n, hd.out16, g + r, lane);
             continue;
         }
 #pragma unroll
@@ -1783,7 +1806,7 @@ __global__ __launch_bounds__(NWV * 64, (PART ? 1 : 3)) void train_tail_tm(const 
 // the same fragments; the fc5 outputs meet in LDS and wave 0 finishes the heads (heads_finish).  Per value the chains
 // are dense_small's and heads_tm's: the same bits.
 // ---------------------------------------------------------------------------
-template <int NB4, int NB5>
+template <int NB4, int NB5, bool LG = false>
 __global__ __launch_bounds__(256) void infer_tail_tm(const f4 *__restrict__ h4, const f4 *__restrict__ w5s,
                                                     const float *__restrict__ bias5, int nout5, f4 *__restrict__ h5_out,
                                                     const f4 *__restrict__ wp0, const f4 *__restrict__ wp1,
@@ -1888,7 +1911,7 @@ __global__ __launch_bounds__(256) void infer_tail_tm(const f4 *__restrict__ h4, 
 #pragma unroll
         for (int s4 = 0; s4 < 4; s4++) a1 = mfma4(W1[kb][s4], B[s4], a1);
     }
-    heads_finish(sa0[lane], a1, bb, bz, bt, bl, n, out16, g, lane);
+    heads_finish<LG>(sa0[lane], a1, bb, bz, bt, bl, n, out16, g, lane);
 }
 
 // up to this many groups (16 candidates each) fc4 runs as 3 output slabs per group block: 8-wave workgroups

@@ -400,12 +400,12 @@ int launch_conv3_rot(const float *in, const float *wp, const float *bias, int co
     return 0;
 }
 
-template <int NB, int WAVES, int EPI = 0, int GR = 1>
+template <int NB, int WAVES, int EPI = 0, int GR = 1, bool LG = false>
 int launch_dense(const float *in, int KB, const float *wp, const float *bias, int nout, float *out, int G,
                  hipStream_t st, int slabs = 1, int ksplit = 1, float *part = nullptr, heads_args hd = heads_args(),
                  cv_dropout_args dr = cv_dropout_args())
 {
-    auto k = dense_tm<NB, WAVES, EPI, GR>;
+    auto k = dense_tm<NB, WAVES, EPI, GR, LG>;
     size_t lds = (size_t)3 * ((NB + WAVES - 1) / WAVES * WAVES) * 1024;
     if (EPI == 3) lds = (size_t)3 * 48 * 1024;          // the tail streams fc5 in stages of 4 k fragments x 12 output fragments
     if (set_lds(k, lds)) return 1;
@@ -725,7 +725,9 @@ static bool slim_small_pass(const cv_model *m, int G)
     return unfused < 0.97 * fused;
 }
 
-int cv_mfma_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStream_t st)
+// logits: the kernel form of every stage is chosen as without it; the form that computes the heads runs with its
+// logits epilogue (template argument LG, heads_finish<true>) and reports it in its name
+int cv_mfma_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStream_t st, bool logits)
 {
     if (n <= 0) return 0;
     const cv_arch &a = m->arch;
@@ -877,7 +879,7 @@ int cv_mfma_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStr
         else if (form == 1 && m->inf_rag_s >= 0) { m->stage_kernel[3] = "dense_rag<7, 8>"; rc |= launch_dense_rag(m->tm_p3, s.kb4, m->wps_fc4, P + o[7], a.fc4, m->tm_h4, G, s.nb4, m->inf_rag_s, st); }
         else if (form == 1) { m->stage_kernel[3] = "dense_tm<7, 8, 0, 1>"; rc |= launch_dense<7, 8>(m->tm_p3, s.kb4, m->wps_fc4, P + o[7], a.fc4, m->tm_h4, G, st, 3); }
         else if (can_fused) {      // fc4 + fc5 + heads as one kernel
-            m->stage_kernel[3] = "dense_tm<21, 8, 3, 2>";
+            m->stage_kernel[3] = logits ? "dense_tm<21, 8, 3, 2, true>" : "dense_tm<21, 8, 3, 2>";
             heads_args h3 = hd;
             h3.wp5p = (const f4 *)m->wp5p_fc5; h3.bias5 = P + o[9]; h3.nout5 = a.fc5; h3.h5_out = (f4 *)m->tm_h5;
             h3.keep = m->keep_act;
@@ -885,7 +887,8 @@ int cv_mfma_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStr
             heads_args hk;                           // by value: the pointer to the device copy + what changes per call
             if (tail_args_refresh(m, h3, st, &hk.tail)) return 1;
             hk.n = n; hk.out16 = out16;
-            rc |= launch_dense<21, 8, 3, 2>(m->tm_p3, s.kb4, m->wp_fc4, P + o[7], a.fc4, m->tm_h4, G, st, 1, 1, nullptr, hk);
+            if (logits) rc |= launch_dense<21, 8, 3, 2, true>(m->tm_p3, s.kb4, m->wp_fc4, P + o[7], a.fc4, m->tm_h4, G, st, 1, 1, nullptr, hk);
+            else rc |= launch_dense<21, 8, 3, 2>(m->tm_p3, s.kb4, m->wp_fc4, P + o[7], a.fc4, m->tm_h4, G, st, 1, 1, nullptr, hk);
             tail_done = true;
         }
         else if (m->variant & 32) { m->stage_kernel[3] = "dense_tm<21, 8, 0, 2>"; rc |= launch_dense<21, 8, 0, 2>(m->tm_p3, s.kb4, m->wp_fc4, P + o[7], a.fc4, m->tm_h4, G, st); }
@@ -903,17 +906,19 @@ int cv_mfma_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStr
             // fc5 + the heads as one launch of four-wave workgroups, one per group (was dense_small<4, 7> + heads_tm in small
             // passes: 30 -> 18 us).  Up to 560 groups it also beats the ring kernel with the heads on its tail (dense_tm<11, 4, 2>:
             // 257 / 320 / 512 groups 23 / 24 / 25 us against 31 / 31 / 33; from 625 on 34 against 32 and growing with the pass)
-            m->stage_kernel[4] = "infer_tail_tm<21, 11>";
-            infer_tail_tm<21, 11><<<G, 256, 0, st>>>((const f4 *)m->tm_h4, (const f4 *)m->wps3_fc5, P + o[9], a.fc5, (f4 *)m->tm_h5,
-                                                     (const f4 *)m->wp_heads0, (const f4 *)m->wp_heads1, P + o[11], P + o[13],
-                                                     P + o[15], P + o[17], n, out16);
+            m->stage_kernel[4] = logits ? "infer_tail_tm<21, 11, true>" : "infer_tail_tm<21, 11>";
+            auto kt = logits ? infer_tail_tm<21, 11, true> : infer_tail_tm<21, 11>;
+            kt<<<G, 256, 0, st>>>((const f4 *)m->tm_h4, (const f4 *)m->wps3_fc5, P + o[9], a.fc5, (f4 *)m->tm_h5,
+                                  (const f4 *)m->wp_heads0, (const f4 *)m->wp_heads1, P + o[11], P + o[13],
+                                  P + o[15], P + o[17], n, out16);
             heads_done = true;
         } else if (G <= m->inf_fc4_small_g && (m->variant & 128)) {
             m->stage_kernel[4] = "dense_small<4, 7, 0>";
             rc |= launch_dense_small<4, 7>(m->tm_h4, s.nb4, m->wps3_fc5, P + o[9], a.fc5, m->tm_h5, G, 3, st, s.nb5);
         } else if (m->variant & 512) {      // fc5 + heads as one kernel
-            m->stage_kernel[4] = "dense_tm<11, 4, 2, 1>";
-            rc |= launch_dense<11, 4, 2>(m->tm_h4, s.nb4, m->wp_fc5, P + o[9], a.fc5, m->tm_h5, G, st, 1, 1, nullptr, hd);
+            m->stage_kernel[4] = logits ? "dense_tm<11, 4, 2, 1, true>" : "dense_tm<11, 4, 2, 1>";
+            if (logits) rc |= launch_dense<11, 4, 2, 1, true>(m->tm_h4, s.nb4, m->wp_fc5, P + o[9], a.fc5, m->tm_h5, G, st, 1, 1, nullptr, hd);
+            else rc |= launch_dense<11, 4, 2>(m->tm_h4, s.nb4, m->wp_fc5, P + o[9], a.fc5, m->tm_h5, G, st, 1, 1, nullptr, hd);
             heads_done = true;
         } else {                            // (two groups per wave, as for fc4, measured: 79.5 -> 75.3 us; not worth a variant)
             m->stage_kernel[4] = "dense_tm<11, 4, 0, 1>";
@@ -952,8 +957,9 @@ int cv_mfma_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStr
         cv_prof_end(m, 3, st);
         cv_prof_begin(m, 4, st);
         if (m->variant & 512) {
-            m->stage_kernel[4] = "dense_tm<2, 4, 2, 1>";
-            rc |= launch_dense<2, 4, 2>(m->tm_h4, s.nb4, m->wp_fc5, P + o[9], a.fc5, m->tm_h5, G, st, 1, 1, nullptr, hd);
+            m->stage_kernel[4] = logits ? "dense_tm<2, 4, 2, 1, true>" : "dense_tm<2, 4, 2, 1>";
+            if (logits) rc |= launch_dense<2, 4, 2, 1, true>(m->tm_h4, s.nb4, m->wp_fc5, P + o[9], a.fc5, m->tm_h5, G, st, 1, 1, nullptr, hd);
+            else rc |= launch_dense<2, 4, 2>(m->tm_h4, s.nb4, m->wp_fc5, P + o[9], a.fc5, m->tm_h5, G, st, 1, 1, nullptr, hd);
             heads_done = true;
         } else {
             m->stage_kernel[4] = "dense_tm<2, 4, 0, 1>";
@@ -999,11 +1005,12 @@ int cv_mfma_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStr
                     if (tail_args_refresh(m, h3, st, &tail)) return 1;
                     tail_done = true;
                 }
-#define CV_SLIM_LAUNCH(W) do { if (set_lds(conv3fc4_slim<W>, lds)) return 1; \
-                    conv3fc4_slim<W><<<nblk(G, W), W * 64, lds, st>>>((const f4 *)m->tm_p2, (const f4 *)m->wp_conv[2], P + o[5], a.cout[2], \
+#define CV_SLIM_LAUNCH(W) do { auto ks = (logits && tail) ? conv3fc4_slim<W, true> : conv3fc4_slim<W>; if (set_lds(ks, lds)) return 1; \
+                    ks<<<nblk(G, W), W * 64, lds, st>>>((const f4 *)m->tm_p2, (const f4 *)m->wp_conv[2], P + o[5], a.cout[2], \
                                                           (const f4 *)m->wp_fc4, P + o[7], a.fc4, (f4 *)m->tm_h4, G, tail, n, out16); } while (0)
-                if (wv == 8) { m->stage_kernel[2] = "conv3fc4_slim<8>"; CV_SLIM_LAUNCH(8); }
-                else { m->stage_kernel[2] = "conv3fc4_slim<4>"; CV_SLIM_LAUNCH(4); }
+                const bool lgs = logits && tail;           // (without the tail the kernel computes no heads: the plain form)
+                if (wv == 8) { m->stage_kernel[2] = lgs ? "conv3fc4_slim<8, true>" : "conv3fc4_slim<8>"; CV_SLIM_LAUNCH(8); }
+                else { m->stage_kernel[2] = lgs ? "conv3fc4_slim<4, true>" : "conv3fc4_slim<4>"; CV_SLIM_LAUNCH(4); }
 #undef CV_SLIM_LAUNCH
             }
             cv_prof_end(m, 2, st);
@@ -1025,8 +1032,9 @@ int cv_mfma_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStr
         }
         cv_prof_begin(m, 4, st);
         if (m->variant & 512) {
-            m->stage_kernel[4] = "dense_tm<2, 4, 2, 1>";
-            rc |= launch_dense<2, 4, 2>(m->tm_h4, s.nb4, m->wp_fc5, P + o[9], a.fc5, m->tm_h5, G, st, 1, 1, nullptr, hd);
+            m->stage_kernel[4] = logits ? "dense_tm<2, 4, 2, 1, true>" : "dense_tm<2, 4, 2, 1>";
+            if (logits) rc |= launch_dense<2, 4, 2, 1, true>(m->tm_h4, s.nb4, m->wp_fc5, P + o[9], a.fc5, m->tm_h5, G, st, 1, 1, nullptr, hd);
+            else rc |= launch_dense<2, 4, 2>(m->tm_h4, s.nb4, m->wp_fc5, P + o[9], a.fc5, m->tm_h5, G, st, 1, 1, nullptr, hd);
             heads_done = true;
         } else {
             m->stage_kernel[4] = "dense_tm<2, 4, 0, 1>";
@@ -1042,18 +1050,37 @@ int cv_mfma_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStr
     if (heads_done) return 0;
     cv_prof_begin(m, 5, st);
     if (m->variant & 2) {
-        m->stage_kernel[5] = "heads_tm";
-        heads_tm<<<nblk(G, 4), 256, 0, st>>>((const f4 *)m->tm_h4, (const f4 *)m->tm_h5, s.nb4, s.nb5,
+        m->stage_kernel[5] = logits ? "heads_tm<true>" : "heads_tm";
+        auto kh = logits ? heads_tm<true> : heads_tm<false>;
+        kh<<<nblk(G, 4), 256, 0, st>>>((const f4 *)m->tm_h4, (const f4 *)m->tm_h5, s.nb4, s.nb5,
                                             (const f4 *)m->wp_heads0, (const f4 *)m->wp_heads1, P + o[11], P + o[13],
                                             P + o[15], P + o[17], n, out16, G);
         rc = 0;
     } else {
-        m->stage_kernel[5] = "heads_kernel";
-        rc = cv_launch_heads(m, m->tm_h4, m->tm_h5, 1, n, out16, st);
+        m->stage_kernel[5] = logits ? "heads_kernel<true>" : "heads_kernel";
+        rc = cv_launch_heads(m, m->tm_h4, m->tm_h5, 1, n, out16, st, logits);
     }
     cv_prof_end(m, 5, st);
     CV_HIP(hipGetLastError());
     return rc;
+}
+
+// cv_forward_conv_map behind cv_mfma_forward over the same chunk: layer 1 reads x, layers 2 / 3 the pooled map below
+// from the pass workspace.  A pass that made conv1 + pool1 inside its conv2 kernel left no pool1 map: conv1_tm writes it
+// (an existing instance; tm_p1 is otherwise unused by such a pass, and what cv_get_activation reports does not change).
+int cv_mfma_conv_map(cv_model *m, const float *x, int64_t n, int layer, float *dst, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    if (layer == 1) return cv_conv_map_plain(m, 1, x, nullptr, n, dst, st);
+    if (layer == 2 && !m->stage_kernel[0]) {
+        const int G = (int)((n + 15) / 16);
+        const float *B1 = m->params + m->poff[1];
+        if (cv_layout_current(m, CVL_CONV, "cv_forward_conv_map")) return 1;
+        if (is_full(m->arch)) conv1_tm<5><<<nblk((int64_t)G * 4, 4), 256, 0, st>>>(x, n, m->wp_conv1, B1, m->arch.cout[0], (f4 *)m->tm_p1, G);
+        else conv1_tm<1><<<nblk((int64_t)G * 4, 4), 256, 0, st>>>(x, n, m->wp_conv1, B1, m->arch.cout[0], (f4 *)m->tm_p1, G);
+        CV_HIP(hipGetLastError());
+    }
+    return cv_conv_map_plain(m, layer, nullptr, layer == 2 ? m->tm_p1 : m->tm_p2, n, dst, st);
 }
 
 // ---------------------------------------------------------------------------

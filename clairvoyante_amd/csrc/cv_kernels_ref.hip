@@ -79,7 +79,8 @@ __global__ void ref_dense_selu(const float *__restrict__ x, const float *__restr
 // The four heads (v3.py:124-138): 16 candidates x 16 outputs per block.
 //   base     = sigmoid(d4 . Wb + bb)            (reads the fc4 side, v3.py:125)
 //   zyg/type/len = softmax(selu(fc5 . W + b) + 1e-10)
-template <bool TM>
+// LG (cv_forward_logits): the three softmax heads leave selu(.) + 1e-10 itself, the base head its sigmoid as ever
+template <bool TM, bool LG = false>
 __global__ __launch_bounds__(256) void heads_kernel(
     const float *__restrict__ h4, const float *__restrict__ h5, int K4, int K5, int KB4, int KB5,
     const float *__restrict__ wb, const float *__restrict__ bb, const float *__restrict__ wz,
@@ -104,6 +105,10 @@ __global__ __launch_bounds__(256) void heads_kernel(
     __syncthreads();
     if (cand >= n) return;
     float *o = out16 + (size_t)cand * 16;
+    if constexpr (LG) {
+        o[j] = j < 4 ? cvm::sigmoid(pre[c][j]) : cvm::selu(pre[c][j]) + 1e-10f;
+        return;
+    }
     if (j == 0) {
         for (int k = 0; k < 4; k++) o[k] = cvm::sigmoid(pre[c][k]);
     } else if (j == 1) {
@@ -122,6 +127,37 @@ __global__ __launch_bounds__(256) void heads_kernel(
         cvm::softmax<6>(l, p);
         for (int k = 0; k < 6; k++) o[10 + k] = p[k];
     }
+}
+
+// ref_conv_selu over a tile-major input map (feature k = (h*4 + w)*FPP + ci, KB fragments per group): the same chain
+// per output value, the output in natural layout.  cv_forward_conv_map's one extra launch under impl 1: the tile
+// kernels pool the raw accumulators, so the map before pooling exists nowhere on their path.
+__global__ void ref_conv_selu_tm(const float *__restrict__ in_tm, int KB, int FPP, const float *__restrict__ w,
+                                 const float *__restrict__ bias, float *__restrict__ out, int64_t n,
+                                 int H, int cin, int kh, int cout)
+{
+    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t total = n * H * 4 * cout;
+    if (t >= total) return;
+    int co = (int)(t % cout);
+    int64_t r = t / cout;
+    int wo = (int)(r % 4); r /= 4;
+    int h = (int)(r % H);
+    int64_t i = r / H;
+    const int padt = (kh - 1) / 2;
+    float acc = 0.0f;
+    for (int a = 0; a < kh; a++) {
+        int hi = h + a - padt;
+        if (hi < 0 || hi >= H) continue;
+        for (int b = 0; b < 4; b++) {
+            int wi = wo + b - 1;
+            if (wi < 0 || wi >= 4) continue;
+            const int k0 = (hi * 4 + wi) * FPP;
+            const float *wr = w + ((size_t)(a * 4 + b) * cin) * cout + co;
+            for (int ci = 0; ci < cin; ci++) acc = __builtin_fmaf(in_tm[cv_tm_index(i, k0 + ci, KB)], wr[(size_t)ci * cout], acc);
+        }
+    }
+    out[t] = cvm::selu(acc + bias[co]);
 }
 
 // TM -> natural copy: feature k = pos*FPP + f (f < FP real, FPP padded)
@@ -143,20 +179,21 @@ inline unsigned nblk(int64_t total, int bs) { return (unsigned)((total + bs - 1)
 }  // namespace
 
 int cv_launch_heads(cv_model *m, const float *h4, const float *h5, int tm, int64_t n, float *out16,
-                    hipStream_t st)
+                    hipStream_t st, bool logits)
 {
     if (n <= 0) return 0;
     const float *P = m->params;
     const int64_t *o = m->poff;
     unsigned g = (unsigned)((n + 15) / 16);
-    if (tm)
-        heads_kernel<true><<<g, 256, 0, st>>>(h4, h5, m->arch.fc4, m->arch.fc5, m->sh.nb4, m->sh.nb5,
-                                             P + o[10], P + o[11], P + o[12], P + o[13], P + o[14],
-                                             P + o[15], P + o[16], P + o[17], n, out16);
-    else
-        heads_kernel<false><<<g, 256, 0, st>>>(h4, h5, m->arch.fc4, m->arch.fc5, 0, 0, P + o[10],
-                                              P + o[11], P + o[12], P + o[13], P + o[14], P + o[15],
-                                              P + o[16], P + o[17], n, out16);
+    if (tm) {
+        auto k = logits ? heads_kernel<true, true> : heads_kernel<true>;
+        k<<<g, 256, 0, st>>>(h4, h5, m->arch.fc4, m->arch.fc5, m->sh.nb4, m->sh.nb5, P + o[10], P + o[11], P + o[12],
+                             P + o[13], P + o[14], P + o[15], P + o[16], P + o[17], n, out16);
+    } else {
+        auto k = logits ? heads_kernel<false, true> : heads_kernel<false>;
+        k<<<g, 256, 0, st>>>(h4, h5, m->arch.fc4, m->arch.fc5, 0, 0, P + o[10], P + o[11], P + o[12], P + o[13],
+                             P + o[14], P + o[15], P + o[16], P + o[17], n, out16);
+    }
     CV_HIP(hipGetLastError());
     return 0;
 }
@@ -194,7 +231,7 @@ static int ref_alloc(cv_model *m, int64_t cap)
 }
 
 // one chunk (n <= ref_cap) through the plain kernels
-int cv_ref_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStream_t st)
+int cv_ref_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStream_t st, bool logits)
 {
     if (n <= 0) return 0;
     if (ref_alloc(m, n)) return 1;
@@ -217,5 +254,27 @@ int cv_ref_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStre
     CV_HIP(hipGetLastError());
     m->last_n = n;
     m->last_impl = 0;
-    return cv_launch_heads(m, m->r_h4, m->r_h5, 0, n, out16, st);
+    return cv_launch_heads(m, m->r_h4, m->r_h5, 0, n, out16, st, logits);
+}
+
+// selu(conv_layer) before pooling of the n candidates of a chunk, natural layout [n, hc, 4, cout], from the pooled map
+// of the layer below: in_tm (tile-major, what the tile path left) or in (natural: x for layer 1, the plain path's map)
+int cv_conv_map_plain(cv_model *m, int layer, const float *in, const float *in_tm, int64_t n, float *dst, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    const int l = layer - 1;
+    const float *P = m->params;
+    const int64_t *o = m->poff;
+    const int H = m->sh.hc[l], C = m->arch.cout[l];
+    const int64_t tot = n * H * 4 * C;
+    if (in_tm) {
+        const int nt = m->sh.ntile[l - 1];
+        ref_conv_selu_tm<<<nblk(tot, 256), 256, 0, st>>>(in_tm, m->sh.hp[l - 1] * 4 * nt, nt * 16, P + o[2 * l], P + o[2 * l + 1],
+                                                         dst, n, H, m->sh.cin[l], m->arch.kh[l], C);
+    } else {
+        ref_conv_selu<<<nblk(tot, 256), 256, 0, st>>>(in, P + o[2 * l], P + o[2 * l + 1], dst, n, H, m->sh.cin[l],
+                                                      m->arch.kh[l], C);
+    }
+    CV_HIP(hipGetLastError());
+    return 0;
 }

@@ -120,6 +120,11 @@ class Clairvoyante(object):
     def setOption(self, key, value):
         _lib.check(self._lib.cv_set_option(self._h, key.encode(), int(value)))
 
+    def getOption(self, key):
+        v = ctypes.c_int64()
+        _lib.check(self._lib.cv_get_option(self._h, key.encode(), ctypes.byref(v)))
+        return int(v.value)
+
     def paramShapes(self):
         return dict(self._shapes)
 
@@ -190,6 +195,16 @@ class Clairvoyante(object):
                                         ctypes.c_void_p(out16.data_ptr()), self._stream()))
         return out16
 
+    def embeddings_device(self, x_dev, out16=None):
+        """predict_device with the logits in place of the softmaxes (cv_forward_logits): out16 [n,16] = the base
+        sigmoid, then selu(FC) + 1e-10 of the zygosity, variant-type and indel-length heads (embedding1..4, v3.py:154-158)."""
+        n = x_dev.shape[0]
+        if out16 is None:
+            out16 = torch.empty((n, _lib.NUM_OUT), dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.cv_forward_logits(self._h, ctypes.c_void_p(x_dev.data_ptr()), n,
+                                               ctypes.c_void_p(out16.data_ptr()), self._stream()))
+        return out16
+
     def evaluateCounts(self, X, Y, counts=None):
         """The evaluation report's counters of a labelled batch (train.EvaluateReport as numbers; layout:
         include/clairvoyante_amd.h, cv_eval_counts) ADDED to `counts`, a device int64[64] tensor -- allocated and zeroed
@@ -245,21 +260,22 @@ class Clairvoyante(object):
             st = self._hstreams = (torch.cuda.Stream(device=self.device), torch.cuda.Stream(device=self.device))
         return st
 
-    def _predict_host(self, XArray):
+    def _predict_host(self, XArray, fn=None):
+        fn = fn or self.predict_device            # (or embeddings_device: the same pass with the logits epilogue)
         with torch.cuda.device(self.device):
             if torch.is_tensor(XArray):
-                out = self.predict_device(self._to_dev(XArray, (33, 4, 4))).cpu().numpy()
+                out = fn(self._to_dev(XArray, (33, 4, 4))).cpu().numpy()
             else:
                 x = np.ascontiguousarray(XArray, dtype=np.float32).reshape((-1, 33, 4, 4))
                 n = x.shape[0]
                 if n < self.PIPE_MIN:
-                    out = self.predict_device(torch.from_numpy(x).to(self.device)).cpu().numpy()
+                    out = fn(torch.from_numpy(x).to(self.device)).cpu().numpy()
                 else:
-                    out = self._predict_host_parts(x, n)
+                    out = self._predict_host_parts(x, n, fn)
         # (views of ONE fresh [n,16] array: the four heads side by side, as the kernels store them)
         return out[:, 0:4], out[:, 4:6], out[:, 6:10], out[:, 10:16]
 
-    def _predict_host_parts(self, x, n):
+    def _predict_host_parts(self, x, n, fn):
         cut = self._pipe_cuts(n)
         main = torch.cuda.current_stream(self.device)
         cs, ds = self._host_streams()
@@ -273,7 +289,7 @@ class Clairvoyante(object):
                 dev[lo:hi].copy_(torch.from_numpy(x[lo:hi]))       # (host-synchronous: the runtime stages pageable memory)
                 ev = torch.cuda.Event(); ev.record(cs)
             main.wait_event(ev)
-            self.predict_device(dev[lo:hi], out[lo:hi])
+            fn(dev[lo:hi], out[lo:hi])
             d = torch.cuda.Event(); d.record(main); done.append(d)
         with torch.cuda.stream(ds):
             for (lo, hi), d in zip(zip(cut[:-1], cut[1:]), done):
@@ -292,6 +308,66 @@ class Clairvoyante(object):
         self.predictVarTypeRTVal = None; self.predictIndelLengthRTVal = None
         (self.predictBaseRTVal, self.predictZygosityRTVal,
          self.predictVarTypeRTVal, self.predictIndelLengthRTVal) = self._predict_host(XArray)
+
+    def embeddings(self, XArray):
+        """session.run((embedding1, .., embedding4)) of getEmbedding.py:55-57 -> (base sigmoid [n,4], zygosity logits
+        [n,2], variant-type logits [n,4], indel-length logits [n,6]); the host batch goes up in parts as in predict."""
+        return self._predict_host(XArray, self.embeddings_device)
+
+    LAYER_NAMES = ("conv1", "conv2", "conv3", "fc4", "fc5", "YBaseChangeSigmoid", "YZygositySoftmax", "YVarTypeSoftmax",
+                   "YIndelLengthSoftmax", "embedding1", "embedding2", "embedding3", "embedding4")
+
+    def layers(self, XArray, names):
+        """session.run of graph nodes by name: m.session.run(m.conv1, feed_dict=...) of a reference script becomes
+        m.layers(X, ["conv1"])["conv1"].  -> {name: numpy array} for names among LAYER_NAMES: conv1..conv3 are the SELU
+        maps BEFORE pooling [n,hc,4,c] (cv_forward_conv_map), fc4 / fc5 [n,units], the four outputs of predict, the four
+        of embeddings.  One pass per kind asked for; fc4 / fc5 come from a predict pass under option keep_activations,
+        which is put back afterwards.  Every array lives on the device until it is copied out: ask for a block of
+        candidates at a time (conv3 of the full topology is 20 KB per candidate)."""
+        names = list(names)
+        for name in names:
+            if name not in self.LAYER_NAMES:
+                raise KeyError(name)
+        res = {}
+        with torch.cuda.device(self.device):
+            x = self._to_dev(XArray, (33, 4, 4))
+            n = x.shape[0]
+            a = self._arch
+            hc = [33, 33 - (a.pool[0] - 1)]
+            hc.append(hc[1] - (a.pool[1] - 1))
+            for l in (1, 2, 3):
+                if "conv%d" % l in names:
+                    dst = torch.empty((n, hc[l - 1], 4, a.cout[l - 1]), dtype=torch.float32, device=self.device)
+                    if n:
+                        _lib.check(self._lib.cv_forward_conv_map(self._h, ctypes.c_void_p(x.data_ptr()), n, l,
+                                                                 ctypes.c_void_p(dst.data_ptr()), self._stream()))
+                    res["conv%d" % l] = dst.cpu().numpy()
+            heads = ((0, 4), (4, 6), (6, 10), (10, 16))
+            outs = ("YBaseChangeSigmoid", "YZygositySoftmax", "YVarTypeSoftmax", "YIndelLengthSoftmax")
+            want_fc = [k for k in ("fc4", "fc5") if k in names]
+            if want_fc or any(k in names for k in outs):
+                # one predict pass, block by block of at most a chunk: layers 4 / 5 are the LAST chunk's
+                step = self.getOption("chunk") if self.getOption("impl") else min(self.getOption("chunk"), 4096)
+                out = torch.empty((n, _lib.NUM_OUT), dtype=torch.float32, device=self.device)
+                fc = {k: np.empty((n, a.fc4 if k == "fc4" else a.fc5), dtype=np.float32) for k in want_fc}
+                keep = self.getOption("keep_activations")
+                if want_fc:
+                    self.setOption("keep_activations", 1)
+                try:
+                    for lo in range(0, n, step):
+                        hi = min(n, lo + step)
+                        self.predict_device(x[lo:hi], out[lo:hi])
+                        for k in want_fc:
+                            fc[k][lo:hi] = self.getActivation(4 if k == "fc4" else 5, hi - lo).cpu().numpy()
+                finally:
+                    self.setOption("keep_activations", keep)
+                res.update(fc)
+                o = out.cpu().numpy()
+                res.update({k: o[:, c0:c1] for k, (c0, c1) in zip(outs, heads)})
+            if any(k.startswith("embedding") for k in names):
+                e = self.embeddings_device(x).cpu().numpy()
+                res.update({"embedding%d" % (i + 1): e[:, c0:c1] for i, (c0, c1) in enumerate(heads)})
+        return {k: res[k] for k in names}
 
     def getActivation(self, layer, n):
         """Intermediate of the last pass in the reference's layout (debug / parity); layers 6 / 7 are the

@@ -81,6 +81,22 @@ int cv_params_changed(cv_model *m);
  * out16_dev [n,16]: columns 0..3 base sigmoid, 4..5 zygosity softmax,
  * 6..9 variant-type softmax, 10..15 indel-length softmax.  n may be 0.          */
 int cv_forward(cv_model *m, const float *x_dev, int64_t n, float *out16_dev, void *stream);
+/* The same pass with the logits where cv_forward leaves the softmaxes -- embedding1..4 of getEmbedding.py:55-57
+ * (v3.py:154-158).  out16_dev [n,16]: columns 0..3 the base sigmoid (the bits cv_forward writes there), 4..5, 6..9 and
+ * 10..15 selu(FC) + 1e-10f of the zygosity, variant-type and indel-length heads.  Same contract as cv_forward (any n,
+ * chunked, asynchronous on `stream`, the same workspace) and, per stage, the same kernel form: the one that computes
+ * the heads runs with its logits epilogue, a template argument that cv_kernel_name shows ("heads_tm<true>",
+ * "dense_tm<21, 8, 3, 2, true>", ...).  Counts as the last pass for cv_get_activation.                           */
+int cv_forward_logits(cv_model *m, const float *x_dev, int64_t n, float *out16_dev, void *stream);
+/* selu(conv_layer) BEFORE pooling -- m.conv1..m.conv3 of getTensorAndLayerPNG.py:124-132 -- of all n candidates, into
+ * dst_dev in natural layout [n, hc, 4, cout] (full: hc = 33 / 29 / 26; slim, which does not pool: 33, and the values
+ * are cv_get_activation 1..3's).  layer 1..3, anything else is an error.  The tile kernels pool the raw accumulators,
+ * so this map exists nowhere on their path: per chunk the entry runs the forward pass (which leaves the workspace,
+ * cv_kernel_name and cv_get_activation as cv_forward would) and one plain launch over the pooled map below straight
+ * into dst_dev, whose chunk the pass first uses for its 16 outputs per candidate.  No model state beyond the pass
+ * workspace; candidate offsets in 64 bits.  The inspection path, not the throughput path: the same bits under
+ * "impl" 0 and 1.                                                                                                  */
+int cv_forward_conv_map(cv_model *m, const float *x_dev, int64_t n, int layer, float *dst_dev, void *stream);
 
 /* Device-side part of callVar.Output (callVar.py:59-72,81-87): per candidate
  * argmax of the three softmax heads (lowest index wins ties, np.argmax), the two
@@ -159,7 +175,8 @@ int cv_vcf_records_host_form(const int32_t *call, const float *qual, int64_t n, 
 /* debug / parity: copy one intermediate of the LAST cv_forward chunk to
  * dst_dev in the reference's natural layout ([n,h,4,c] NHWC or [n,units]).
  * layer: 1..3 = pool1..pool3 outputs (for slim: conv outputs), 4 = fc4, 5 = fc5.
- * Serves what getTensorAndLayerPNG.py:30-37 reaches into m.conv1.. for.
+ * Serves what getTensorAndLayerPNG.py:30-37 reaches into m.conv1.. for in the slim topology, whose pools are 1;
+ * the full topology's maps before pooling come from cv_forward_conv_map.
  * layer 6 / 7 refer to the last cv_grad / cv_loss slice instead: 6 = the alpha-dropout
  * keep mask of fc4 times its affine factor a (selu.py:53-62; 0 where a unit was
  * dropped, a where kept, 1 everywhere at rate 0), 7 = dropout4, the layer's output
