@@ -388,12 +388,22 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv3fc4_slim(const f4 *__restr
 // per k step + 4 per output tile, then heads_finish.  No separate heads launch, the fc5 output is not re-read.
 // GR = groups per wave (1 or 2): with 2 a wave keeps two sets of accumulator tiles and every weight fragment read
 // from LDS feeds both -- twice the MFMA work per barrier and per LDS read, at 2 waves per SIMD.
-// (measured, round 4: a FOUR-slot ring filled three k steps ahead, so that a wave reads the first two weight fragments of
-// step k + 1 while it still multiplies step k, carries them across the barrier in registers and issues this step's loads /
-// DMA pieces behind its first MFMA block -- no LDS round trip between a barrier and the first MFMA.  Bit-identical; the
-// training step did not move: 2.1163 against 2.1167 ms at 10 000, three alternating runs each on one box,
-// profiles/r04/train_ab_fc4_forward_ring.txt.  The step behind a barrier is not what the kernel waits for; removed.)
+// The k step of the GR = 2 forms (round 26): a FOUR-slot ring filled three k steps ahead.  Stage k + 1 is published one
+// barrier early, so a wave reads the first two weight fragments of step k + 1 in the last blocks of step k, carries them
+// across the barrier in registers and opens step k + 1 with MFMAs; the step's two activation loads and three DMA pieces
+// go out one by one behind its first groups of four MFMAs.  With the three-slot ring every wave of the one workgroup on
+// the CU opens a step with its loads, its DMA pieces and an LDS round trip while the matrix pipe idles: the leading
+// waves of the SIMDs spend 421 of a step's 11 581 cycles between the barrier and their first MFMA (per-wave phase probe,
+// -DCV_DENSE_PHASES; the trailing waves wait for the pipe, not for memory).  65 536 candidates, libraries alternated on
+// one box, five rounds: 1.516 -> 1.477 ms (-2.6 %), the pass 18.80 -> 19.02 M candidates/s; MFMA busy 0.893 -> 0.916;
+// same bits (profiles/r26/).  218 VGPRs (the scheduler is pinned block by block and no longer reads 15 fragments ahead).
+// Two k fragments per stage and barrier instead (three stages of 48 KB, as the tail streams fc5): 1.531 ms, no gain; both
+// at once do not fit the LDS (4 x 48 KB).  The other forms keep the three-slot ring: with several workgroups on a CU
+// the neighbours fill the gap (round 4: the training step did not move, profiles/r04/train_ab_fc4_forward_ring.txt).
 // LG (EPI 2 / 3 only): the heads leave their logits (heads_finish<true>, cv_forward_logits).
+#ifndef CV_DENSE_RING
+#define CV_DENSE_RING 1          // (development A/B and the phase probe: 0 = the three-slot ring of the other forms)
+#endif
 template <int NB, int WAVES, int EPI = 0, int GR = 1, bool LG = false>
 __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_tm(const f4 *__restrict__ in_tm, int KB,
                                                         const f4 *__restrict__ wp_all,
@@ -412,6 +422,7 @@ __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_t
     constexpr int NBP = (NB + WAVES - 1) / WAVES * WAVES;
     constexpr int STAGE = NBP * 64;              // f4 per stage
     constexpr int PER = NBP / WAVES;             // fragments each wave stages per k step
+    constexpr int RING = GR == 2 ? CV_DENSE_RING : 0;      // the k step of the two-group forms (see the header)
     // gridDim.z > 1 (training forward of tiny batches): the contraction is split into gridDim.z ranges of k
     // fragments, each workgroup leaves the raw partial accumulators of its range in out_tm ([z][g][NBT] fragments)
     // and dense_ksum adds the ranges in ascending order, + bias, SELU.  A fixed order (reproducible), but not the
@@ -450,16 +461,17 @@ __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_t
     // behind it (it cannot tell the ring slots apart); completion is waited for explicitly
     // (vmcnt) before the barrier that publishes the slot.
     const unsigned ring_base = (unsigned)(size_t)(__attribute__((address_space(3))) f4 *)ring;
+    auto stage_piece = [&](int kb, int slot, int p) {
+        const f4 *gp = wp + ((size_t)kb * NBP + wid * PER + p) * 64 + lane;
+        const unsigned ldst = ring_base + (unsigned)((slot * NBP + wid * PER + p) * 1024);
+        unsigned keep;
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                     "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(gp), "s"(ldst) : "memory");
+    };
     auto stage_async = [&](int kb, int slot) {
 #pragma unroll
-        for (int p = 0; p < PER; p++) {
-            const f4 *gp = wp + ((size_t)kb * NBP + wid * PER + p) * 64 + lane;
-            const unsigned ldst = ring_base + (unsigned)((slot * NBP + wid * PER + p) * 1024);
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                         "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(gp), "s"(ldst) : "memory");
-        }
+        for (int p = 0; p < PER; p++) stage_piece(kb, slot, p);
     };
     // The activation fragments are loaded from asm as well: with no compiler-visible VMEM in
     // the loop hipcc emits no vmcnt waits of its own (its counted waits would also drain the
@@ -476,6 +488,7 @@ __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_t
     };
     stage_async(0, 0);
     stage_async(KB > 1 ? 1 : 0, 1);
+    if constexpr (RING == 1) stage_async(KB > 2 ? 2 : KB - 1, 2);
     f4 hacc0 = zero, hA = zero;                 // EPI 2: base-head tile and its weight fragment of the current k step
     if constexpr (EPI == 2) hA = load_frag(hd.wp0 + lane);
     f4 B[GR];
@@ -486,6 +499,93 @@ __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_t
     if constexpr (EPI == 2) asm volatile("" : "+v"(hA) : : "memory");
     __syncthreads();
     int slot = 0;
+    constexpr int AB = EPI == 3 ? 2 : 3;          // weight fragments read ahead of their MFMAs (EPI 3 is short of 4 VGPRs)
+    CV_DPH_BEGIN
+    if constexpr (RING == 1) {
+        // ---- four-slot ring, the first NPRE weight fragments of a step carried across the barrier (see the header)
+        constexpr int NPRE = 2;
+        static_assert(PER == 3 && NB > NPRE + 2 * AB, "counted wait and block layout below");
+        f4 Apre[NPRE];
+#pragma unroll
+        for (int j = 0; j < NPRE; j++) Apre[j] = ring[j * 64 + lane];
+#pragma unroll 1
+        for (int kb = 0; kb < KB; kb++) {
+            // stage kb+3 and activation fragment kb+1 (indices clamped: the surplus loads of the last steps re-read valid
+            // data and land in ring slots nobody reads again)
+            const int ks = kb + 3 < KB ? kb + 3 : KB - 1;
+            const int kn = kb + 1 < KB ? kb + 1 : KB - 1;
+            const int wslot = (slot + 3) & 3, nslot = (slot + 1) & 3;
+            const f4 *wl = ring + slot * STAGE + lane, *wn = ring + nslot * STAGE + lane;
+            // the reads of the second block go out first, then the MFMAs on what came across the barrier in registers:
+            // nothing between the barrier and the first MFMA waits for memory
+            // The whole step is pinned by sched_barrier (the scheduler, left alone, reads 15 fragments ahead, which leaves
+            // no registers for two more fragments live across the barrier; given only block boundaries it sinks each
+            // block's reads to the block's end).  Every block first reads the fragments of the block behind it, then
+            // multiplies its own.  The step's GR + PER vector-memory instructions (slot (kb+3)%4 was last read in step
+            // kb-1) go out one by one behind the first groups of four MFMAs: at a fixed early place, but not all eight
+            // waves' 40 KiB at one instant.
+            f4 A[2][AB], Bn[GR];
+            auto step_vmem = [&](int i) {
+                if (i < GR) Bn[i] = load_frag_off(bo[i] + (unsigned)kn * 1024u);
+                else stage_piece(ks, wslot, i - GR);
+            };
+#pragma unroll
+            for (int j = 0; j < AB; j++) A[0][j] = wl[(NPRE + j) * 64];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int s = 0; s < 4; s++) {
+#pragma unroll
+                for (int j = 0; j < NPRE; j++)
+#pragma unroll
+                    for (int r = 0; r < GR; r++) {
+                        acc[r][j] = mfma4(Apre[j][s], B[r][s], acc[r][j]);
+                        if (s == 0 && j == 0 && r == 0) CV_DPH_STAMP_AT(cv_dtb, acc[0][0]);
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+                if (s < GR + PER) { step_vmem(s); __builtin_amdgcn_sched_barrier(0); }
+            }
+#pragma unroll
+            for (int ob = NPRE, i = 0; ob < NB; ob += AB, i ^= 1) {
+#pragma unroll
+                for (int j = 0; j < AB; j++)
+                    if (ob + AB + j < NB) A[i ^ 1][j] = wl[(ob + AB + j) * 64];
+                if (ob + AB < NB && ob + 2 * AB >= NB) {
+                    // the block before the last: the first fragments of step kb+1 (published by the barrier that ended
+                    // step kb-1) are read into the registers they cross the barrier in
+#pragma unroll
+                    for (int j = 0; j < NPRE; j++) Apre[j] = wn[j * 64];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int s = 0; s < 4; s++) {
+#pragma unroll
+                    for (int j = 0; j < AB; j++)
+#pragma unroll
+                        for (int r = 0; r < GR; r++)
+                            if (ob + j < NB) acc[r][ob + j] = mfma4(A[i][j][s], B[r][s], acc[r][ob + j]);
+                    if (ob == NPRE && 4 + s < GR + PER) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        step_vmem(4 + s);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            CV_DPH_STAMP_AT(cv_dtl, acc[GR - 1][NB - 1]);
+            CV_DPH_SUM();
+            __builtin_amdgcn_sched_barrier(0);                  // keep the MFMAs above the wait
+            // Counted wait: the step's VMEM order is Bn (GR loads), then its PER DMA pieces (stage kb+3).  vmcnt(PER) leaves
+            // exactly those pieces in flight; Bn and the pieces of stage kb+2 (issued one step ago) have landed, and the
+            // barrier publishes stage kb+2 -- which step kb+1 reads its carried fragments from.
+            asm volatile("s_waitcnt vmcnt(3)" : "+v"(Bn[0]) : : "memory");
+            asm volatile("" : "+v"(Bn[1]) : : "memory");
+            __syncthreads();
+            CV_DPH_STAMP(cv_dta);
+#pragma unroll
+            for (int r = 0; r < GR; r++) B[r] = Bn[r];
+            slot = nslot;
+        }
+    } else {
 #pragma unroll 1
     for (int kb = 0; kb < KB; kb++) {
         // stage kb+2 and activation fragment kb+1 (indices clamped: the surplus loads of the
@@ -503,7 +603,6 @@ __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_t
         // convolution kernels -- makes this ring slower: training step 2.15 -> 2.21 ms, inference 18.41 -> 18.28 M/s on
         // one box; a wave issues at most 5 of them per step, and the barrier needs them early)
         const f4 *wl = ring + slot * STAGE + lane;
-        constexpr int AB = EPI == 3 ? 2 : 3;      // weight fragments read ahead of their MFMAs (EPI 3 is short of 4 VGPRs)
 #pragma unroll
         for (int ob = 0; ob < NB; ob += AB) {
             f4 A[AB];
@@ -516,12 +615,17 @@ __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_t
                 for (int j = 0; j < AB; j++)
 #pragma unroll
                     for (int r = 0; r < GR; r++)
-                        if (ob + j < NB) acc[r][ob + j] = mfma4(A[j][s], B[r][s], acc[r][ob + j]);
+                        if (ob + j < NB) {
+                            acc[r][ob + j] = mfma4(A[j][s], B[r][s], acc[r][ob + j]);
+                            if (ob == 0 && s == 0 && j == 0 && r == 0) CV_DPH_STAMP_AT(cv_dtb, acc[0][0]);
+                        }
         }
         if constexpr (EPI == 2) {
 #pragma unroll
             for (int s = 0; s < 4; s++) hacc0 = mfma4(hA[s], B[0][s], hacc0);
         }
+        CV_DPH_STAMP_AT(cv_dtl, acc[GR - 1][NB - 1]);
+        CV_DPH_SUM();
         __builtin_amdgcn_sched_barrier(0);                  // keep the MFMAs above the wait
         // Counted wait: leave THIS step's PER DMA pieces (stage kb+2, first read two steps from
         // now) in flight; everything older -- Bn and the pieces of stage kb+1 issued one step
@@ -533,10 +637,13 @@ __global__ __launch_bounds__(WAVES * 64, (GR == 2 ? 2 : WAVES / 2)) void dense_t
         if constexpr (GR == 2) asm volatile("" : "+v"(Bn[1]) : : "memory");      // the same wait covers the second fragment
         if constexpr (EPI == 2) { asm volatile("" : "+v"(hAn) : : "memory"); hA = hAn; }
         __syncthreads();
+        CV_DPH_STAMP(cv_dta);
 #pragma unroll
         for (int r = 0; r < GR; r++) B[r] = Bn[r];
         slot = slot + 1 == 3 ? 0 : slot + 1;
     }
+    }
+    CV_DPH_END(EPI == 3, wid);
     CV_STAMP_END(NB == 7 && EPI == 0, 3);
     const int q = lane >> 4;
     if constexpr (EPI == 3) {

@@ -406,7 +406,7 @@ int launch_dense(const float *in, int KB, const float *wp, const float *bias, in
                  cv_dropout_args dr = cv_dropout_args())
 {
     auto k = dense_tm<NB, WAVES, EPI, GR, LG>;
-    size_t lds = (size_t)3 * ((NB + WAVES - 1) / WAVES * WAVES) * 1024;
+    size_t lds = (size_t)(GR == 2 && CV_DENSE_RING ? 4 : 3) * ((NB + WAVES - 1) / WAVES * WAVES) * 1024;   // (the two-group forms: four slots)
     if (EPI == 3) lds = (size_t)3 * 48 * 1024;          // the tail streams fc5 in stages of 4 k fragments x 12 output fragments
     if (set_lds(k, lds)) return 1;
     if (ksplit > 1) {       // partial sums per k range, then dense_ksum (EPI 0 layers only)
@@ -838,7 +838,7 @@ int cv_mfma_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStr
         // fixed lines at 288 / 3 400 groups) -- the same bits whichever runs:
         //   dense_small (one wave per group and slab of 3 tiles, weights from L2): 83 us per round of 1 024 waves;
         //   dense_rag (three slabs on ragged waves): its shape model, + fc5 and the heads as kernels of their own;
-        //   dense_tm<21, 8, 3, 2> (fc4 + fc5 + heads, 16 groups per workgroup, one workgroup per CU): 1 525 us per round.
+        //   dense_tm<21, 8, 3, 2> (fc4 + fc5 + heads, 16 groups per workgroup, one workgroup per CU): 1 490 us per round.
         // Options: infer_fc4_small_groups = the size up to which dense_small is considered at all (288: beyond it the weight
         // matrix is read from L2 7 x G times), infer_slab_groups >= 0 = a fixed line between dense_rag and the fused kernel
         // instead of the estimate (A/B, tests), dense_rag -1 = the round-5 three-slab kernel in dense_rag's place.
@@ -850,7 +850,7 @@ int cv_mfma_forward(cv_model *m, const float *x, int64_t n, float *out16, hipStr
         const rag_shape rsh = dense_rag_shape(G, 7, 3, cus, m->inf_rag_s);
         const double us_rag = rsh.us + 22.0 + 0.019 * G;                          // + fc5 with the heads on its tail (dense_tm<11, 4, 2>)
         const double us_small = 83.0 * (double)(((long)7 * G + 4 * cus - 1) / (4 * cus)) + 12.0;
-        const double us_wide = 1525.0 * (double)(((G + 15) / 16 + cus - 1) / cus) + (can_fused ? -17.0 : 85.0);   // (the launches the fused tail saves the pass / fc5 + heads on their own)
+        const double us_wide = 1490.0 * (double)(((G + 15) / 16 + cus - 1) / cus) + (can_fused ? -17.0 : 85.0);   // (the launches the fused tail saves the pass / fc5 + heads on their own)
         int form;                                                                  // 0 small, 1 three slabs, 2 all 21 tiles per wave (fused with fc5 + heads by variant bit 10)
         if (can_small && (!can_rag || us_small <= us_rag + 12.0)) form = 0;       // (fc5 follows on dense_small too: 12 us less)
         else if (!can_rag) form = 2;

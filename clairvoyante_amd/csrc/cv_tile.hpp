@@ -54,6 +54,22 @@ struct cv_stamp {
     unsigned long long *o_ = cv_wg_stamp + ((size_t)7 * 4096 + i_) * 4; o_[0] = cv_ph[0]; o_[1] = cv_ph[1]; o_[2] = cv_ph[2]; o_[3] = (unsigned long long)(w) | (cv_ph[3] << 8); } } while (0)
 #define CV_PHASE_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #endif
+// -DCV_DENSE_PHASES on top: the k step of the fused fc4 kernel (dense_tm, two groups per wave) in three intervals per
+// wave, summed over the loop (record id 6, which an inference pass leaves free): barrier exit -> first MFMA issued /
+// the MFMA block / last MFMA issued -> barrier exit.  Three s_memtime per step.  The two inside the step are tied to an
+// accumulator as a read-write operand -- behind the MFMA that wrote it, in front of the next one on it -- which leaves
+// the LDS reads free to move as in the shipped schedule (a sched_barrier that lets them cross lets s_memtime cross too).
+// Their values are only subtracted at the step's end, in front of the counted wait, so that no wait for them stands
+// behind the barrier.  The fourth word is the wave's index in its workgroup.  tools/gpu_dense_phases.py prints the shares.
+#ifdef CV_DENSE_PHASES
+#define CV_DPH_BEGIN unsigned long long cv_dph[3] = {0, 0, 0}, cv_dtb = 0, cv_dtl = 0, cv_dta = __builtin_amdgcn_s_memtime(), cv_dtp = cv_dta;
+#define CV_DPH_STAMP(t) do { t = __builtin_amdgcn_s_memtime(); } while (0)
+#define CV_DPH_STAMP_AT(t, a) asm volatile("s_memtime %0" : "=s"(t), "+v"(a))
+#define CV_DPH_SUM() do { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(cv_dtb), "+s"(cv_dtl));   /* the asm stamps are not tracked by the compiler */ \
+    cv_dph[0] += cv_dtb - cv_dta; cv_dph[1] += cv_dtl - cv_dtb; cv_dph[2] += cv_dta - cv_dtp; cv_dtp = cv_dtl; } while (0)
+#define CV_DPH_END(cond, w) do { cv_dph[2] += cv_dta - cv_dtp; if ((cond) && (threadIdx.x & 63) == 0) { const unsigned i_ = atomicAdd(&cv_wg_stamp_n[6], 1u) & 4095u; \
+    unsigned long long *o_ = cv_wg_stamp + ((size_t)6 * 4096 + i_) * 4; o_[0] = cv_dph[0]; o_[1] = cv_dph[1]; o_[2] = cv_dph[2]; o_[3] = (unsigned long long)(w); } } while (0)
+#endif
 #else
 #define CV_STAMP_BEGIN
 #define CV_STAMP_END(cond, kid) do { } while (0)
@@ -62,6 +78,13 @@ struct cv_stamp {
 #define CV_PHASE_BEGIN
 #define CV_PHASE(i) do { } while (0)
 #define CV_PHASE_END(cond, w) do { } while (0)
+#endif
+#ifndef CV_DPH_BEGIN
+#define CV_DPH_BEGIN
+#define CV_DPH_STAMP(t) do { } while (0)
+#define CV_DPH_STAMP_AT(t, a) do { } while (0)
+#define CV_DPH_SUM() do { } while (0)
+#define CV_DPH_END(cond, w) do { } while (0)
 #endif
 #ifndef CV_PHASE_DRAIN
 #define CV_PHASE_DRAIN() do { } while (0)
